@@ -11,9 +11,15 @@ WaveformModes series that is already resident in HBM.  N = 1: workload cfg3 of B
 (h, ell = 2..16, 285 modes, 1e5 time steps, 37 x 37 grid).  N > 1: workload cfg4, the SAME transformation of a
 1e6-step series whose time axis is sharded over the N ranks (STRONG scaling: total work fixed; BASELINE.json
 configs[3] / north star): the input-mode halos are exchanged over RCCL point-to-point inside the timed region, `value`
-is the whole-job rate, and before the sharded loop rank 0 transforms the whole 1e6-step series on its own GPU so that
-the line carries its own single-GPU reference (`strong_scaling`).  `--workload` overrides (cfg3 with N > 1 = the weak
+is the whole-job rate, and with --full, before the sharded loop, rank 0 transforms the whole 1e6-step series on its own GPU
+so that the line carries its own single-GPU reference (`strong_scaling`).  `--workload` overrides (cfg3 with N > 1 = the weak
 scaling of round 1: 1e5 steps per rank).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  `--full` adds everything
+else the benchmark measures or checks: the rocprofv3 --pmc child passes behind `roofline.traffic`, the CPU baselines,
+the `rotation` / `boost_free` / `abd_boost_free` sub-records, and with N > 1 rank 0's single-GPU pass of the whole series
+with the parity of the sharded result against it.  `--dump-outputs DIR` writes what the last timed step returned (see
+dump_outputs) for output-for-output comparisons of two builds: the inputs are seeded, identical from run to run.
 """
 import argparse
 import json
@@ -121,6 +127,33 @@ def committed_pmc_traffic(workload, world, per_gpu):
         if kname.startswith(DOMINANT_KERNEL) and "traffic_bytes" in counters:
             return counters["traffic_bytes"], f"{name} (tools/run_profiles.sh on kernel sources {stamp} = this build), 2 x FETCH_SIZE + WRITE_SIZE"
     return None, f"{name} has no row for {DOMINANT_KERNEL}"
+
+
+DUMP_BYTES = 60 * 2**20  # --dump-outputs: at most this much in all, over every rank (under 64 MB with the .npy headers)
+
+
+def dump_outputs(directory, t, data, axis=0, suffix="", budget=DUMP_BYTES):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the output times `t<suffix>.npy` and the modes
+    `data<suffix>.npy` (float64, real and imaginary parts on a last axis of 2; output times along `axis`).  Where the modes exceed
+    the budget, a fixed seeded sample of output times (in increasing order) is written; `data_rows<suffix>.npy` holds their
+    indices.  `data`: a torch tensor (read back after the timed region) or a numpy array."""
+    t = np.asarray(t, dtype=np.float64)
+    n = int(data.shape[axis])
+    row_bytes = 16 * int(np.prod(data.shape)) // max(n, 1)
+    k = int(min(n, max(1, (budget - t.nbytes) // (row_bytes + 8))))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    if isinstance(data, np.ndarray):
+        sel = np.take(data, rows, axis=axis)
+        sel = np.stack([sel.real, sel.imag], axis=-1).astype(np.float64)
+    else:
+        import torch
+
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=data.device)
+        sel = torch.view_as_real(data.index_select(axis, idx)).cpu().numpy().astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, f"t{suffix}.npy"), t)
+    np.save(os.path.join(directory, f"data{suffix}.npy"), sel)
+    np.save(os.path.join(directory, f"data_rows{suffix}.npy"), rows.astype(np.float64))
 
 
 def launch_ranks(n, argv):
@@ -522,6 +555,8 @@ def inprocess_line(args):
         t_out, out = go(devices, pieces)
     elapsed = time.perf_counter() - t0
     out = np.array(out)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, t_out, out, axis=1 if abd else 0)
     # parity inside the run: the same number of time shards on ONE context (bit for bit), and the default one-context call (rounding)
     t_one, out_one = go(None, pieces)
     same_bits = bool(np.array_equal(t_one, t_out) and np.array_equal(out_one, out))
@@ -591,7 +626,15 @@ def main():
     ap.add_argument("--inprocess", type=int, default=0, metavar="N",
                     help="ONE process, N devices, host arrays in and out: engine.transform_modes(devices=[0..N-1]) (no process group; with fewer "
                     "devices than N the contexts share them: parity only).  Prints its own line; PCIe-inclusive, not the headline `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks: live rocprofv3 --pmc passes (roofline.traffic), CPU baselines, the "
+                    "rotation / boost_free / abd_boost_free sub-records; N > 1: rank 0's single-GPU pass and the parity against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output times and modes of the last timed step as DIR/*.npy (float64; a seeded sample of the "
+                    "output times where the modes exceed 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.inprocess:
         return inprocess_line(args)
     if args.workload is None:
@@ -614,7 +657,7 @@ def main():
     under_profiler = any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_LIBRARY_CTOR"))
     if under_profiler:  # (a profiler's preloaded library has initialised the GPU already: no child programs from here)
         traffic_note = "not measured: this run is itself under a profiler"
-    if world == 1 and not pmc_child and not args.no_live_pmc and args.workload == "cfg3" and not under_profiler:
+    if args.full and world == 1 and not pmc_child and not args.no_live_pmc and args.workload == "cfg3" and not under_profiler:
         child = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-live-pmc", "--workload", args.workload,
                  "--boost-scale", str(args.boost_scale), "--time-axis", args.time_axis] + (["--n-times", str(args.n_times)] if args.n_times else [])
         traffic, traffic_note = live_pmc_traffic(child)
@@ -745,7 +788,8 @@ def main():
     # ---- cfg4 / cfg5 on several GPUs: the whole series on ONE GPU (rank 0's), in the same run: the reference of the strong-scaling line
     n1 = None
     whole_out = None
-    if strong and world > 1 and not args.no_n1_reference:
+    n1_reference = args.full and not args.no_n1_reference
+    if strong and world > 1 and n1_reference:
         if rank == 0:
             if abd:
                 _, whole_host, _ = synthetic.abd_workload(args.workload, n_times=n_global, axis=args.time_axis)
@@ -783,8 +827,8 @@ def main():
     last = {}
 
     def step():
-        _, rows, _ = st(local, out=out)
-        last["rows"] = rows  # (time shards: a view of `out`; grid columns: this rank's block of the reduce-scatter)
+        t_out, rows, _ = st(local, out=out)
+        last["t"], last["rows"] = t_out, rows  # (time shards: a view of `out`; grid columns: this rank's block of the reduce-scatter)
         return rows.shape[1 if abd else 0]
 
     def fence():
@@ -810,12 +854,15 @@ def main():
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["t"], last["rows"], axis=1 if abd else 0, suffix=f"_rank{rank}" if world > 1 else "",
+                     budget=DUMP_BYTES // world)
 
     # ---- cfg4 / cfg5, N > 1: the shards' outputs of the LAST timed step, reassembled on rank 0, against rank 0's own single-GPU
     # transform of the whole series from the same run (the check of the RCCL path that only hardware can give; the same
     # comparison on one device is tests/test_gpu_full_size.py::test_cfg4_eight_shards_equal_whole, bar 1e-14 x scale)
     parity = None
-    if strong and world > 1 and not args.no_parity and not args.no_n1_reference:
+    if strong and world > 1 and not args.no_parity and n1_reference:
         comm_dev = dev if backend == "nccl" else torch.device("cpu")
         counts = torch.zeros(world, dtype=torch.int64, device=comm_dev)
         counts[rank] = int(n_out)
@@ -895,7 +942,7 @@ def main():
                 )
                 + f"{per_gpu} time steps per GPU ({n_global} total"
                 + ("" if args.time_axis == "uniform" else f"; NON-UNIFORM time axis '{args.time_axis}': synthetic.time_axis") + "), " + workload_terms
-                + (" (cfg2's second step; its first, the rotor series, is the `rotation` line of the default run at this l range: tools/bench_rotation.py 8)"
+                + (" (cfg2's second step; its first, the rotor series, is the `rotation` line of the --full run at this l range: tools/bench_rotation.py 8)"
                    if args.workload == "cfg2" else "") + ", "
                 f"{n_theta}x{n_theta} grid, {n_out} output steps on rank 0",
                 "ranks": dict({"world_size": dist.get_world_size() if world > 1 else 1, "backend": dist.get_backend() if world > 1 else None},
@@ -1001,13 +1048,13 @@ def main():
                 },
                 "ideal_fusion_bytes_per_step": 2 * (16 * n_modes + 8),
             }
-        if world == 1 and args.cpu_sample > 0 and not abd:
+        if args.full and world == 1 and args.cpu_sample > 0 and not abd:
             line["cpu_baseline"] = cpu_baseline(spec, args.cpu_sample)
             line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(spec, args.cpu_sample)
-        if world == 1 and not abd and not pmc_child:
+        if args.full and world == 1 and not abd and not pmc_child:
             line["rotation"] = rotation_line(local, ell_max, ctx, 3000 if args.cpu_sample > 0 else 0)
             line["boost_free"] = boost_free_line(local, t_global, kw, n_theta, ell_max, ctx)
-            if args.workload == "cfg3" and args.cpu_sample > 0:  # (the default run; the profiling commands pass --cpu-sample 0)
+            if args.workload == "cfg3" and args.cpu_sample > 0:  # (the --full run; the profiling commands pass --cpu-sample 0)
                 del local
                 torch.cuda.empty_cache()
                 line["abd_boost_free"] = abd_boost_free_line(ctx)

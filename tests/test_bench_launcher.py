@@ -75,7 +75,7 @@ def test_committed_pmc_summary_is_reported_only_for_the_build_it_was_taken_on(tm
 
 @pytest.mark.gpu
 def test_two_rank_cfg4_line_carries_its_own_parity_check():
-    rc, line, err = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--n-times", "60000"], timeout=900)
+    rc, line, err = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--n-times", "60000", "--full"], timeout=900)
     assert rc == 0, err
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["ranks"]["world_size"] == 2
     par = line["strong_scaling"]["parity"]
@@ -86,10 +86,10 @@ def test_two_rank_cfg4_line_carries_its_own_parity_check():
 
 @pytest.mark.gpu
 def test_two_rank_cfg5_strong_scaling_line_carries_its_own_parity_check():
-    """`--workload cfg5 --gpus N`: total fixed (here 4000 steps instead of 2e5), rank 0 transforms the whole six-field series
+    """`--workload cfg5 --gpus N --full`: total fixed (here 4000 steps instead of 2e5), rank 0 transforms the whole six-field series
     first, the two shards' outputs are gathered and compared with it (scri/asymptotic_bondi_data/transformations.py:391-412 is what
     the shards reproduce); two ranks share the box's one GPU (gloo dry run)."""
-    rc, line, err = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg5", "--n-times", "4000"], timeout=900)
+    rc, line, err = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg5", "--n-times", "4000", "--full"], timeout=900)
     assert rc == 0, err
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["ranks"]["world_size"] == 2
     ss = line["strong_scaling"]
@@ -97,3 +97,53 @@ def test_two_rank_cfg5_strong_scaling_line_carries_its_own_parity_check():
     par = ss["parity"]
     assert par["rows_compared"] == par["rows_of_n1_result"] > 3900
     assert par["within_bar"], par
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """`--dump-outputs`: output times in full, the modes as float64 (re, im) -- all of them where they fit, otherwise the same
+    seeded sample of output times on every run -- under 64 MB in all"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(3)
+    t = np.linspace(0.0, 1.0, 40000)
+    data = rng.normal(size=(40000, 285)) + 1j * rng.normal(size=(40000, 285))  # 182 MB of modes: sampled
+    for name, arr in (("a", torch.from_numpy(data)), ("b", data)):
+        bench.dump_outputs(str(tmp_path / name), t, arr)
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["data.npy", "data_rows.npy", "t.npy"]
+        assert sum(p.stat().st_size for p in (tmp_path / name).iterdir()) < 64e6
+        got, rows = np.load(tmp_path / name / "data.npy"), np.load(tmp_path / name / "data_rows.npy")
+        assert got.dtype == np.float64 and rows.dtype == np.float64 and got.shape == (rows.size, 285, 2) and 1000 < rows.size < 40000
+        assert np.all(np.diff(rows) > 0)
+        assert np.array_equal(got[..., 0] + 1j * got[..., 1], data[rows.astype(np.int64)])
+        assert np.array_equal(np.load(tmp_path / name / "t.npy"), t)
+    assert np.array_equal(np.load(tmp_path / "a" / "data_rows.npy"), np.load(tmp_path / "b" / "data_rows.npy"))
+    six = data[:600, :25].reshape(6, 100, 25)  # six fields: output times along axis 1, small enough to go whole
+    bench.dump_outputs(str(tmp_path / "c"), t[:100], six, axis=1, suffix="_rank1")
+    got = np.load(tmp_path / "c" / "data_rank1.npy")
+    assert got.shape == (6, 100, 25, 2) and np.array_equal(got[..., 0] + 1j * got[..., 1], six)
+    assert np.array_equal(np.load(tmp_path / "c" / "data_rows_rank1.npy"), np.arange(100.0))
+
+
+def test_steps_must_be_positive():
+    rc, line, err = _run(["--gpus", "1", "--steps", "0"], timeout=120)
+    assert rc != 0 and line is None and "--steps" in err
+
+
+@pytest.mark.gpu
+def test_plain_one_gpu_line_and_its_outputs(tmp_path):
+    """The plain run: the headline line without the secondary measurements of `--full`, and the last step's outputs"""
+    import numpy as np
+
+    rc, line, err = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert rc == 0, err
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f64" and line["higher_is_better"]
+    assert line["unit"] == "timesteps/s" and line["ms_per_step"] > 0 and abs(line["value"] - 1e5 * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    assert not {"cpu_baseline", "cpu_baseline_all_cores", "rotation", "boost_free", "abd_boost_free"} & set(line)
+    t, data, rows = (np.load(tmp_path / f) for f in ("t.npy", "data.npy", "data_rows.npy"))
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) < 64e6
+    assert data.shape == (rows.size, 285, 2) and rows[-1] < t.size and np.all(np.isfinite(data)) and np.abs(data).max() > 0

@@ -2,7 +2,7 @@
 # A/B of two builds of the library on the bench's secondary lines (boost_free synthesis, rotation): base = scri_amd/libscri_amd_base.so
 for lib in scri_amd/libscri_amd_base.so scri_amd/libscri_amd.so; do
   for i in 1 2; do
-    SCRI_AMD_LIB_PATH=$PWD/$lib python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-live-pmc 2>/dev/null | python -c "
+    SCRI_AMD_LIB_PATH=$PWD/$lib python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-live-pmc --full 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,10 +5,10 @@ set -u
 OUT=gpurun_out
 mkdir -p $OUT
 bash tools/run_profiles.sh > $OUT/run_profiles.log 2>&1
-python3 bench.py --workload cfg2 --cpu-sample 0 2>/dev/null | tail -1 > $OUT/bench_cfg2_line.json
-python3 bench.py --workload cfg4 --gpus 1 --steps 5 --warmup 2 --cpu-sample 0 2>/dev/null | tail -1 > $OUT/bench_cfg4_1gpu_line.json
+python3 bench.py --workload cfg2 --cpu-sample 0 --full 2>/dev/null | tail -1 > $OUT/bench_cfg2_line.json
+python3 bench.py --workload cfg4 --gpus 1 --steps 5 --warmup 2 --cpu-sample 0 --full 2>/dev/null | tail -1 > $OUT/bench_cfg4_1gpu_line.json
 python3 bench.py --workload cfg5 --steps 5 --warmup 2 --cpu-sample 0 2>/dev/null | tail -1 > $OUT/bench_cfg5_shard_line.json
-python3 bench.py --boost-scale 26.7 --cpu-sample 0 --no-live-pmc 2>/dev/null | tail -1 > $OUT/bench_cfg3_beta1e-2.json
+python3 bench.py --boost-scale 26.7 --cpu-sample 0 --no-live-pmc --full 2>/dev/null | tail -1 > $OUT/bench_cfg3_beta1e-2.json
 for a in "16 100000" "16 1000000" "8 100000" "24 100000"; do python3 tools/bench_rotation.py $a 2>/dev/null | tail -1; done > $OUT/rotation_lines.jsonl
 for i in 1 2 3; do python3 tools/host_mode_rate.py 2>/dev/null | tail -1; done > $OUT/host_mode_rate.txt
 python3 tools/superrest_timing.py 100000 12 250 > $OUT/superrest_timing.txt 2>&1
