@@ -182,7 +182,8 @@ int bms_shard_plan(bms_ctx* ctx, const double* t, int64_t n_times, const bms_tra
                    int64_t out_i1, int64_t need_rows[2], int64_t window[2]);
 /* bms_transform_modes for HOST arrays as a three-stage pipeline over `pieces` time shards of the output range: upload of
  * shard k + 1, kernels of shard k and download of shard k - 1 run side by side on three streams (a long series in host memory
- * waits for PCIe, not for the kernels).  in->mem must be BMS_HOST, no auxiliary fields.  data_out: host
+ * waits for PCIe, not for the kernels).  in->mem must be BMS_HOST; psi companions (n_aux 0..4, host rows like the data, any
+ * aux_ld >= their number of modes) travel up with the rows of every shard.  data_out: host
  * c16[window rows][n_out], t_out f8[window rows] (size them with bms_output_window); full rate needs page-locked arrays
  * (bms_host_alloc for the result, bms_host_register for a caller's input).  Same results as the sharded path. */
 int bms_transform_modes_pipelined(bms_ctx* ctx, const bms_wm_input* in, const bms_transformation* tr, int pieces, double* t_out,

@@ -186,6 +186,9 @@ class AsymptoticBondiData:
         # scri_amd extension (not in the reference): `group` = a torch.distributed process group over whose ranks the time axis is
         # split; this object then holds THIS rank's contiguous block of rows, and so does the result (scri_amd/sharding.py)
         group = kwargs.pop("group", None)
+        # ... and how the ranks split the work: "rows" (time shards + halo exchange), "columns" (grid columns, for strong boosts) or
+        # "auto" (scri_amd.sharding.choose_partition); without `group` it means nothing and is ignored
+        partition = kwargs.pop("partition", "auto")
         devices = kwargs.pop("devices", None)  # the GPUs of this process a long host-memory series is dealt over (engine.transform_abd)
         frame_rotation, boost_velocity, supertranslation, working_ell_max, output_ell_max = _process_transformation_kwargs(
             self.ell_max, **kwargs
@@ -197,7 +200,7 @@ class AsymptoticBondiData:
 
             u_global, have = sharding.gather_time_axis(self._time, group, ctx=self._ctx)
             u_new, raw_new, _ = sharding.transform_abd_sharded(self._raw_dev if self._device else self._raw_data, u_global, self.ell_max, tr,
-                                                              group=group, have=have, ctx=self._ctx)
+                                                              group=group, have=have, ctx=self._ctx, partition=partition)
             if self._device:
                 return type(self)(np.array(u_new), output_ell_max, ctx=self._ctx, _raw=raw_new.contiguous(), device=True)
             return type(self)(u_new, output_ell_max, ctx=self._ctx, _raw=np.ascontiguousarray(raw_new))

@@ -78,7 +78,8 @@ extern "C" int bms_transform_modes_shard(bms_ctx* c, const bms_wm_input* in, con
 // way at 57 GB/s = 8 ms per direction against 6 ms of kernels): one call does upload -> kernels -> download one after the
 // other (26 ms), this does them side by side.  Uploads run at full rate from page-locked memory (bms_host_register /
 // bms_host_alloc); from pageable memory the runtime stages them.  data_out: host c16[i_hi - i_lo][n_out] (best page-locked).
-// Results are those of the sharded path (equal to the one-call path to rounding).  No psi companions (aux) here.
+// Results are those of the sharded path (equal to the one-call path to rounding).  The psi companions (in->aux_data, host rows
+// like the data) travel up with every piece's rows, on the same stream and under the same event.
 extern "C" int bms_transform_modes_pipelined(bms_ctx* c, const bms_wm_input* in, const bms_transformation* tr, int pieces,
                                              double* t_out, void* data_out, int64_t* n_times_out) try {
   return bms_transform_modes_pipelined_part(c, in, tr, pieces, 0, pieces < 1 ? 1 : pieces, t_out, data_out, n_times_out);
@@ -93,11 +94,21 @@ extern "C" int bms_transform_modes_pipelined_part(bms_ctx* c, const bms_wm_input
                                                   int piece1, double* t_out, void* data_out, int64_t* n_times_out) try {
   if (!c) return BMS_ERR_INVALID;
   if (!in || !tr || !t_out || !data_out || !n_times_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (in->mem != BMS_HOST || in->n_aux != 0) return fail(c, BMS_ERR_INVALID, "the pipelined path takes host data without auxiliary fields");
+  if (in->mem != BMS_HOST) return fail(c, BMS_ERR_INVALID, "the pipelined path takes host data");
   if (!in->t || !in->data) return fail(c, BMS_ERR_INVALID, "NULL argument");
   if (in->ell_min < 0 || in->ell_max < in->ell_min) return fail(c, BMS_ERR_INVALID, "bad ell range");
   if (in->ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", in->ell_max, MAX_ELL);
   if (in->ld < LM_total_size(in->ell_min, in->ell_max)) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
+  // psi companions travel with the data rows of every piece: all of them are checked before the first copy is issued
+  if (in->n_aux < 0 || in->n_aux > 4) return fail(c, BMS_ERR_INVALID, "0..4 auxiliary fields, got %d", in->n_aux);
+  int aux_modes[4] = {0, 0, 0, 0};
+  for (int a = 0; a < in->n_aux; ++a) {
+    if (!in->aux_data[a]) return fail(c, BMS_ERR_INVALID, "auxiliary field %d is NULL", a);
+    if (in->aux_ell_min[a] < 0 || in->aux_ell_max[a] < in->aux_ell_min[a]) return fail(c, BMS_ERR_INVALID, "bad l range of auxiliary field %d", a);
+    if (in->aux_ell_max[a] > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "auxiliary field %d: ell_max = %d is beyond %d", a, in->aux_ell_max[a], MAX_ELL);
+    aux_modes[a] = LM_total_size(in->aux_ell_min[a], in->aux_ell_max[a]);
+    if (in->aux_ld[a] < aux_modes[a]) return fail(c, BMS_ERR_INVALID, "auxiliary field %d: row stride smaller than its number of modes", a);
+  }
   if (tr->ell_max_out < std::abs(in->spin_weight)) return fail(c, BMS_ERR_INVALID, "ell_max_out < |s|");
   HIP_TRY(c, hipSetDevice(c->device));
   const int64_t n = in->n_times;
@@ -143,6 +154,13 @@ extern "C" int bms_transform_modes_pipelined_part(bms_ctx* c, const bms_wm_input
   if ((rc = dev_buf_t(c, "pipe_in1", (size_t)max_rows * n_modes * 2, &d_in[1]))) return rc;
   if ((rc = dev_buf_t(c, "pipe_out0", (size_t)max_out * n_out * 2, &d_out[0]))) return rc;
   if ((rc = dev_buf_t(c, "pipe_out1", (size_t)max_out * n_out * 2, &d_out[1]))) return rc;
+  double* d_aux[4][2] = {};
+  for (int a = 0; a < in->n_aux; ++a)
+    for (int b = 0; b < 2; ++b) {
+      char nm[32];
+      snprintf(nm, sizeof nm, "pipe_aux%d_%d", a, b);
+      if ((rc = dev_buf_t(c, nm, (size_t)max_rows * aux_modes[a] * 2, &d_aux[a][b]))) return rc;
+    }
   if (!c->pipe_up) {
     HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
     HIP_TRY(c, create_download_stream(c));
@@ -174,12 +192,16 @@ extern "C" int bms_transform_modes_pipelined_part(bms_ctx* c, const bms_wm_input
       const hipError_t ew = hipStreamWaitEvent(c->pipe_up, ev_c[k - 2], 0);
       if (ew != hipSuccess) return ew;
     }
-    hipError_t e = in->ld == n_modes
-                       ? hipMemcpyAsync(d_in[(k - p0) & 1], host_in + (size_t)r0[k] * in->ld * 16, (size_t)rows * n_modes * 16, hipMemcpyHostToDevice, c->pipe_up)
-                       : hipMemcpy2DAsync(d_in[(k - p0) & 1], (size_t)n_modes * 16, host_in + (size_t)r0[k] * in->ld * 16, (size_t)in->ld * 16,
-                                          (size_t)n_modes * 16, (size_t)rows, hipMemcpyHostToDevice, c->pipe_up);
+    // rows [r0, r1) of one field, packed (row stride = its number of modes) into the piece's buffer
+    auto rows_up = [&](double* dst, const void* src, int64_t ld, int nm) -> hipError_t {
+      const char* from = (const char*)src + (size_t)r0[k] * ld * 16;
+      return ld == nm ? hipMemcpyAsync(dst, from, (size_t)rows * nm * 16, hipMemcpyHostToDevice, c->pipe_up)
+                      : hipMemcpy2DAsync(dst, (size_t)nm * 16, from, (size_t)ld * 16, (size_t)nm * 16, (size_t)rows, hipMemcpyHostToDevice, c->pipe_up);
+    };
+    hipError_t e = rows_up(d_in[(k - p0) & 1], host_in, in->ld, n_modes);
+    for (int a = 0; a < in->n_aux && e == hipSuccess; ++a) e = rows_up(d_aux[a][(k - p0) & 1], in->aux_data[a], in->aux_ld[a], aux_modes[a]);
     if (e != hipSuccess) return e;
-    return hipEventRecord(ev_up[k], c->pipe_up);
+    return hipEventRecord(ev_up[k], c->pipe_up);  // (covers the companions' rows too)
   };
   PieceTables shared_tables;
   struct AsyncScope {
@@ -212,6 +234,10 @@ extern "C" int bms_transform_modes_pipelined_part(bms_ctx* c, const bms_wm_input
     piece.data = d_in[(k - p0) & 1];
     piece.ld = n_modes;
     piece.mem = BMS_DEVICE;
+    for (int a = 0; a < in->n_aux; ++a) {
+      piece.aux_data[a] = d_aux[a][(k - p0) & 1];
+      piece.aux_ld[a] = aux_modes[a];
+    }
     const bms_shard sh = {r0[k], r1[k] - r0[k], cut[k], cut[k + 1], 0, 0};
     int64_t got = 0, first = 0;
     rc = transform_modes_impl(c, &piece, tr, &sh, t_out + (cut[k] - i_lo), d_out[(k - p0) & 1], &got, &first, nullptr);

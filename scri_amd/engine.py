@@ -407,14 +407,16 @@ def transform_modes(
     the returned tuple then has the first global index appended.  Two more entries (col_part, col_parts) select a
     part of the grid columns (include/scri_amd.h, bms_shard): the output is then that part's contribution, to be
     summed over the parts.
-    devices (host mode, no shard, no aux): the GPUs of this process the time shards of the pipelined call are dealt over, one
+    devices (host mode, no shard): the GPUs of this process the time shards of the pipelined call are dealt over, one
     context and one host thread per entry, e.g. [0, 1, ..., 7] (default: SCRI_AMD_DEVICES, else the one context `ctx`); every
-    device receives its own rows + halo at upload time.  pieces: the number of time shards (default PIPELINE_PIECES on one
-    context, pieces_for(devices) on several); the result depends on `pieces` only (to rounding), not on how they are dealt."""
+    device receives its own rows + halo at upload time, psi companions' rows included.  pieces: the number of time shards (default
+    PIPELINE_PIECES on one context, pieces_for(devices) on several); the result depends on `pieces` only (to rounding), not on how
+    they are dealt.  A call with psi companions takes the pipelined or dealt path only when it names `devices` or `pieces`:
+    neither SCRI_AMD_DEVICES nor auto_pieces applies to it."""
     if devices is None and not device and shard is None and not grid and not aux and np.asarray(data).nbytes >= PIPELINE_MIN_BYTES:
         devices = default_devices()  # (the environment's default is for LONG series: a short one is not worth k threads and k set-ups)
-    if devices is not None and (device or shard is not None or grid or aux):
-        raise ValueError("`devices` deals a whole host-memory series over several GPUs: no shard, no device pointers, no psi companions")
+    if devices is not None and (device or shard is not None or grid):
+        raise ValueError("`devices` deals a whole host-memory series over several GPUs: no shard, no device pointers, no grid output")
     ctx = _ctx(ctx) if not devices else contexts_for(devices[:1], first=ctx)[0]
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
@@ -438,6 +440,7 @@ def transform_modes(
     inp.ell_min, inp.ell_max = int(ell_min), int(ell_max)
     inp.spin_weight, inp.conformal_weight, inp.type_term = int(spin_weight), int(conformal_weight), int(type_term)
     inp.n_aux = len(aux)
+    aux_host = []
     for i, a in enumerate(aux):
         adata, amin, amax, aspin, acoeff, apower = a[:6]
         if device:
@@ -448,6 +451,7 @@ def transform_modes(
             if adata.shape != ((n if shard is None else int(shard[1])), LM_total_size(amin, amax)):
                 raise ValueError("auxiliary data shape mismatch")
             keep.append(adata)
+            aux_host.append(adata)
             inp.aux_data[i] = adata.ctypes.data
             inp.aux_ld[i] = adata.shape[1]
         inp.aux_ell_min[i], inp.aux_ell_max[i], inp.aux_spin[i] = int(amin), int(amax), int(aspin)
@@ -480,12 +484,15 @@ def transform_modes(
         return t_out[: n_new.value], out[: n_new.value]
     if not device:
         _lib.register_if_reused(data)  # an input array seen for the second time is page-locked in place: uploads at PCIe rate
+        if devices or pieces is not None:
+            for adata in aux_host:  # (the companions travel with every shard's rows: the same rate for them)
+                _lib.register_if_reused(adata)
     if devices:
         ctxs = contexts_for(devices, first=ctx)
         res = _transform_modes_multi(t, data, inp, transformation, n_out, ctxs, int(pieces or pieces_for(devices, n, ell_max, data.nbytes)))
         if res is not None:
             return res
-    elif shard is None and not aux and not os.environ.get("SCRI_AMD_NO_PIPELINE"):
+    elif shard is None and (not aux or pieces is not None) and not os.environ.get("SCRI_AMD_NO_PIPELINE"):
         chosen = int(pieces) if pieces is not None else auto_pieces(n, ell_max, data.nbytes)
         if pieces is not None or chosen >= 2:
             res = _transform_modes_pipelined(t, data, inp, transformation, n_out, ctx, pieces=chosen)

@@ -226,18 +226,23 @@ class ShardedTransform:
     (default: near-equal contiguous blocks, shard_bounds).  partition: "rows" (time shards + point-to-point halo exchange of
     input modes, plan A of SURVEY 8(e)), "columns" (every rank gathers the whole input, transforms its part of the grid
     columns over all times, one reduce-scatter of the output rows: plan B, for boosts whose time skew makes the row halos
-    overlap; WaveformModes only) or "auto" (choose_partition).  overlap=True ("rows", WaveformModes): the outputs that need
-    own rows only are transformed while the halos travel, the two edges afterwards (three engine calls instead of one).
+    overlap) or "auto" (choose_partition).  overlap=True ("rows", WaveformModes): the outputs that need own rows only are
+    transformed while the halos travel, the two edges afterwards (three engine calls instead of one).
+    aux (WaveformModes, BMS_TERM_PSI): the psi companions in the engine's tuple form (rows, ell_min, ell_max, spin, coeff, power),
+    `rows` this rank's rows of the companion (the same rows as the data; None: handed to every call as `aux_rows`).  They travel
+    with the data: side by side with it in the one exchange buffer ("rows"), in the one all-gather ("columns").
 
     Calling the object with this rank's rows returns (t_out, rows_out, first): rows_out[k] is the output sample whose global
     INPUT index is first + k ("rows": the rank's own outputs, consecutive over the ranks; "columns": block `rank` of the
     reduce-scatter).  Rows may be a torch tensor on the context's device (stays in HBM, RCCL moves the halos device to
     device), or a host array / CPU tensor (the shard call uploads it).  `compute`: the per-shard arithmetic,
-    compute(t_global, ext_rows, shard) -> (t_out, data_out, first) with shard = (row0, n_rows, out_i0, out_i1[, part, parts]);
-    the default is the engine (C ABI) -- the CPU tests of the multi-rank logic pass the oracle."""
+    compute(t_global, ext_rows, shard[, ext_aux]) -> (t_out, data_out, first) with shard = (row0, n_rows, out_i0, out_i1[, part, parts])
+    and ext_aux (only with companions) the companions' tuples with their rows [row0, row0 + n_rows); the default is the engine
+    (C ABI) -- the CPU tests of the multi-rank logic pass the oracle.  "columns" of kind "abd": t_out / first are the part call's own
+    (its window divides by gamma, `window` above is the WaveformModes flavour)."""
 
     def __init__(self, kind, t_global, transformation, ell_min=None, ell_max=None, spin_weight=None, conformal_weight=None, type_term=None,
-                 group=None, have=None, partition="auto", overlap=False, ctx=None, compute=None):
+                 group=None, have=None, partition="auto", overlap=False, ctx=None, compute=None, aux=()):
         import numpy as np
         import torch.distributed as dist
 
@@ -257,12 +262,20 @@ class ShardedTransform:
         else:
             self.have, self.need, self.window = plan(self.t_global, transformation, self.world, have=have)
         if partition == "auto":
-            partition = choose_partition(self.have, self.need) if kind == "modes" and self.world > 1 else "rows"
+            partition = choose_partition(self.have, self.need) if self.world > 1 else "rows"
         if partition not in ("rows", "columns"):
             raise ValueError(f"partition {partition!r}: 'auto', 'rows' or 'columns'")
-        if partition == "columns" and kind != "modes":
-            raise NotImplementedError("the column partition is wired in for WaveformModes series only")
         self.partition = partition
+        aux = [tuple(a) for a in aux]
+        if aux and kind != "modes":
+            raise ValueError("psi companions belong to WaveformModes series (kind 'modes')")
+        if len(aux) > 4 or any(len(a) != 6 for a in aux):
+            raise ValueError("aux: at most four (rows, ell_min, ell_max, spin, coeff, power) tuples")
+        self.aux_meta = [tuple(a[1:6]) for a in aux]  # (ell_min, ell_max, spin, coeff, power) per companion
+        self.aux_rows = [a[0] for a in aux]
+        # columns of the exchange buffer: the data, then every companion
+        widths = [self.n_modes_in if kind == "modes" else 0] + [(lmax + 1) ** 2 - lmin**2 for lmin, lmax, *_ in self.aux_meta]
+        self._col_off = [sum(widths[:k]) for k in range(len(widths) + 1)]
         self._compute = compute
         i0, i1 = self.have[self.rank]
         self.own = i1 - i0
@@ -310,24 +323,35 @@ class ShardedTransform:
 
     # -- the per-shard arithmetic: the engine through the C ABI
     def _engine_call(self, ext, shard, out=None):
-        """ext: torch tensor (device of the context or CPU) or numpy rows -> (t_out, rows_out, first)"""
+        """ext: torch tensor (device of the context or CPU) or numpy rows -> (t_out, rows_out, first).  With companions `ext` holds
+        the data and the companions side by side (the columns of the exchange buffer)."""
         import numpy as np
         import torch
 
         from . import engine
 
+        ext, ext_aux = self._split_columns(ext)
         if self._compute is not None:
-            host = ext.cpu().numpy() if isinstance(ext, torch.Tensor) else np.asarray(ext)
-            return self._compute(self.t_global, host, tuple(int(x) for x in shard))
+            def host_of(x):
+                return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+            shard = tuple(int(x) for x in shard)
+            if not ext_aux:
+                return self._compute(self.t_global, host_of(ext), shard)
+            return self._compute(self.t_global, host_of(ext), shard, [(host_of(r),) + m for r, m in zip(ext_aux, self.aux_meta)])
         on_device = isinstance(ext, torch.Tensor) and ext.device.type == "cuda"
         if on_device:
             self._sync_before_engine(ext)  # (whatever torch queued on its stream -- copies, halo rows -- is in place before the kernels read it)
         if not on_device:
-            host = np.ascontiguousarray(ext.numpy() if isinstance(ext, torch.Tensor) else ext)
+            def host_of(x):
+                return np.ascontiguousarray(x.numpy() if isinstance(x, torch.Tensor) else x)
+
+            host = host_of(ext)
             if self.kind == "abd":
                 return engine.transform_abd(self.t_global, host, self.ell_max, self.tr, ctx=self.ctx, shard=shard)
             return engine.transform_modes(self.t_global, host, self.ell_min, self.ell_max, self.spin_weight, self.conformal_weight,
-                                          self.type_term, self.tr, ctx=self.ctx, shard=shard)
+                                          self.type_term, self.tr, aux=[(host_of(r),) + m for r, m in zip(ext_aux, self.aux_meta)], ctx=self.ctx,
+                                          shard=shard)
         n_alloc = max(0, min(len(self.t_global), int(shard[3])) - max(0, int(shard[2])))
         if self.kind == "abd":
             # (the engine writes field f at out_ptr + f * (out_i1 - out_i0) * n_out and fills its first n_new rows)
@@ -336,15 +360,49 @@ class ShardedTransform:
                 out = torch.empty(shape, dtype=torch.complex128, device=ext.device)
             elif tuple(out.shape) != shape or not out.is_contiguous():
                 raise ValueError(f"`out` must be a contiguous complex128 tensor of shape {shape}")
-            t_out, n_new, first = engine.transform_abd(self.t_global, ext.data_ptr(), self.ell_max, self.tr, ctx=self.ctx, shard=shard[:4],
+            t_out, n_new, first = engine.transform_abd(self.t_global, ext.data_ptr(), self.ell_max, self.tr, ctx=self.ctx, shard=shard,
                                                        device=True, out_ptr=out.data_ptr())
             return t_out, out[:, :n_new], first
         if out is None:
             out = torch.empty((max(n_alloc, 1), self.n_modes_out), dtype=torch.complex128, device=ext.device)
+        # (a companion is a block of columns of the same rows: its own pointer, the buffer's row stride)
+        aux = [(r.data_ptr(),) + m + (r.stride(0),) for r, m in zip(ext_aux, self.aux_meta)]
         t_out, n_new, first = engine.transform_modes(
             self.t_global, ext.data_ptr(), self.ell_min, self.ell_max, self.spin_weight, self.conformal_weight, self.type_term, self.tr,
-            ctx=self.ctx, device=True, ld=ext.stride(0), out_ptr=out.data_ptr(), shard=shard)
+            aux=aux, ctx=self.ctx, device=True, ld=ext.stride(0), out_ptr=out.data_ptr(), shard=shard)
         return t_out, out[:n_new], first
+
+    def _split_columns(self, block):
+        """rows of the data and the companions side by side -> (data rows, [companion rows]) as column views"""
+        if not self.aux_meta:
+            return block, []
+        o = self._col_off
+        return block[:, : o[1]], [block[:, o[k] : o[k + 1]] for k in range(1, len(o) - 1)]
+
+    def _companions(self, aux_rows, n_rows):
+        """this call's rows of the companions as torch tensors (host or device, as handed in), checked against the declared shapes"""
+        import numpy as np
+        import torch
+
+        rows = list(aux_rows) if aux_rows is not None else self.aux_rows
+        if len(rows) != len(self.aux_meta) or any(r is None for r in rows):
+            raise ValueError(f"{len(self.aux_meta)} companions were declared: hand their rows to the constructor or to the call")
+        out = []
+        for k, r in enumerate(rows):
+            r = r if isinstance(r, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(r, dtype=np.complex128))
+            want = (n_rows, self._col_off[k + 2] - self._col_off[k + 1])
+            if tuple(r.shape) != want:
+                raise ValueError(f"companion {k}: rows of shape {tuple(r.shape)}, expected {want} (the rows of the data)")
+            out.append(r)
+        return out
+
+    def _with_companions(self, loc, aux_rows):
+        """this rank's data rows and its companions' rows side by side (one block for one exchange / all-gather)"""
+        import torch
+
+        if not self.aux_meta:
+            return loc
+        return torch.cat([loc] + [r.to(loc.device) for r in self._companions(aux_rows, loc.shape[0])], dim=1)
 
     def _sync_before_engine(self, tensor):
         """The halo rows were put in place by torch (RCCL completion waits and copies on torch's current stream).  With the
@@ -364,14 +422,21 @@ class ShardedTransform:
 
         if self.kind != "modes" or self.partition != "rows" or self.world == 1:
             return None
+        return self._own_block(like)[:, : self.n_modes_in]
+
+    def _own_block(self, like=None):
+        """this rank's own rows in the exchange buffer, every column (data + companions)"""
+        import torch
+
         n0, n1 = self.need[self.rank]
         if self._ext is None or (like is not None and (self._ext.device != like.device)):
             device = like.device if like is not None else "cpu"
-            self._ext = torch.empty((max(n1 - n0, self.own), self.n_modes_in), dtype=torch.complex128, device=device)
+            self._ext = torch.empty((max(n1 - n0, self.own), self._col_off[-1]), dtype=torch.complex128, device=device)
         lo = self.have[self.rank][0] - n0 if n1 > n0 else 0
         return self._ext[lo : lo + self.own]
 
-    def __call__(self, local, out=None):
+    def __call__(self, local, out=None, aux_rows=None):
+        """aux_rows: this call's rows of the companions (default: those given to the constructor)"""
         import numpy as np
         import torch
 
@@ -399,38 +464,50 @@ class ShardedTransform:
             return np.asarray(t_out), rows, int(first)
 
         if world == 1:
-            return back(self._engine_call(loc, (0, self.own, 0, self.own), out=out))
+            return back(self._engine_call(self._with_companions(loc, aux_rows), (0, self.own, 0, self.own), out=out))
         if self.partition == "columns":
-            full = replicate_rows(loc, self.have, group=self.group)
+            # one all-gather of the rows (data and companions side by side), this rank's part of the grid columns over all times, one
+            # reduce-scatter of the contributions along the output rows
+            full = replicate_rows(self._with_companions(loc, aux_rows), self.have, group=self.group, dim=rows_axis)
             n = len(self.t_global)
-            n_new_all = self.window[1] - self.window[0]
-            total, _ = padded_rows(n_new_all, world)
             t_all, part, first = self._engine_call(full, (0, n, 0, n, rank, world))
             if not isinstance(part, torch.Tensor):
                 part = torch.from_numpy(np.ascontiguousarray(part))
-            if self._part is None or self._part.device != part.device or self._part.shape[1] != part.shape[1]:
-                self._part = torch.zeros((total, part.shape[1]), dtype=torch.complex128, device=part.device)
+            if self.kind == "abd":  # [6, N', n_out]: the output rows first for the reduce-scatter; N' and the first index are the call's own
+                part = part[:, : len(t_all)].movedim(1, 0)
+                n_new_all, first_all = len(t_all), int(first)
+            else:
+                n_new_all, first_all = self.window[1] - self.window[0], self.window[0]
+            total, _ = padded_rows(n_new_all, world)
+            if self._part is None or self._part.device != part.device or self._part.shape[0] != total or self._part.shape[1:] != part.shape[1:]:
+                self._part = torch.zeros((total,) + tuple(part.shape[1:]), dtype=torch.complex128, device=part.device)
             self._part[: part.shape[0]] = part
             rows, (r0, r1) = reduce_scatter_rows(self._part, n_new_all, group=self.group)
-            return back((np.asarray(t_all)[r0:r1], rows, self.window[0] + r0))
+            if self.kind == "abd":
+                rows = rows.movedim(0, 1).contiguous()
+            return back((np.asarray(t_all)[r0:r1], rows, first_all + r0))
         n0, n1 = self.need[rank]
         if n1 <= n0:  # no output falls into this rank's rows: it only serves its neighbours' halos
-            exchange_halos(loc, self.have[rank], (i0, i0), self.have, self.need, group=self.group, dim=rows_axis)
+            exchange_halos(self._with_companions(loc, aux_rows), self.have[rank], (i0, i0), self.have, self.need, group=self.group, dim=rows_axis)
             shape = (6, 0, self.n_modes_out) if self.kind == "abd" else (0, self.n_modes_out)
             return back((np.empty(0), torch.empty(shape, dtype=torch.complex128, device=loc.device), max(i0, self.window[0])))
         if self.kind == "abd":
             ext = exchange_halos(loc, self.have[rank], self.need[rank], self.have, self.need, group=self.group, dim=1)
             return back(self._engine_call(ext, (n0, ext.shape[1], i0, i1), out=out))
-        view = self.own_rows_view(like=loc)
+        own_block = self._own_block(like=loc)  # (the data's columns of it: own_rows_view)
+        view = own_block[:, : self.n_modes_in]
         if view.data_ptr() != loc.data_ptr():
             view.copy_(loc)
+        if self.aux_meta:  # the companions' rows beside the data's: one exchange moves the halos of all of them
+            for k, r in enumerate(self._companions(aux_rows, self.own)):
+                own_block[:, self._col_off[k + 1] : self._col_off[k + 2]].copy_(r)
         ext_buf = self._ext[: n1 - n0]
         if self.interior is None:
-            ext = exchange_halos(view, self.have[rank], self.need[rank], self.have, self.need, group=self.group, out=ext_buf)
+            ext = exchange_halos(own_block, self.have[rank], self.need[rank], self.have, self.need, group=self.group, out=ext_buf)
             return back(self._engine_call(ext, (n0, ext.shape[0], i0, i1), out=out))
         # interior outputs from own rows while the halos travel; then the two edges from the completed rows
         a, b = self.interior
-        pending = exchange_halos(view, self.have[rank], self.need[rank], self.have, self.need, group=self.group, out=ext_buf, wait=False)
+        pending = exchange_halos(own_block, self.have[rank], self.need[rank], self.have, self.need, group=self.group, out=ext_buf, wait=False)
         if out is None and self._compute is None and view.device.type == "cuda":
             out = torch.empty((max(self.n_out_rows, 1), self.n_modes_out), dtype=torch.complex128, device=view.device)
         first_all = max(i0, self.window[0])
@@ -442,7 +519,7 @@ class ShardedTransform:
             dst = out[o0c - first_all : o1c - first_all] if out is not None else None
             return self._engine_call(src, (row0, src.shape[0], o0, o1), out=dst)
 
-        mid = piece(view, i0, a, b)  # own rows only: runs under the exchange
+        mid = piece(own_block, i0, a, b)  # own rows only: runs under the exchange
         ext = pending()
         parts = [p for p in (piece(ext, n0, i0, a), mid, piece(ext, n0, b, i1)) if p is not None]
         t_out = np.concatenate([np.asarray(p[0]) for p in parts]) if parts else np.empty(0)
@@ -456,15 +533,16 @@ class ShardedTransform:
 
 
 def transform_modes_sharded(local_rows, t_global, ell_min, ell_max, spin_weight, conformal_weight, type_term, transformation, group=None,
-                            have=None, partition="auto", overlap=False, ctx=None, compute=None):
+                            have=None, partition="auto", overlap=False, ctx=None, compute=None, aux=()):
     """This rank's output rows of the BMS transformation of a WaveformModes series sharded over `group` (one call; a caller
-    that repeats the transformation keeps a ShardedTransform).  Returns (t_out, rows_out, first_global_index)."""
+    that repeats the transformation keeps a ShardedTransform).  aux: the psi companions as (rows, ell_min, ell_max, spin, coeff,
+    power), `rows` this rank's rows of each.  Returns (t_out, rows_out, first_global_index)."""
     st = ShardedTransform("modes", t_global, transformation, ell_min, ell_max, spin_weight, conformal_weight, type_term, group=group, have=have,
-                          partition=partition, overlap=overlap, ctx=ctx, compute=compute)
+                          partition=partition, overlap=overlap, ctx=ctx, compute=compute, aux=aux)
     return st(local_rows)
 
 
-def transform_abd_sharded(local_raw, u_global, ell_max, transformation, group=None, have=None, ctx=None, compute=None):
+def transform_abd_sharded(local_raw, u_global, ell_max, transformation, group=None, have=None, ctx=None, compute=None, partition="auto"):
     """The same for AsymptoticBondiData storage: local_raw [6, own rows, (ell_max+1)^2] -> (u_out, raw_out [6, n', n_out], first)."""
-    st = ShardedTransform("abd", u_global, transformation, ell_max=ell_max, group=group, have=have, partition="rows", ctx=ctx, compute=compute)
+    st = ShardedTransform("abd", u_global, transformation, ell_max=ell_max, group=group, have=have, partition=partition, ctx=ctx, compute=compute)
     return st(local_raw)

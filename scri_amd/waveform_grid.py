@@ -157,9 +157,11 @@ def process_transformation_kwargs(ell_max, **kwargs):
     return supertranslation, ell_max_supertranslation, ell_max, n_theta, n_phi, frame_rotation, boost_velocity, kwargs
 
 
-def _prepare(w_modes, kwargs):
+def _prepare(w_modes, kwargs, companion_objects=False):
     """Everything from_modes does before touching the data (scri/waveform_grid.py:417-557): frame check, kwargs, the
-    type-specific term and the auxiliary Weyl scalars it needs.  Consumes the keys it understands from `kwargs`."""
+    type-specific term and the auxiliary Weyl scalars it needs.  Consumes the keys it understands from `kwargs`.
+    companion_objects: the first entry of every aux tuple is the companion WaveformModes itself, not its `.data` (which would
+    bring a device-resident one to the host)."""
     if w_modes.frameType != Inertial:
         raise ValueError(
             "\nInput waveform object must be in an inertial frame; "
@@ -193,7 +195,8 @@ def _prepare(w_modes, kwargs):
                     )
                 if w_tmp.n_times != w_modes.n_times:
                     raise ValueError("auxiliary waveform has a different number of time steps")
-                aux.append((w_tmp.data, w_tmp.ell_min, w_tmp.ell_max, w_tmp.spin_weight, comb(5 - dt, 5 - DT), DT - dt))
+                aux.append((w_tmp if companion_objects else w_tmp.data, w_tmp.ell_min, w_tmp.ell_max, w_tmp.spin_weight, comb(5 - dt, 5 - DT),
+                            DT - dt))
         elif dt not in [psi4, hdot, news]:
             warnings.warn(
                 "\nNo BMS transformation is implemented for waveform objects "
@@ -223,7 +226,7 @@ def transform(w_modes, **kwargs):
     # ... and `devices` = the GPUs of THIS process a long host-memory series is dealt over (engine.transform_modes; default SCRI_AMD_DEVICES)
     devices = kwargs.pop("devices", None)
     original_kwargs = kwargs.copy()
-    supertranslation, frame_rotation, boost_velocity, n_theta, n_phi, type_term, aux = _prepare(w_modes, kwargs)
+    supertranslation, frame_rotation, boost_velocity, n_theta, n_phi, type_term, aux = _prepare(w_modes, kwargs, companion_objects=group is not None)
     s = w_modes.spin_weight
 
     # to_modes argument checks (waveform_grid.py:291-297)
@@ -241,13 +244,24 @@ def transform(w_modes, **kwargs):
     if group is not None:
         from . import sharding
 
-        if trailing or aux:
-            raise NotImplementedError("a series sharded over a process group carries neither trailing data dimensions nor psi companions")
+        if trailing:
+            raise NotImplementedError("a series sharded over a process group carries no trailing data dimensions")
         t_global, have = sharding.gather_time_axis(w_modes.t, group, ctx=w_modes._ctx)
         resident = getattr(w_modes, "is_device_resident", False)
+        # the companions are rank-local too, with the rows of `w_modes`: they travel with its rows (same halo plan, same all-gather)
+        aux_rows = []
+        for a in aux:
+            c = a[0]
+            if c.n_times != w_modes.n_times or tuple(c._data_shape()[2:]):
+                raise ValueError("a psi companion of a sharded series holds this rank's rows of it, without trailing dimensions")
+            if resident:
+                rows_c = c._dev if c.is_device_resident else c.data
+            else:
+                rows_c = c._dev.cpu().numpy() if c.is_device_resident else c.data
+            aux_rows.append((rows_c,) + tuple(a[1:]))
         t_new, rows, _ = sharding.transform_modes_sharded(
             w_modes._dev if resident else w_modes.data, t_global, w_modes.ell_min, w_modes.ell_max, s, w_modes.conformal_weight, type_term, tr,
-            group=group, have=have, partition=partition, overlap=overlap_halo, ctx=w_modes._ctx,
+            group=group, have=have, partition=partition, overlap=overlap_halo, ctx=w_modes._ctx, aux=aux_rows,
         )
         if resident:
             dev_out, data_new = rows, np.empty((0, 0))
@@ -282,7 +296,7 @@ def transform(w_modes, **kwargs):
     else:
         t_new, data_new = engine.transform_modes(
             w_modes.t, w_modes.data, w_modes.ell_min, w_modes.ell_max, s, w_modes.conformal_weight, type_term, tr,
-            aux=aux, ctx=w_modes._ctx, devices=None if aux else devices,
+            aux=aux, ctx=w_modes._ctx, devices=devices,
         )
     if kwargs:
         warnings.warn("\nUnused kwargs passed to this function:\n{}".format(pprint.pformat(kwargs, width=1)))
