@@ -125,8 +125,8 @@ struct bms_ctx {
   std::vector<Slab> slabs;             // reserved by bms_ctx_reserve; the newest one with room serves the named buffers
   int delta_lmax = -1;                 // Delta tables cached up to this l
   int delta_mfma_lmax = -1;            // ... in the MFMA B-image packing
-  hipStream_t pipe_up = nullptr, pipe_down = nullptr;  // bms_transform_modes_pipelined: uploads and downloads beside the kernels
-  // set by bms_transform_modes_pipelined around its per-piece calls: the pieces share one transformation, so the
+  hipStream_t pipe_up = nullptr, pipe_down = nullptr;  // run_host_pipeline: uploads and downloads beside the kernels
+  // set by SharedPieceTables around the per-piece calls of a pipelined call: the pieces share one transformation, so the
   // per-direction tables are computed (and read back) once, and a piece returns without waiting for its kernels
   bool async_pieces = false;
   bool piece_tables_valid = false;
@@ -364,10 +364,71 @@ inline int run_dealt_over_contexts(bms_ctx* const* ctxs, int n_ctx, int pieces, 
 }
 
 
+// A series in HOST memory through the device in pieces k0 .. k1 - 1 over three streams, so that its transfers run beside the kernels
+// (the link is full duplex): piece k goes up on c->pipe_up (up(k, slot)), is computed on c->stream (compute(k, slot), a status) and
+// comes home on c->pipe_down (down(k, slot)), through two staging slots, slot = (k - k0) & 1; the host thread only enqueues.  The
+// transformations (bms_transform_*_pipelined_part) and the rotations of a host series in blocks (engine_rotate.hip) use it.
+//   compute k waits for upload k and, out of place, for download k - 2 (its output slot has left);
+//   upload k waits for download k - 2 in place (in_place: the download reads the upload's slot), for compute k - 2 otherwise;
+//   download k follows compute k: with host_waits the host synchronises on it before it enqueues the download, else pipe_down waits.
+//   (For the transformations stream waits instead of the host wait made no difference, three alternating runs: 14.9 / 15.1 / 13.7
+//   against 14.9 / 15.1 / 16.2 ms -- the transfers, not the kernels' gaps, set the time.)
+// Issue order: upload k0, compute k0, upload k0 + 1, download k0, then upload k + 1, compute k, download k -- the first piece of a
+// transformation reads its per-direction tables back with a blocking copy, which would wait for an upload queued before it.
+// In the rocprofv3 trace of the transformations the uploads run on a DMA engine beside the kernels; the downloads are executed by the
+// runtime as shader copies (__amd_rocclr_copyBuffer) that take turns with the compute kernels.  Storing the results straight into the
+// page-locked array from the analysis kernel (on a side stream, with a small grid) was tried: the stores leave at 42 GB/s instead of
+// 57 and every memory-bound kernel running beside them crawls -- 19.8 ms against 15.7 ms per cfg3 transform.
+// A HIP error fails the call with "<err_first>: ..." if the first upload could not be issued, "<err>: ..." otherwise.  Once anything is
+// enqueued every exit synchronises the three streams and returns the events.
+template <class Up, class Compute, class Down>
+int run_host_pipeline(bms_ctx* c, int k0, int k1, bool in_place, bool host_waits, const char* err_first, const char* err, Up up,
+                      Compute compute, Down down) {
+  if (!c->pipe_up) {
+    HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
+    HIP_TRY(c, create_download_stream(c));
+  }
+  const int n = k1 - k0;
+  std::vector<hipEvent_t> ev_up(n), ev_c(n), ev_dn(n);
+  for (int i = 0; i < n; ++i) ev_up[i] = ScopedTimer::get(c), ev_c[i] = ScopedTimer::get(c), ev_dn[i] = ScopedTimer::get(c);
+  auto send = [&](int i) -> hipError_t {  // upload of piece k0 + i
+    if (i >= n) return hipSuccess;
+    hipError_t e = i >= 2 ? hipStreamWaitEvent(c->pipe_up, in_place ? ev_dn[i - 2] : ev_c[i - 2], 0) : hipSuccess;
+    if (e == hipSuccess) e = up(k0 + i, i & 1);
+    return e == hipSuccess ? hipEventRecord(ev_up[i], c->pipe_up) : e;
+  };
+  int rc = BMS_OK;
+  hipError_t he = send(0);
+  const bool first_failed = he != hipSuccess;
+  for (int i = 0; i < n && he == hipSuccess; ++i) {
+    const int k = k0 + i, slot = i & 1;
+    if (i > 0 && (he = send(i + 1)) != hipSuccess) break;
+    if ((he = hipStreamWaitEvent(c->stream, ev_up[i], 0)) != hipSuccess) break;
+    if (!in_place && i >= 2 && (he = hipStreamWaitEvent(c->stream, ev_dn[i - 2], 0)) != hipSuccess) break;
+    if ((rc = compute(k, slot)) != BMS_OK) break;
+    if (i == 0 && (he = send(1)) != hipSuccess) break;
+    if ((he = hipEventRecord(ev_c[i], c->stream)) != hipSuccess) break;
+    if ((he = host_waits ? hipEventSynchronize(ev_c[i]) : hipStreamWaitEvent(c->pipe_down, ev_c[i], 0)) != hipSuccess) break;
+    if ((he = down(k, slot)) != hipSuccess) break;
+    if ((he = hipEventRecord(ev_dn[i], c->pipe_down)) != hipSuccess) break;
+  }
+  (void)hipStreamSynchronize(c->pipe_up);
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipStreamSynchronize(c->pipe_down);
+  for (int i = 0; i < n; ++i) c->event_pool.push_back(ev_up[i]), c->event_pool.push_back(ev_c[i]), c->event_pool.push_back(ev_dn[i]);
+  if (rc) return rc;
+  if (he != hipSuccess) return fail(c, BMS_ERR_HIP, "%s: %s", first_failed ? err_first : err, hipGetErrorString(he));
+  return BMS_OK;
+}
+
+
 // ====================================================================================================== tables of one transformation
 
 constexpr int SPLINE_TILE = 320;  // knots per (pixel group, tile) wave: measured sweep 128..640 on cfg3, best at 320 (halo re-reads 10 %)
 constexpr int SPLINE_HALO = 32;
+// input rows an output range reads beyond its knots on either side: bms_shard_plan, the pieces of the pipelined calls and the chunk
+// loops all take their rows from needed_rows (engine_tables.hip), so a shard planned by one holds what the others read
+constexpr int ROW_MARGIN = SPLINE_HALO + 2;
 
 inline long long round_up(long long a, long long b) { return (a + b - 1) / b * b; }
 
@@ -409,6 +470,37 @@ struct PieceTables {  // tables shared by the pieces of one pipelined call: per 
   BsplineForward* d_bsfwd = nullptr;
 };
 
+// For its lifetime the per-piece calls on `c` share one PieceTables (the pipelined calls, bms_transform_modes_series): the first piece
+// builds the tables, the others read them, and a piece returns without waiting for its kernels
+struct SharedPieceTables {
+  bms_ctx* c;
+  PieceTables tables;
+  explicit SharedPieceTables(bms_ctx* c_) : c(c_) {
+    c->piece_tables = &tables;
+    c->piece_tables_valid = false;
+    c->async_pieces = true;
+  }
+  ~SharedPieceTables() {
+    c->async_pieces = false;
+    c->piece_tables_valid = false;
+    c->piece_tables = nullptr;
+  }
+  SharedPieceTables(const SharedPieceTables&) = delete;
+  SharedPieceTables& operator=(const SharedPieceTables&) = delete;
+};
+
+// The time shards of a pipelined call (plan_pieces): the output window cut into `pieces` (clamped to at least 8 outputs each), of which
+// this call runs [p0, p1); piece k produces outputs [cut[k], cut[k + 1]) from input rows [r0[k], r1[k]) -- what bms_shard_plan names for
+// that output range.  (A clamped count keeps the pieces that exist: a caller that dealt a larger count over its contexts still covers
+// every one once.)
+struct PiecePlan {
+  int pieces = 0, p0 = 0, p1 = 0;
+  std::vector<int64_t> cut, r0, r1;
+  int64_t max_rows = 0, max_out = 0;  // over the pieces [p0, p1)
+  bms_shard shard(int k) const { return {r0[k], r1[k] - r0[k], cut[k], cut[k + 1], 0, 0}; }
+  int64_t rows_out(int k) const { return cut[k + 1] - cut[k]; }
+};
+
 // ---- shared helpers (engine_tables.hip unless noted)
 BMS_INTERNAL void build_rotor_grid(const double fr[4], const double v[3], int n_theta, int n_phi, std::vector<Quat>& R);
 BMS_INTERNAL void theta_quadrature_weights(int n_theta, std::vector<double>& q);
@@ -422,6 +514,10 @@ BMS_INTERNAL void build_pixel_tables(const bms_transformation* tr, PixelTables& 
 BMS_INTERNAL void output_window(const PixelTables& T, const double* t, int64_t n, int64_t& i_lo, int64_t& i_hi);
 BMS_INTERNAL void output_window_abd(const PixelTables& T, const double* u, int64_t n, int64_t& i_lo, int64_t& i_hi);
 BMS_INTERNAL void needed_knots(const PixelTables& T, const double* t, int64_t n, int64_t c0, int64_t c1, int64_t& ja, int64_t& jb);
+BMS_INTERNAL void needed_rows(const PixelTables& T, const double* t, int64_t n, int64_t c0, int64_t c1, int64_t& r0, int64_t& r1);
+BMS_INTERNAL void plan_pieces(const PixelTables& T, const double* t, int64_t n, int64_t i_lo, int64_t i_hi, int pieces, int piece0, int piece1,
+                              PiecePlan& P);
+BMS_INTERNAL int piece_produced(bms_ctx* c, const PiecePlan& P, int k, int64_t got, int64_t first);
 BMS_INTERNAL int build_analysis(bms_ctx* c, const char* tag, int n_theta, int n_phi, int spin, int ell_min_out, int ell_max_out,
                           AnalysisPlan& A);
 inline bool analysis_reads_contiguous_rows(const AnalysisPlan& A) { return !A.fused && !A.large && A.separable; }
@@ -455,6 +551,8 @@ BMS_INTERNAL int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, P
                                int plan, hipStream_t PS = nullptr,
                                const std::function<int(hipStream_t, const DevPixel&, int)>& behind_tables = nullptr,
                                const std::function<void()>& while_waiting = nullptr);
+BMS_INTERNAL int tables_and_window(bms_ctx* c, const bms_transformation* tr, const double* t, int64_t n, bool abd, PixelTables& T, int64_t& i_lo,
+                                   int64_t& i_hi);
 BMS_INTERNAL int column_range(bms_ctx* c, const bms_shard* sh, int n_cols, int& cA, int& cB);
 BMS_INTERNAL int part_analysis_matrix(bms_ctx* c, const AnalysisPlan& A, const char* name, int n_cols, const int* col_of_pixel,
                                 double** d_At, long long* ld_at);

@@ -227,21 +227,19 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
 
   // ---- chunk loop: 6 fields x (Y, R, G)
   const BsplineSpread spread = skew_spread(T, cA, cB, u);
-  const int margin = SPLINE_HALO + 2;
   const double bytes_per_row = 19.0 * ldg * 8.0;  // 6 x (Y, R, G) + F
-  int64_t chunk = (int64_t)((double)c->ws_limit / bytes_per_row - 4.0 * margin);
-  if (chunk < 4 * margin && chunk < n_new)
+  int64_t chunk = (int64_t)((double)c->ws_limit / bytes_per_row - 4.0 * ROW_MARGIN);
+  if (chunk < 4 * ROW_MARGIN && chunk < n_new)
     return fail(c, BMS_ERR_NOMEM, "work space limit of %llu bytes holds fewer than %d rows of the six %d-column grids (%.0f bytes each); raise it with bms_ctx_set_workspace_limit",
-                (unsigned long long)c->ws_limit, 8 * margin, n_cols, bytes_per_row);
+                (unsigned long long)c->ws_limit, 8 * ROW_MARGIN, n_cols, bytes_per_row);
   chunk = std::min<int64_t>(chunk, n_new);
   if (!regular_mesh && chunk < n_new)
     return fail(c, BMS_ERR_UNSUPPORTED, "irregular time axis (steps vary by more than 1e3 within 48 samples): the series does not fit the work space in one piece");
   const int spline_tile = regular_mesh ? SPLINE_TILE : (int)std::min<int64_t>(n + 1, 0x7fffffff);  // one tile: exact recurrences
   for (int64_t c0 = i_lo; c0 < i_hi; c0 += chunk) {
     const int64_t c1_ = std::min<int64_t>(c0 + chunk, i_hi);
-    int64_t ja, jb;
-    needed_knots(T, u, n, c0, c1_, ja, jb);
-    const int64_t g0 = regular_mesh ? std::max<int64_t>(0, ja - margin) : 0, g1 = regular_mesh ? std::min<int64_t>(n, jb + margin + 1) : n;
+    int64_t g0 = 0, g1 = n;  // (irregular time axis: the whole series)
+    if (regular_mesh) needed_rows(T, u, n, c0, c1_, g0, g1);
     const int64_t rows_in = g1 - g0, rows_out = c1_ - c0;
     if (g0 < row0 || g1 > row0 + rows_avail)
       return fail(c, BMS_ERR_INVALID,
@@ -368,104 +366,44 @@ extern "C" int bms_transform_abd_pipelined_part(bms_ctx* c, const double* u, con
   if (ell_max < 0 || tr->ell_max_out < 0) return fail(c, BMS_ERR_INVALID, "bad ell_max");
   if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
   PixelTables T;
-  {
-    DevPixel DP;
-    const cplx cv0[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    if ((rc = device_pixel_tables(c, tr, T, 0, 0, 0, nullptr, nullptr, cv0, DP, 0))) return rc;
-  }
   int64_t i_lo, i_hi;
-  output_window_abd(T, u, n, i_lo, i_hi);
+  if ((rc = tables_and_window(c, tr, u, n, true, T, i_lo, i_hi))) return rc;
+  *n_times_out = i_hi - i_lo;
+  PiecePlan P;
+  plan_pieces(T, u, n, i_lo, i_hi, pieces, piece0, piece1, P);
+  if (P.p1 <= P.p0) return BMS_OK;
   const int64_t n_new = i_hi - i_lo;
-  *n_times_out = n_new;
-  if (n_new <= 0) return BMS_OK;
-  if (pieces < 1) pieces = 1;
-  if (pieces > n_new / 8) pieces = (int)std::max<int64_t>(1, n_new / 8);
-  const int p0 = std::min(std::max(piece0, 0), pieces), p1 = std::min(std::max(piece1, p0), pieces);
-  if (p1 <= p0) return BMS_OK;
   const int64_t nm = (int64_t)(ell_max + 1) * (ell_max + 1), n_out = (int64_t)(tr->ell_max_out + 1) * (tr->ell_max_out + 1);
-  std::vector<int64_t> cut(pieces + 1), r0(pieces), r1(pieces);
-  int64_t max_rows = 0, max_out = 0;
-  for (int k = 0; k <= pieces; ++k) cut[k] = i_lo + (n_new * k) / pieces;
-  for (int k = p0; k < p1; ++k) {
-    int64_t ja, jb;
-    needed_knots(T, u, n, cut[k], cut[k + 1], ja, jb);
-    const int margin = SPLINE_HALO + 2;  // as bms_shard_plan
-    r0[k] = std::max<int64_t>(0, ja - margin);
-    r1[k] = std::min<int64_t>(n, jb + margin + 1);
-    max_rows = std::max(max_rows, r1[k] - r0[k]);
-    max_out = std::max(max_out, cut[k + 1] - cut[k]);
-  }
   double *d_in[2], *d_out[2];
-  if ((rc = dev_buf_t(c, "pipe_in0", (size_t)6 * max_rows * nm * 2, &d_in[0]))) return rc;
-  if ((rc = dev_buf_t(c, "pipe_in1", (size_t)6 * max_rows * nm * 2, &d_in[1]))) return rc;
-  if ((rc = dev_buf_t(c, "pipe_out0", (size_t)6 * max_out * n_out * 2, &d_out[0]))) return rc;
-  if ((rc = dev_buf_t(c, "pipe_out1", (size_t)6 * max_out * n_out * 2, &d_out[1]))) return rc;
-  if (!c->pipe_up) {
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
-    HIP_TRY(c, create_download_stream(c));
-  }
-  std::vector<hipEvent_t> ev_up(pieces), ev_c(pieces), ev_dn(pieces);
-  for (int k = p0; k < p1; ++k) ev_up[k] = ScopedTimer::get(c), ev_c[k] = ScopedTimer::get(c), ev_dn[k] = ScopedTimer::get(c);
-  auto give_back = [&]() {
-    for (int k = p0; k < p1; ++k) c->event_pool.push_back(ev_up[k]), c->event_pool.push_back(ev_c[k]), c->event_pool.push_back(ev_dn[k]);
-  };
-  const char* host_in = (const char*)raw;
-  char* host_out = (char*)raw_out;
-  auto upload_piece = [&](int k) -> hipError_t {  // the six fields' rows [r0, r1) -> c16[6][rows][nm]
-    const int64_t rows = r1[k] - r0[k];
-    for (int f = 0; f < 6; ++f) {
-      const hipError_t e = hipMemcpyAsync(d_in[(k - p0) & 1] + (size_t)f * rows * nm * 2, host_in + ((size_t)f * n + r0[k]) * nm * 16, (size_t)rows * nm * 16,
-                                          hipMemcpyHostToDevice, c->pipe_up);
-      if (e != hipSuccess) return e;
-    }
-    return hipEventRecord(ev_up[k], c->pipe_up);
-  };
-  PieceTables shared_tables;
-  struct AsyncScope {
-    bms_ctx* c;
-    ~AsyncScope() {
-      c->async_pieces = false;
-      c->piece_tables_valid = false;
-      c->piece_tables = nullptr;
-    }
-  } scope{c};
-  c->piece_tables = &shared_tables;
-  c->piece_tables_valid = false;
-  c->async_pieces = true;
-  hipError_t he = upload_piece(p0);
-  if (he != hipSuccess) {
-    give_back();
-    return fail(c, BMS_ERR_HIP, "pipelined upload: %s", hipGetErrorString(he));
-  }
-  for (int k = p0; k < p1 && rc == BMS_OK; ++k) {
-    if (k > p0 && k + 1 < p1 && (he = upload_piece(k + 1)) != hipSuccess) break;
-    if ((he = hipStreamWaitEvent(c->stream, ev_up[k], 0)) != hipSuccess) break;
-    if (k >= p0 + 2 && (he = hipStreamWaitEvent(c->stream, ev_dn[k - 2], 0)) != hipSuccess) break;  // its output buffer has left
-    const bms_shard sh = {r0[k], r1[k] - r0[k], cut[k], cut[k + 1], 0, 0};
-    int64_t got = 0, first = 0;
-    rc = transform_abd_impl(c, u, d_in[(k - p0) & 1], BMS_DEVICE, n, ell_max, tr, &sh, u_out + (cut[k] - i_lo), d_out[(k - p0) & 1], &got, &first);
-    if (rc) break;
-    if (k == p0 && p0 + 1 < p1 && (he = upload_piece(p0 + 1)) != hipSuccess) break;  // (after piece 0's blocking table read-back)
-    if (got != cut[k + 1] - cut[k] || first != cut[k]) {
-      rc = fail(c, BMS_ERR_HIP, "pipelined shard [%lld, %lld) produced %lld rows from %lld", (long long)cut[k], (long long)cut[k + 1],
-                (long long)got, (long long)first);
-      break;
-    }
-    if ((he = hipEventRecord(ev_c[k], c->stream)) != hipSuccess) break;
-    if ((he = hipEventSynchronize(ev_c[k])) != hipSuccess) break;
-    for (int f = 0; f < 6 && he == hipSuccess; ++f)
-      he = hipMemcpyAsync(host_out + ((size_t)f * n_new + (cut[k] - i_lo)) * n_out * 16, d_out[(k - p0) & 1] + (size_t)f * got * n_out * 2,
-                          (size_t)got * n_out * 16, hipMemcpyDeviceToHost, c->pipe_down);
-    if (he != hipSuccess) break;
-    if ((he = hipEventRecord(ev_dn[k], c->pipe_down)) != hipSuccess) break;
-  }
-  (void)hipStreamSynchronize(c->pipe_up);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipStreamSynchronize(c->pipe_down);
-  give_back();
-  if (rc) return rc;
-  if (he != hipSuccess) return fail(c, BMS_ERR_HIP, "pipelined transfer: %s", hipGetErrorString(he));
-  return BMS_OK;
+  if ((rc = dev_buf_t(c, "pipe_in0", (size_t)6 * P.max_rows * nm * 2, &d_in[0]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_in1", (size_t)6 * P.max_rows * nm * 2, &d_in[1]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_out0", (size_t)6 * P.max_out * n_out * 2, &d_out[0]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_out1", (size_t)6 * P.max_out * n_out * 2, &d_out[1]))) return rc;
+  SharedPieceTables shared(c);
+  return run_host_pipeline(
+      c, P.p0, P.p1, false, true, "pipelined upload", "pipelined transfer",
+      [&](int k, int slot) {  // the six fields' rows [r0, r1) -> c16[6][rows][nm]
+        const int64_t rows = P.r1[k] - P.r0[k];
+        hipError_t e = hipSuccess;
+        for (int f = 0; f < 6 && e == hipSuccess; ++f)
+          e = hipMemcpyAsync(d_in[slot] + (size_t)f * rows * nm * 2, (const char*)raw + ((size_t)f * n + P.r0[k]) * nm * 16, (size_t)rows * nm * 16,
+                             hipMemcpyHostToDevice, c->pipe_up);
+        return e;
+      },
+      [&](int k, int slot) {
+        const bms_shard sh = P.shard(k);
+        int64_t got = 0, first = 0;
+        const int rc2 = transform_abd_impl(c, u, d_in[slot], BMS_DEVICE, n, ell_max, tr, &sh, u_out + (P.cut[k] - i_lo), d_out[slot], &got, &first);
+        return rc2 ? rc2 : piece_produced(c, P, k, got, first);
+      },
+      [&](int k, int slot) {
+        const int64_t got = P.rows_out(k);
+        hipError_t e = hipSuccess;
+        for (int f = 0; f < 6 && e == hipSuccess; ++f)
+          e = hipMemcpyAsync((char*)raw_out + ((size_t)f * n_new + (P.cut[k] - i_lo)) * n_out * 16, d_out[slot] + (size_t)f * got * n_out * 2,
+                             (size_t)got * n_out * 16, hipMemcpyDeviceToHost, c->pipe_down);
+        return e;
+      });
 } BMS_CATCH(c)
 
 // the six fields over several contexts of one process (see bms_transform_modes_multi)

@@ -36,11 +36,7 @@ extern "C" int bms_shard_plan(bms_ctx* c, const double* t, int64_t n, const bms_
     need_rows[0] = need_rows[1] = 0;
     return BMS_OK;
   }
-  int64_t ja, jb;
-  needed_knots(T, t, n, a, b, ja, jb);
-  const int margin = SPLINE_HALO + 2;
-  need_rows[0] = std::max<int64_t>(0, ja - margin);
-  need_rows[1] = std::min<int64_t>(n, jb + margin + 1);
+  needed_rows(T, t, n, a, b, need_rows[0], need_rows[1]);
   return BMS_OK;
 } BMS_CATCH(c)
 
@@ -51,14 +47,7 @@ extern "C" int bms_output_window(bms_ctx* c, const double* t, int64_t n, const b
   int rc = validate_common(c, n, t, tr, 0, 0, nullptr, abd ? 2 : 4);
   if (rc) return rc;
   PixelTables T;
-  DevPixel DP;
-  const cplx cv[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-  if ((rc = device_pixel_tables(c, tr, T, 0, 0, 0, nullptr, nullptr, cv, DP, 0))) return rc;
-  if (abd)
-    output_window_abd(T, t, n, window[0], window[1]);
-  else
-    output_window(T, t, n, window[0], window[1]);
-  return BMS_OK;
+  return tables_and_window(c, tr, t, n, abd, T, window[0], window[1]);
 } BMS_CATCH(c)
 
 static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_transformation* tr, const bms_shard* sh, double* t_out,
@@ -118,155 +107,60 @@ extern "C" int bms_transform_modes_pipelined_part(bms_ctx* c, const bms_wm_input
   if (!regular) return fail(c, BMS_ERR_UNSUPPORTED, "the time steps vary by more than 1e3 within 48 samples: not sharded");
   // per-direction tables once (on the device, read back), for the window and for every piece's row range
   PixelTables T;
-  {
-    DevPixel DP;
-    const cplx cv0[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    if ((rc = device_pixel_tables(c, tr, T, 0, 0, 0, nullptr, nullptr, cv0, DP, 0))) return rc;
-  }
   int64_t i_lo, i_hi;
-  output_window(T, in->t, n, i_lo, i_hi);
-  const int64_t n_new = i_hi - i_lo;
-  *n_times_out = n_new;
-  if (n_new <= 0) return BMS_OK;
-  if (pieces < 1) pieces = 1;
-  if (pieces > n_new / 8) pieces = (int)std::max<int64_t>(1, n_new / 8);
-  // (a clamped count keeps the pieces that exist: a caller that dealt a larger count over its contexts still covers every one once)
-  const int p0 = std::min(std::max(piece0, 0), pieces), p1 = std::min(std::max(piece1, p0), pieces);
-  if (p1 <= p0) return BMS_OK;
+  if ((rc = tables_and_window(c, tr, in->t, n, false, T, i_lo, i_hi))) return rc;
+  *n_times_out = i_hi - i_lo;
+  PiecePlan P;
+  plan_pieces(T, in->t, n, i_lo, i_hi, pieces, piece0, piece1, P);
+  if (P.p1 <= P.p0) return BMS_OK;
   const int n_modes = LM_total_size(in->ell_min, in->ell_max);
   const int s_abs = std::abs(in->spin_weight);
   const int n_out = LM_total_size(s_abs, tr->ell_max_out);
-  // plan: output cuts and the input rows each piece needs
-  std::vector<int64_t> cut(pieces + 1), r0(pieces), r1(pieces);
-  int64_t max_rows = 0, max_out = 0;
-  for (int k = 0; k <= pieces; ++k) cut[k] = i_lo + (n_new * k) / pieces;
-  for (int k = p0; k < p1; ++k) {
-    int64_t ja, jb;
-    needed_knots(T, in->t, n, cut[k], cut[k + 1], ja, jb);
-    const int margin = SPLINE_HALO + 2;  // as bms_shard_plan
-    r0[k] = std::max<int64_t>(0, ja - margin);
-    r1[k] = std::min<int64_t>(n, jb + margin + 1);
-    max_rows = std::max(max_rows, r1[k] - r0[k]);
-    max_out = std::max(max_out, cut[k + 1] - cut[k]);
-  }
   double *d_in[2], *d_out[2];
-  if ((rc = dev_buf_t(c, "pipe_in0", (size_t)max_rows * n_modes * 2, &d_in[0]))) return rc;
-  if ((rc = dev_buf_t(c, "pipe_in1", (size_t)max_rows * n_modes * 2, &d_in[1]))) return rc;
-  if ((rc = dev_buf_t(c, "pipe_out0", (size_t)max_out * n_out * 2, &d_out[0]))) return rc;
-  if ((rc = dev_buf_t(c, "pipe_out1", (size_t)max_out * n_out * 2, &d_out[1]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_in0", (size_t)P.max_rows * n_modes * 2, &d_in[0]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_in1", (size_t)P.max_rows * n_modes * 2, &d_in[1]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_out0", (size_t)P.max_out * n_out * 2, &d_out[0]))) return rc;
+  if ((rc = dev_buf_t(c, "pipe_out1", (size_t)P.max_out * n_out * 2, &d_out[1]))) return rc;
   double* d_aux[4][2] = {};
   for (int a = 0; a < in->n_aux; ++a)
     for (int b = 0; b < 2; ++b) {
       char nm[32];
       snprintf(nm, sizeof nm, "pipe_aux%d_%d", a, b);
-      if ((rc = dev_buf_t(c, nm, (size_t)max_rows * aux_modes[a] * 2, &d_aux[a][b]))) return rc;
+      if ((rc = dev_buf_t(c, nm, (size_t)P.max_rows * aux_modes[a] * 2, &d_aux[a][b]))) return rc;
     }
-  if (!c->pipe_up) {
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
-    HIP_TRY(c, create_download_stream(c));
-  }
-  std::vector<hipEvent_t> ev_up(pieces), ev_c(pieces), ev_dn(pieces);
-  for (int k = p0; k < p1; ++k) {
-    ev_up[k] = ScopedTimer::get(c);
-    ev_c[k] = ScopedTimer::get(c);
-    ev_dn[k] = ScopedTimer::get(c);
-  }
-  auto give_back = [&]() {
-    for (int k = p0; k < p1; ++k) {
-      c->event_pool.push_back(ev_up[k]);
-      c->event_pool.push_back(ev_c[k]);
-      c->event_pool.push_back(ev_dn[k]);
-    }
+  // rows [r0, r1) of piece k of one field, packed (row stride = its number of modes) into the piece's buffer
+  auto rows_up = [&](int k, double* dst, const void* src, int64_t ld, int nm) -> hipError_t {
+    const int64_t rows = P.r1[k] - P.r0[k];
+    const char* from = (const char*)src + (size_t)P.r0[k] * ld * 16;
+    return ld == nm ? hipMemcpyAsync(dst, from, (size_t)rows * nm * 16, hipMemcpyHostToDevice, c->pipe_up)
+                    : hipMemcpy2DAsync(dst, (size_t)nm * 16, from, (size_t)ld * 16, (size_t)nm * 16, (size_t)rows, hipMemcpyHostToDevice, c->pipe_up);
   };
-  const char* host_in = (const char*)in->data;
-  char* host_out = (char*)data_out;
-  // The host waits for a piece's kernels before it issues the download.  SCRI_AMD_PIPE_EVENTS=1 (experiment): the streams wait for
-  // each other through events and the host runs ahead, so that the kernels of consecutive pieces follow each other without the
-  // host's round trip in between -- measured, three alternating runs: 14.9 / 15.1 / 16.2 ms with the host wait, 14.9 / 15.1 / 13.7
-  // with events: no difference, the transfers and not the kernels' gaps set the time.
-  const bool host_wait = BMS_PROBE_ENV("SCRI_AMD_PIPE_EVENTS") == nullptr;
-  auto upload_piece = [&](int k) -> hipError_t {
-    // the buffer was read by the kernels of piece k - 2 (host_wait: the host has waited for them before it gets here)
-    const int64_t rows = r1[k] - r0[k];
-    if (!host_wait && k >= p0 + 2) {
-      const hipError_t ew = hipStreamWaitEvent(c->pipe_up, ev_c[k - 2], 0);
-      if (ew != hipSuccess) return ew;
-    }
-    // rows [r0, r1) of one field, packed (row stride = its number of modes) into the piece's buffer
-    auto rows_up = [&](double* dst, const void* src, int64_t ld, int nm) -> hipError_t {
-      const char* from = (const char*)src + (size_t)r0[k] * ld * 16;
-      return ld == nm ? hipMemcpyAsync(dst, from, (size_t)rows * nm * 16, hipMemcpyHostToDevice, c->pipe_up)
-                      : hipMemcpy2DAsync(dst, (size_t)nm * 16, from, (size_t)ld * 16, (size_t)nm * 16, (size_t)rows, hipMemcpyHostToDevice, c->pipe_up);
-    };
-    hipError_t e = rows_up(d_in[(k - p0) & 1], host_in, in->ld, n_modes);
-    for (int a = 0; a < in->n_aux && e == hipSuccess; ++a) e = rows_up(d_aux[a][(k - p0) & 1], in->aux_data[a], in->aux_ld[a], aux_modes[a]);
-    if (e != hipSuccess) return e;
-    return hipEventRecord(ev_up[k], c->pipe_up);  // (covers the companions' rows too)
-  };
-  PieceTables shared_tables;
-  struct AsyncScope {
-    bms_ctx* c;
-    ~AsyncScope() {
-      c->async_pieces = false;
-      c->piece_tables_valid = false;
-      c->piece_tables = nullptr;
-    }
-  } scope{c};
-  c->piece_tables = &shared_tables;
-  c->piece_tables_valid = false;
-  c->async_pieces = true;
-  hipError_t he = upload_piece(p0);
-  if (he != hipSuccess) {
-    give_back();
-    return fail(c, BMS_ERR_HIP, "pipelined upload: %s", hipGetErrorString(he));
-  }
-  for (int k = p0; k < p1 && rc == BMS_OK; ++k) {
-    // piece k + 1 travels while piece k is transformed; its buffer was read by the kernels of piece k - 1.  (Piece 0 reads
-    // its per-direction tables back with a blocking copy, which waits for every upload under way: piece 1 is sent after it.)
-    auto send_next = [&]() -> hipError_t {
-      if (k + 1 >= p1) return hipSuccess;
-      return upload_piece(k + 1);
-    };
-    if (k > p0 && (he = send_next()) != hipSuccess) break;
-    if ((he = hipStreamWaitEvent(c->stream, ev_up[k], 0)) != hipSuccess) break;
-    if (k >= p0 + 2 && (he = hipStreamWaitEvent(c->stream, ev_dn[k - 2], 0)) != hipSuccess) break;  // its output buffer has left
-    bms_wm_input piece = *in;
-    piece.data = d_in[(k - p0) & 1];
-    piece.ld = n_modes;
-    piece.mem = BMS_DEVICE;
-    for (int a = 0; a < in->n_aux; ++a) {
-      piece.aux_data[a] = d_aux[a][(k - p0) & 1];
-      piece.aux_ld[a] = aux_modes[a];
-    }
-    const bms_shard sh = {r0[k], r1[k] - r0[k], cut[k], cut[k + 1], 0, 0};
-    int64_t got = 0, first = 0;
-    rc = transform_modes_impl(c, &piece, tr, &sh, t_out + (cut[k] - i_lo), d_out[(k - p0) & 1], &got, &first, nullptr);
-    if (rc) break;
-    if (k == p0 && (he = send_next()) != hipSuccess) break;
-    if (got != cut[k + 1] - cut[k] || first != cut[k]) {
-      rc = fail(c, BMS_ERR_HIP, "pipelined shard [%lld, %lld) produced %lld rows from %lld", (long long)cut[k], (long long)cut[k + 1],
-                (long long)got, (long long)first);
-      break;
-    }
-    if ((he = hipEventRecord(ev_c[k], c->stream)) != hipSuccess) break;
-    // The host waits for the piece's kernels and then issues the download (the next upload is already on its way).  In the
-    // rocprofv3 trace of this loop the uploads run on a DMA engine beside the kernels; the downloads are executed by the runtime
-    // as shader copies (__amd_rocclr_copyBuffer) that take turns with the compute kernels.  Storing the results straight into the
-    // page-locked array from the analysis kernel (on a side stream, with a small grid) was tried: the stores leave at 42 GB/s
-    // instead of 57 and every memory-bound kernel running beside them crawls -- 19.8 ms against 15.7 ms per cfg3 transform.
-    if ((he = host_wait ? hipEventSynchronize(ev_c[k]) : hipStreamWaitEvent(c->pipe_down, ev_c[k], 0)) != hipSuccess) break;
-    if ((he = hipMemcpyAsync(host_out + (size_t)(cut[k] - i_lo) * n_out * 16, d_out[(k - p0) & 1], (size_t)got * n_out * 16,
-                             hipMemcpyDeviceToHost, c->pipe_down)) != hipSuccess)
-      break;
-    if ((he = hipEventRecord(ev_dn[k], c->pipe_down)) != hipSuccess) break;
-  }
-  (void)hipStreamSynchronize(c->pipe_up);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipStreamSynchronize(c->pipe_down);
-  give_back();
-  if (rc) return rc;
-  if (he != hipSuccess) return fail(c, BMS_ERR_HIP, "pipelined transfer: %s", hipGetErrorString(he));
-  return BMS_OK;
+  SharedPieceTables shared(c);
+  return run_host_pipeline(
+      c, P.p0, P.p1, false, true, "pipelined upload", "pipelined transfer",
+      [&](int k, int slot) {  // (the companions' rows under the same event as the data's)
+        hipError_t e = rows_up(k, d_in[slot], in->data, in->ld, n_modes);
+        for (int a = 0; a < in->n_aux && e == hipSuccess; ++a) e = rows_up(k, d_aux[a][slot], in->aux_data[a], in->aux_ld[a], aux_modes[a]);
+        return e;
+      },
+      [&](int k, int slot) {
+        bms_wm_input piece = *in;
+        piece.data = d_in[slot];
+        piece.ld = n_modes;
+        piece.mem = BMS_DEVICE;
+        for (int a = 0; a < in->n_aux; ++a) {
+          piece.aux_data[a] = d_aux[a][slot];
+          piece.aux_ld[a] = aux_modes[a];
+        }
+        const bms_shard sh = P.shard(k);
+        int64_t got = 0, first = 0;
+        const int rc2 = transform_modes_impl(c, &piece, tr, &sh, t_out + (P.cut[k] - i_lo), d_out[slot], &got, &first, nullptr);
+        return rc2 ? rc2 : piece_produced(c, P, k, got, first);
+      },
+      [&](int k, int slot) {
+        return hipMemcpyAsync((char*)data_out + (size_t)(P.cut[k] - i_lo) * n_out * 16, d_out[slot], (size_t)P.rows_out(k) * n_out * 16,
+                              hipMemcpyDeviceToHost, c->pipe_down);
+      });
 } BMS_CATCH(c)
 
 // One process, several GPUs, ONE call: the `pieces` time shards of the pipelined plan dealt in contiguous runs over the n_ctx contexts
@@ -352,18 +246,7 @@ extern "C" int bms_transform_modes_series(bms_ctx* c, const bms_wm_input* in, in
   }
   double* d_res = nullptr;  // series-major results, c16[n_series][n][n_out]
   if ((rc = dev_buf_t(c, "series_res", (size_t)n_series * n * n_out * 2, &d_res))) return rc;
-  PieceTables shared_tables;
-  struct AsyncScope {
-    bms_ctx* c;
-    ~AsyncScope() {
-      c->async_pieces = false;
-      c->piece_tables_valid = false;
-      c->piece_tables = nullptr;
-    }
-  } scope{c};
-  c->piece_tables = &shared_tables;
-  c->piece_tables_valid = false;
-  c->async_pieces = true;
+  SharedPieceTables shared(c);
   int64_t n_new = 0;
   rc = BMS_OK;
   for (int j = 0; j < n_series && rc == BMS_OK; ++j) {
@@ -848,25 +731,23 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
 
   // ---------------------------------------------------------------- chunk loop over output samples
   const BsplineSpread spread = skew_spread(T, cA, cB, in->t);
-  const int margin = SPLINE_HALO + 2;
   // bytes per output row ~ (Y + R + G [+ Yaux]) * ldg * 8
   const double bytes_per_row = (4.0 + (psi ? 1.0 : 0.0)) * ldg * 8.0;  // Y, R, G, F (+ Yaux)
   // rows the work space limit allows; a chunk shorter than a few spline halos would spend its time re-synthesising them,
   // so below that the limit is reported as too small rather than silently exceeded
-  int64_t chunk = (int64_t)((double)c->ws_limit / bytes_per_row - 4.0 * margin);
-  if (chunk < 4 * margin && chunk < n_new)
+  int64_t chunk = (int64_t)((double)c->ws_limit / bytes_per_row - 4.0 * ROW_MARGIN);
+  if (chunk < 4 * ROW_MARGIN && chunk < n_new)
     return fail(c, BMS_ERR_NOMEM, "work space limit of %llu bytes holds fewer than %d rows of the %d-column grids (%.0f bytes each); raise it with bms_ctx_set_workspace_limit",
-                (unsigned long long)c->ws_limit, 8 * margin, n_cols, bytes_per_row);
+                (unsigned long long)c->ws_limit, 8 * ROW_MARGIN, n_cols, bytes_per_row);
   chunk = std::min<int64_t>(chunk, n_new);
   if (!regular_mesh && chunk < n_new)
     return fail(c, BMS_ERR_UNSUPPORTED, "irregular time axis (steps vary by more than 1e3 within 48 samples): the series does not fit the work space in one piece");
   const int spline_tile = regular_mesh ? SPLINE_TILE : (int)std::min<int64_t>(n + 1, 0x7fffffff);  // one tile: exact recurrences
   for (int64_t c0 = i_lo; c0 < i_hi; c0 += chunk) {
     const int64_t c1 = std::min<int64_t>(c0 + chunk, i_hi);
-    int64_t ja, jb;
-    needed_knots(T, in->t, n, c0, c1, ja, jb);
     // (irregular time axis: the whole series, so that the single-tile recurrences start and end at the true ends)
-    const int64_t g0 = regular_mesh ? std::max<int64_t>(0, ja - margin) : 0, g1 = regular_mesh ? std::min<int64_t>(n, jb + margin + 1) : n;
+    int64_t g0 = 0, g1 = n;
+    if (regular_mesh) needed_rows(T, in->t, n, c0, c1, g0, g1);
     const int64_t rows_in = g1 - g0, rows_out = c1 - c0;
     if (g0 < row0 || g1 > row0 + rows_avail)
       return fail(c, BMS_ERR_INVALID,

@@ -5,6 +5,15 @@
 // ====================================================================================================== rotation
 
 constexpr int ROT_RING = 64;
+
+// block k of `blocks` of the rows of a series in host memory (row stride ld) to (up) or from a packed device buffer (row stride n_modes)
+static hipError_t copy_block(char* host, int64_t ld, double* dev, int64_t n_modes, int64_t n_times, int blocks, int k, bool up, hipStream_t s) {
+  const int64_t r0 = n_times * k / blocks, rows = n_times * (k + 1) / blocks - r0;
+  const size_t row_bytes = (size_t)n_modes * 16, pitch = (size_t)ld * 16;
+  char* h = host + (size_t)r0 * pitch;
+  return up ? hipMemcpy2DAsync(dev, row_bytes, h, pitch, row_bytes, (size_t)rows, hipMemcpyHostToDevice, s)
+            : hipMemcpy2DAsync(h, pitch, dev, row_bytes, row_bytes, (size_t)rows, hipMemcpyDeviceToHost, s);
+}
 // sync_after = false (internal callers, device data, constant rotor): the call returns with the work enqueued
 int rotate_impl(bms_ctx* c, void* data, int mem, int64_t n_times, int64_t ld, int ell_min, int ell_max, const void* spinors, bool series,
                 bool sync_after) {
@@ -83,8 +92,8 @@ int rotate_impl(bms_ctx* c, void* data, int mem, int64_t n_times, int64_t ld, in
     return BMS_OK;
   };
   // A long series in HOST memory is all transfer (cfg2: 117 MB each way at 57 GB/s against 0.1 ms of kernel), and one call sends it, turns it
-  // and brings it back one after the other.  The link is full duplex: blocks of rows go up on one stream, are rotated on the context's
-  // stream and come back on a third, ordered by events, two staging buffers -- the rows are independent, so there is no halo; the
+  // and brings it back one after the other.  The link is full duplex: blocks of rows go up, are rotated in place and come back on three
+  // streams (run_host_pipeline), two staging buffers -- the rows are independent, so there is no halo; the
   // result is the one-call result to the last bit or two (a row's rounding depends on the launch geometry of the kernel: 5e-16,
   // tools/probes/rot_block_probe.py).  From page-locked memory (bms_host_register / bms_host_alloc) the copies run at the rate
   // of the link and side by side (l <= 16, 1e5 steps: 16.3 -> 9 ms); from pageable memory the runtime stages them and little is gained.
@@ -103,40 +112,15 @@ int rotate_impl(bms_ctx* c, void* data, int mem, int64_t n_times, int64_t ld, in
       HIP_TRY(c, hipMemcpyAsync(r, spinors, rot_bytes, hipMemcpyHostToDevice, c->stream));
       d_r = r;
     }
-    if (!c->pipe_up) {
-      HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
-      HIP_TRY(c, create_download_stream(c));
-    }
-    std::vector<hipEvent_t> ev(3 * (size_t)blocks);
-    for (auto& e : ev) e = ScopedTimer::get(c);
-    hipError_t he = hipSuccess;
-    char* host = (char*)data;
-    for (int k = 0; k < blocks && he == hipSuccess && rc == BMS_OK; ++k) {
-      const int64_t r0 = (int64_t)n_times * k / blocks, r1 = (int64_t)n_times * (k + 1) / blocks, rows = r1 - r0;
-      double* buf = d_buf[k & 1];
-      hipEvent_t up = ev[3 * k], done = ev[3 * k + 1], down = ev[3 * k + 2];
-      if (k >= 2 && (he = hipStreamWaitEvent(c->pipe_up, ev[3 * (k - 2) + 2], 0)) != hipSuccess) break;  // the buffer's last rows have left
-      if ((he = hipMemcpy2DAsync(buf, row_bytes, host + (size_t)r0 * ld * 16, (size_t)ld * 16, row_bytes, (size_t)rows, hipMemcpyHostToDevice,
-                                 c->pipe_up)) != hipSuccess)
-        break;
-      if ((he = hipEventRecord(up, c->pipe_up)) != hipSuccess) break;
-      if ((he = hipStreamWaitEvent(c->stream, up, 0)) != hipSuccess) break;
-      rc = launch_segments(buf, rows, n_modes, series ? d_r + 4 * r0 : d_r);
-      if (rc) break;
-      if ((he = hipEventRecord(done, c->stream)) != hipSuccess) break;
-      if ((he = hipStreamWaitEvent(c->pipe_down, done, 0)) != hipSuccess) break;
-      if ((he = hipMemcpy2DAsync(host + (size_t)r0 * ld * 16, (size_t)ld * 16, buf, row_bytes, row_bytes, (size_t)rows, hipMemcpyDeviceToHost,
-                                 c->pipe_down)) != hipSuccess)
-        break;
-      he = hipEventRecord(down, c->pipe_down);
-    }
-    (void)hipStreamSynchronize(c->pipe_up);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->pipe_down);
-    for (auto e : ev) c->event_pool.push_back(e);
-    if (rc) return rc;
-    if (he != hipSuccess) return fail(c, BMS_ERR_HIP, "rotation of a host series in blocks: %s", hipGetErrorString(he));
-    return BMS_OK;
+    const char* err = "rotation of a host series in blocks";
+    return run_host_pipeline(
+        c, 0, blocks, true, false, err, err,
+        [&](int k, int slot) { return copy_block((char*)data, ld, d_buf[slot], n_modes, n_times, blocks, k, true, c->pipe_up); },
+        [&](int k, int slot) {
+          const int64_t r0 = n_times * k / blocks;
+          return launch_segments(d_buf[slot], n_times * (k + 1) / blocks - r0, n_modes, series ? d_r + 4 * r0 : d_r);
+        },
+        [&](int k, int slot) { return copy_block((char*)data, ld, d_buf[slot], n_modes, n_times, blocks, k, false, c->pipe_down); });
   }
   if (!series && mem == BMS_DEVICE && !sync_after) {
     if (!c->rot_ring_host) {
@@ -236,48 +220,21 @@ extern "C" int bms_rotate_const_D(bms_ctx* c, void* data, int mem, int64_t n_tim
     if ((rc = dev_buf_t(c, "rot_pipe1", (size_t)rows_max * n_modes * 2, &d_in[1]))) return rc;
     if ((rc = dev_buf_t(c, "rotD_pipe0", (size_t)rows_max * n_modes * 2, &d_out[0]))) return rc;
     if ((rc = dev_buf_t(c, "rotD_pipe1", (size_t)rows_max * n_modes * 2, &d_out[1]))) return rc;
-    if (!c->pipe_up) {
-      HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
-      HIP_TRY(c, create_download_stream(c));
-    }
-    std::vector<hipEvent_t> ev(3 * (size_t)blocks);
-    for (auto& e : ev) e = ScopedTimer::get(c);
-    auto products = [&](const double* in, double* out, int64_t rows) -> int {
-      for (int l = ell_min; l <= ell_max; ++l) {
-        const int n = 2 * l + 1;
-        const long long col = (long long)l * l - (long long)ell_min * ell_min;
-        TIMED(c, BMS_TAG_ROTATE, launch_zgemm3m(c->stream, in + 2 * col, 2 * n_modes, d_B + boff[l], round_up(n, 64) * 2, out + 2 * col, 2 * n_modes,
-                                                rows, n, n, nullptr, nullptr));
-      }
-      return BMS_OK;
-    };
-    hipError_t he = hipSuccess;
-    char* host = (char*)data;
-    for (int k = 0; k < blocks && he == hipSuccess && rc == BMS_OK; ++k) {
-      const int64_t r0 = (int64_t)n_times * k / blocks, r1 = (int64_t)n_times * (k + 1) / blocks, rows = r1 - r0;
-      hipEvent_t up = ev[3 * k], done = ev[3 * k + 1], down = ev[3 * k + 2];
-      if (k >= 2 && (he = hipStreamWaitEvent(c->pipe_up, ev[3 * (k - 2) + 1], 0)) != hipSuccess) break;  // the input buffer has been read
-      if ((he = hipMemcpy2DAsync(d_in[k & 1], row_bytes, host + (size_t)r0 * ld * 16, (size_t)ld * 16, row_bytes, (size_t)rows, hipMemcpyHostToDevice,
-                                 c->pipe_up)) != hipSuccess)
-        break;
-      if ((he = hipEventRecord(up, c->pipe_up)) != hipSuccess) break;
-      if ((he = hipStreamWaitEvent(c->stream, up, 0)) != hipSuccess) break;
-      if (k >= 2 && (he = hipStreamWaitEvent(c->stream, ev[3 * (k - 2) + 2], 0)) != hipSuccess) break;  // the output buffer has left
-      if ((rc = products(d_in[k & 1], d_out[k & 1], rows))) break;
-      if ((he = hipEventRecord(done, c->stream)) != hipSuccess) break;
-      if ((he = hipStreamWaitEvent(c->pipe_down, done, 0)) != hipSuccess) break;
-      if ((he = hipMemcpy2DAsync(host + (size_t)r0 * ld * 16, (size_t)ld * 16, d_out[k & 1], row_bytes, row_bytes, (size_t)rows, hipMemcpyDeviceToHost,
-                                 c->pipe_down)) != hipSuccess)
-        break;
-      he = hipEventRecord(down, c->pipe_down);
-    }
-    (void)hipStreamSynchronize(c->pipe_up);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->pipe_down);
-    for (auto e : ev) c->event_pool.push_back(e);
-    if (rc) return rc;
-    if (he != hipSuccess) return fail(c, BMS_ERR_HIP, "rotation of a host series in blocks: %s", hipGetErrorString(he));
-    return BMS_OK;
+    const char* err = "rotation of a host series in blocks";
+    return run_host_pipeline(
+        c, 0, blocks, false, false, err, err,
+        [&](int k, int slot) { return copy_block((char*)data, ld, d_in[slot], n_modes, n_times, blocks, k, true, c->pipe_up); },
+        [&](int k, int slot) -> int {
+          const int64_t rows = n_times * (k + 1) / blocks - n_times * k / blocks;
+          for (int l = ell_min; l <= ell_max; ++l) {
+            const int n = 2 * l + 1;
+            const long long col = (long long)l * l - (long long)ell_min * ell_min;
+            TIMED(c, BMS_TAG_ROTATE, launch_zgemm3m(c->stream, d_in[slot] + 2 * col, 2 * n_modes, d_B + boff[l], round_up(n, 64) * 2,
+                                                    d_out[slot] + 2 * col, 2 * n_modes, rows, n, n, nullptr, nullptr));
+          }
+          return BMS_OK;
+        },
+        [&](int k, int slot) { return copy_block((char*)data, ld, d_out[slot], n_modes, n_times, blocks, k, false, c->pipe_down); });
   }
   if (mem == BMS_HOST) {
     if ((rc = dev_buf_t(c, "rot_data", data_bytes / 8, &d_data))) return rc;

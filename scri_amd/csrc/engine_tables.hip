@@ -282,6 +282,43 @@ void needed_knots(const PixelTables& T, const double* t, int64_t n, int64_t c0, 
   jb = std::min<int64_t>(jb, n - 1);
 }
 
+// input rows [r0, r1) that output samples [c0, c1) read: their knots and ROW_MARGIN on either side, within [0, n)
+void needed_rows(const PixelTables& T, const double* t, int64_t n, int64_t c0, int64_t c1, int64_t& r0, int64_t& r1) {
+  int64_t ja, jb;
+  needed_knots(T, t, n, c0, c1, ja, jb);
+  r0 = std::max<int64_t>(0, ja - ROW_MARGIN);
+  r1 = std::min<int64_t>(n, jb + ROW_MARGIN + 1);
+}
+
+// the pieces of a pipelined call over the output window [i_lo, i_hi) of the axis t (PiecePlan); none when the window is empty
+void plan_pieces(const PixelTables& T, const double* t, int64_t n, int64_t i_lo, int64_t i_hi, int pieces, int piece0, int piece1,
+                 PiecePlan& P) {
+  const int64_t n_new = i_hi - i_lo;
+  P = PiecePlan{};
+  if (n_new <= 0) return;
+  if (pieces < 1) pieces = 1;
+  if (pieces > n_new / 8) pieces = (int)std::max<int64_t>(1, n_new / 8);
+  P.pieces = pieces;
+  P.p0 = std::min(std::max(piece0, 0), pieces);
+  P.p1 = std::min(std::max(piece1, P.p0), pieces);
+  P.cut.resize(pieces + 1);
+  P.r0.assign(pieces, 0);
+  P.r1.assign(pieces, 0);
+  for (int k = 0; k <= pieces; ++k) P.cut[k] = i_lo + (n_new * k) / pieces;
+  for (int k = P.p0; k < P.p1; ++k) {
+    needed_rows(T, t, n, P.cut[k], P.cut[k + 1], P.r0[k], P.r1[k]);
+    P.max_rows = std::max(P.max_rows, P.r1[k] - P.r0[k]);
+    P.max_out = std::max(P.max_out, P.rows_out(k));
+  }
+}
+
+// a piece that produced another output range than planned fails the call
+int piece_produced(bms_ctx* c, const PiecePlan& P, int k, int64_t got, int64_t first) {
+  if (got == P.rows_out(k) && first == P.cut[k]) return BMS_OK;
+  return fail(c, BMS_ERR_HIP, "pipelined shard [%lld, %lld) produced %lld rows from %lld", (long long)P.cut[k], (long long)P.cut[k + 1],
+              (long long)got, (long long)first);
+}
+
 
 
 
@@ -852,6 +889,20 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
   T.alpha.assign(back + n_pix, back + n_pix + n_cols);
   T.skew_a.assign(back + 2 * (size_t)n_pix, back + 2 * (size_t)n_pix + n_cols);
   T.skew_b.assign(back + 3 * (size_t)n_pix, back + 3 * (size_t)n_pix + n_cols);
+  return BMS_OK;
+}
+
+// the per-direction tables of `tr` alone (on the device, read back) and the output window of the axis t (the ABD flavour's when abd)
+int tables_and_window(bms_ctx* c, const bms_transformation* tr, const double* t, int64_t n, bool abd, PixelTables& T, int64_t& i_lo,
+                      int64_t& i_hi) {
+  DevPixel DP;
+  const cplx cv0[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+  const int rc = device_pixel_tables(c, tr, T, 0, 0, 0, nullptr, nullptr, cv0, DP, 0);
+  if (rc) return rc;
+  if (abd)
+    output_window_abd(T, t, n, i_lo, i_hi);
+  else
+    output_window(T, t, n, i_lo, i_hi);
   return BMS_OK;
 }
 

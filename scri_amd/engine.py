@@ -273,12 +273,49 @@ def _context_array(ctxs):
     return arr
 
 
-def _transform_modes_multi(t, data, inp, transformation, n_out, ctxs, pieces):
-    """bms_transform_modes_multi: the `pieces` time shards of the output window dealt in contiguous runs over one context per
-    device, one host thread each inside the library, slice + halo shipped at upload time (no GPU-to-GPU traffic).  None: a series
-    the engine does not shard (the one-call path takes it)."""
+def _wm_input(t, data, ld, mem, ell_min, ell_max, spin_weight, conformal_weight, type_term, aux=()):
+    """bms_wm_input of the time axis `t` (float64, contiguous), the data's address, row stride and memory kind, and per psi companion
+    (address, row stride, ell_min, ell_max, spin, coeff, power)."""
+    inp = bms_wm_input()
+    inp.n_times, inp.t = t.shape[0], dptr(t)
+    inp.data, inp.ld, inp.mem = int(data), int(ld), mem
+    inp.ell_min, inp.ell_max = int(ell_min), int(ell_max)
+    inp.spin_weight, inp.conformal_weight, inp.type_term = int(spin_weight), int(conformal_weight), int(type_term)
+    inp.n_aux = len(aux)
+    for i, (adata, ald, amin, amax, aspin, acoeff, apower) in enumerate(aux):
+        inp.aux_data[i], inp.aux_ld[i] = int(adata), int(ald)
+        inp.aux_ell_min[i], inp.aux_ell_max[i], inp.aux_spin[i] = int(amin), int(amax), int(aspin)
+        inp.aux_coeff[i], inp.aux_power[i] = float(acoeff), int(apower)
+    return inp
+
+
+def _run_pipelined(ctxs, single, multi, *args):
+    """The pipelined call on one context (entry `single`) or its time shards dealt in contiguous runs over several, one host thread each
+    inside the library (entry `multi`); every context ships its own rows + halo at upload time, no GPU-to-GPU traffic.  `args` follow
+    the context argument(s).  False: a series the engine does not shard (graded time steps), which the one-call path takes."""
+    lib = _lib.load()
+    if len(ctxs) == 1:
+        name, rc = single, getattr(lib, single)(ctxs[0].handle, *args)
+    else:
+        name, rc = multi, getattr(lib, multi)(_context_array(ctxs), len(ctxs), *args)
+    try:
+        ctxs[0].check(rc, name)
+    except NotImplementedError:
+        return False
+    return True
+
+
+def _transform_modes_pipelined(t, data, inp, transformation, n_out, ctxs, pieces):
+    """Host-memory callers of a long series wait for PCIe, not for the kernels (cfg3: 456 MB each way against 6 ms of
+    kernels), and one call does upload -> kernels -> download one after the other.  bms_transform_modes_pipelined cuts the
+    output range into `pieces` time shards (bms_shard_plan names the input rows each one needs, exactly as for the
+    multi-GPU split) and runs upload, kernels and download of neighbouring shards side by side on three streams;
+    bms_transform_modes_multi deals the shards over the contexts `ctxs`.  Results are those of the sharded path (equal to the
+    one-call path to rounding; tests/test_gpu_sharding.py) and depend on `pieces` only.  Returns None when the series cannot
+    be sharded (graded time steps).  (`data`, the array `inp` points to, is not read: it keeps the argument order of the two
+    helpers this one merges.)"""
     if not np.all(np.diff(t) > 0):
-        return None
+        return None  # the one-call path raises the ValueError the reference's callers expect
     n = t.shape[0]
     if n < 8 * pieces + 16:
         return None
@@ -287,94 +324,13 @@ def _transform_modes_multi(t, data, inp, transformation, n_out, ctxs, pieces):
     out = _lib.pinned_empty((n, n_out), np.complex128)
     t_out = np.empty(n, dtype=float)
     got = c_i64(0)
-    rc = _lib.load().bms_transform_modes_multi(_context_array(ctxs), len(ctxs), ctypes.byref(inp), ctypes.byref(transformation), int(pieces),
-                                               dptr(t_out), vptr(out), ctypes.byref(got))
-    try:
-        ctxs[0].check(rc, "bms_transform_modes_multi")
-    except NotImplementedError:
+    if not _run_pipelined(ctxs, "bms_transform_modes_pipelined", "bms_transform_modes_multi", ctypes.byref(inp), ctypes.byref(transformation),
+                          int(pieces), dptr(t_out), vptr(out), ctypes.byref(got)):
         return None
     return t_out[: got.value], out[: got.value]
 
 
-def _transform_modes_pipelined(t, data, inp, transformation, n_out, ctx, pieces=None):
-    """Host-memory callers of a long series wait for PCIe, not for the kernels (cfg3: 456 MB each way against 6 ms of
-    kernels), and one call does upload -> kernels -> download one after the other.  bms_transform_modes_pipelined cuts the
-    output range into PIPELINE_PIECES time shards (bms_shard_plan names the input rows each one needs, exactly as for the
-    multi-GPU split) and runs upload, kernels and download of neighbouring shards side by side on three streams.  Results
-    are those of the sharded path (equal to the one-call path to rounding; tests/test_gpu_sharding.py).  Returns None when
-    the series cannot be sharded (graded time steps).  SCRI_AMD_PIPELINE_THREADS=1: round 1's version of the same idea
-    (two contexts fed by two host threads)."""
-    if pieces is not None or not os.environ.get("SCRI_AMD_PIPELINE_THREADS"):
-        pieces = int(pieces or PIPELINE_PIECES)
-        if not np.all(np.diff(t) > 0):
-            return None  # the one-call path raises the ValueError the reference's callers expect
-        n = t.shape[0]
-        if n < 8 * pieces + 16:
-            return None
-        # (sized for the whole series instead of asking the device for the window first: one round trip less per call)
-        out = _lib.pinned_empty((n, n_out), np.complex128)
-        t_out = np.empty(n, dtype=float)
-        got = c_i64(0)
-        rc = _lib.load().bms_transform_modes_pipelined(ctx.handle, ctypes.byref(inp), ctypes.byref(transformation), pieces,
-                                                       dptr(t_out), vptr(out), ctypes.byref(got))
-        try:
-            ctx.check(rc, "bms_transform_modes_pipelined")
-        except NotImplementedError:
-            return None
-        return t_out[: got.value], out[: got.value]
-    import threading
-
-    n = t.shape[0]
-    # each shard only validates its own time window; a series that is not increasing everywhere goes to the one-call path,
-    # whose full check raises the ValueError the reference's callers expect
-    if not np.all(np.diff(t) > 0):
-        return None
-    i_lo, i_hi = output_window(t, transformation, ctx=ctx)
-    n_new = i_hi - i_lo
-    if n_new < 8 * PIPELINE_PIECES:
-        return None
-    peer = getattr(ctx, "_pipeline_peer", None)
-    if peer is None:
-        peer = _lib.Context(ctx.device)
-        ctx._pipeline_peer = peer
-    cuts = [i_lo + (n_new * k) // PIPELINE_PIECES for k in range(PIPELINE_PIECES + 1)]
-    out = _lib.pinned_empty((n_new, n_out), np.complex128)
-    t_out = np.empty(n_new, dtype=float)
-    lib = _lib.load()
-    errors = [None, None]
-
-    def run(which, context):
-        try:
-            for k in range(which, PIPELINE_PIECES, 2):
-                a, b = cuts[k], cuts[k + 1]
-                (r0, r1), _ = shard_plan(t, transformation, a, b)
-                piece = bms_wm_input()
-                ctypes.memmove(ctypes.byref(piece), ctypes.byref(inp), ctypes.sizeof(piece))
-                piece.data = data[r0:].ctypes.data
-                sh = bms_shard(int(r0), int(r1 - r0), int(a), int(b))
-                got, first = c_i64(0), c_i64(0)
-                rc = lib.bms_transform_modes_shard(
-                    context.handle, ctypes.byref(piece), ctypes.byref(transformation), ctypes.byref(sh),
-                    dptr(t_out[a - i_lo :]),
-                    vptr(out[a - i_lo :]), ctypes.byref(got), ctypes.byref(first),
-                )
-                context.check(rc, "bms_transform_modes")
-                if got.value != b - a or first.value != a:
-                    raise RuntimeError(f"pipelined shard [{a}, {b}) produced {got.value} rows from {first.value}")
-        except BaseException as e:  # noqa: BLE001 -- re-raised by the caller's thread
-            errors[which] = e
-
-    other = threading.Thread(target=run, args=(1, peer))
-    other.start()
-    run(0, ctx)
-    other.join()
-    for e in errors:
-        if isinstance(e, NotImplementedError):  # a series the engine does not shard: the one-call path handles it
-            return None
-    for e in errors:
-        if e is not None:
-            raise e
-    return t_out, out
+_transform_modes_multi = _transform_modes_pipelined  # (the dealt call site's name: `devices=` calls are observed under it on their own)
 
 
 def transform_modes(
@@ -420,42 +376,27 @@ def transform_modes(
     ctx = _ctx(ctx) if not devices else contexts_for(devices[:1], first=ctx)[0]
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
-    inp = bms_wm_input()
-    inp.n_times = n
-    inp.t = dptr(t)
-    keep = [t]
-    if device:
-        inp.data = int(data)
-        inp.ld = int(ld)
-        inp.mem = BMS_DEVICE
-    else:
+    n_rows = n if shard is None else int(shard[1])
+    if not device:
         data = _lib.as_c16(data)
-        n_rows = n if shard is None else int(shard[1])
         if data.shape != (n_rows, LM_total_size(ell_min, ell_max)):
             raise ValueError(f"data shape {data.shape} inconsistent with rows={n_rows}, ell range [{ell_min}, {ell_max}]")
-        inp.data = data.ctypes.data
-        inp.ld = data.shape[1]
-        inp.mem = BMS_HOST
-        keep.append(data)
-    inp.ell_min, inp.ell_max = int(ell_min), int(ell_max)
-    inp.spin_weight, inp.conformal_weight, inp.type_term = int(spin_weight), int(conformal_weight), int(type_term)
-    inp.n_aux = len(aux)
-    aux_host = []
-    for i, a in enumerate(aux):
+    aux_host = []  # (the host companions, kept alive through the call)
+    aux_in = []
+    for a in aux:
         adata, amin, amax, aspin, acoeff, apower = a[:6]
         if device:
-            inp.aux_data[i] = int(adata)
-            inp.aux_ld[i] = int(a[6])
-        else:
-            adata = _lib.as_c16(adata)
-            if adata.shape != ((n if shard is None else int(shard[1])), LM_total_size(amin, amax)):
-                raise ValueError("auxiliary data shape mismatch")
-            keep.append(adata)
-            aux_host.append(adata)
-            inp.aux_data[i] = adata.ctypes.data
-            inp.aux_ld[i] = adata.shape[1]
-        inp.aux_ell_min[i], inp.aux_ell_max[i], inp.aux_spin[i] = int(amin), int(amax), int(aspin)
-        inp.aux_coeff[i], inp.aux_power[i] = float(acoeff), int(apower)
+            aux_in.append((adata, a[6], amin, amax, aspin, acoeff, apower))
+            continue
+        adata = _lib.as_c16(adata)
+        if adata.shape != (n_rows, LM_total_size(amin, amax)):
+            raise ValueError("auxiliary data shape mismatch")
+        aux_host.append(adata)
+        aux_in.append((adata.ctypes.data, adata.shape[1], amin, amax, aspin, acoeff, apower))
+    if device:
+        inp = _wm_input(t, data, ld, BMS_DEVICE, ell_min, ell_max, spin_weight, conformal_weight, type_term, aux_in)
+    else:
+        inp = _wm_input(t, data.ctypes.data, data.shape[1], BMS_HOST, ell_min, ell_max, spin_weight, conformal_weight, type_term, aux_in)
     s = abs(int(spin_weight))
     n_out = LM_total_size(s, transformation.ell_max_out)
     n_new = c_i64(0)
@@ -488,14 +429,14 @@ def transform_modes(
             for adata in aux_host:  # (the companions travel with every shard's rows: the same rate for them)
                 _lib.register_if_reused(adata)
     if devices:
-        ctxs = contexts_for(devices, first=ctx)
-        res = _transform_modes_multi(t, data, inp, transformation, n_out, ctxs, int(pieces or pieces_for(devices, n, ell_max, data.nbytes)))
+        res = _transform_modes_multi(t, data, inp, transformation, n_out, contexts_for(devices, first=ctx),
+                                     int(pieces or pieces_for(devices, n, ell_max, data.nbytes)))
         if res is not None:
             return res
     elif shard is None and (not aux or pieces is not None) and not os.environ.get("SCRI_AMD_NO_PIPELINE"):
         chosen = int(pieces) if pieces is not None else auto_pieces(n, ell_max, data.nbytes)
         if pieces is not None or chosen >= 2:
-            res = _transform_modes_pipelined(t, data, inp, transformation, n_out, ctx, pieces=chosen)
+            res = _transform_modes_pipelined(t, data, inp, transformation, n_out, [ctx], chosen)
             if res is not None:
                 return res
     out = _lib.pinned_empty((max(n_alloc, 1), n_out), np.complex128)
@@ -522,17 +463,9 @@ def transform_modes_series(t, data, ell_min, ell_max, spin_weight, conformal_wei
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
     if device:
-        inp = bms_wm_input()
-        inp.n_times, inp.t = n, dptr(t)
-        inp.data, inp.ld, inp.mem = int(data), LM_total_size(ell_min, ell_max) * int(n_series), BMS_DEVICE
-        inp.ell_min, inp.ell_max = int(ell_min), int(ell_max)
-        inp.spin_weight, inp.conformal_weight, inp.type_term = int(spin_weight), int(conformal_weight), int(type_term)
-        inp.n_aux = len(aux)
-        for i, a in enumerate(aux):
-            adata, amin, amax, aspin, acoeff, apower = a[:6]
-            inp.aux_data[i], inp.aux_ld[i] = int(adata), LM_total_size(amin, amax) * int(n_series)
-            inp.aux_ell_min[i], inp.aux_ell_max[i], inp.aux_spin[i] = int(amin), int(amax), int(aspin)
-            inp.aux_coeff[i], inp.aux_power[i] = float(acoeff), int(apower)
+        aux_in = [(a[0], LM_total_size(a[1], a[2]) * int(n_series)) + tuple(a[1:6]) for a in aux]
+        inp = _wm_input(t, data, LM_total_size(ell_min, ell_max) * int(n_series), BMS_DEVICE, ell_min, ell_max, spin_weight, conformal_weight,
+                        type_term, aux_in)
         t_out = np.empty(max(n, 1), dtype=float)
         n_new = c_i64(0)
         rc = _lib.load().bms_transform_modes_series(ctx.handle, ctypes.byref(inp), int(n_series), ctypes.byref(transformation), dptr(t_out),
@@ -543,23 +476,14 @@ def transform_modes_series(t, data, ell_min, ell_max, spin_weight, conformal_wei
     if data.ndim != 3 or data.shape[:2] != (n, LM_total_size(ell_min, ell_max)):
         raise ValueError(f"data shape {data.shape} inconsistent with {n} time steps, ell range [{ell_min}, {ell_max}] and one trailing axis")
     n_series = data.shape[2]
-    inp = bms_wm_input()
-    inp.n_times = n
-    inp.t = dptr(t)
-    keep = [t, data]
-    inp.data, inp.ld, inp.mem = data.ctypes.data, data.shape[1] * n_series, BMS_HOST
-    inp.ell_min, inp.ell_max = int(ell_min), int(ell_max)
-    inp.spin_weight, inp.conformal_weight, inp.type_term = int(spin_weight), int(conformal_weight), int(type_term)
-    inp.n_aux = len(aux)
-    for i, a in enumerate(aux):
-        adata, amin, amax, aspin, acoeff, apower = a[:6]
-        adata = _lib.as_c16(adata)
-        if adata.shape != (n, LM_total_size(amin, amax), n_series):
+    aux_host = []  # (kept alive through the call)
+    for a in aux:
+        adata = _lib.as_c16(a[0])
+        if adata.shape != (n, LM_total_size(a[1], a[2]), n_series):
             raise ValueError("auxiliary data shape mismatch")
-        keep.append(adata)
-        inp.aux_data[i], inp.aux_ld[i] = adata.ctypes.data, adata.shape[1] * n_series
-        inp.aux_ell_min[i], inp.aux_ell_max[i], inp.aux_spin[i] = int(amin), int(amax), int(aspin)
-        inp.aux_coeff[i], inp.aux_power[i] = float(acoeff), int(apower)
+        aux_host.append(adata)
+    aux_in = [(h.ctypes.data, h.shape[1] * n_series) + tuple(a[1:6]) for h, a in zip(aux_host, aux)]
+    inp = _wm_input(t, data.ctypes.data, data.shape[1] * n_series, BMS_HOST, ell_min, ell_max, spin_weight, conformal_weight, type_term, aux_in)
     n_out = transformation.n_theta * transformation.n_phi if grid else LM_total_size(abs(int(spin_weight)), transformation.ell_max_out)
     out = _lib.pinned_empty((max(n, 1), n_out, n_series), np.complex128)
     t_out = np.empty(max(n, 1), dtype=float)
@@ -641,35 +565,20 @@ def transform_abd(u, raw, ell_max, transformation, ctx=None, shard=None, device=
         u_out = np.empty(max(fs_out, 1), dtype=float)
     out = _lib.pinned_empty((6, max(fs_out, 1), n_out), np.complex128)
     n_pieces = int(pieces or (pieces_for(devices, n, None, raw.nbytes, abd=True) if devices else auto_pieces_abd(raw.nbytes)))
-    if devices and fs_out >= 8 * n_pieces and np.all(np.diff(u) > 0):
+    ctxs = None
+    if devices:
         # one process, several GPUs: the time shards dealt over one context per device, rows + halo shipped at upload time
-        ctxs = contexts_for(devices, first=ctx)
-        got = c_i64(0)
-        rc = _lib.load().bms_transform_abd_multi(_context_array(ctxs), len(ctxs), dptr(u), vptr(raw), n, int(ell_max), ctypes.byref(transformation),
-                                                 n_pieces, dptr(u_out), vptr(out), ctypes.byref(got))
-        try:
-            ctxs[0].check(rc, "bms_transform_abd_multi")
-        except NotImplementedError:
-            rc = None  # graded time steps are not sharded: the one-call path below takes them
-        if rc is not None:
-            if got.value != out.shape[1]:
-                raise RuntimeError(f"the dealt ABD transform produced a window of {got.value} rows, {out.shape[1]} expected")
-            return u_out, out
+        if fs_out >= 8 * n_pieces and np.all(np.diff(u) > 0):
+            ctxs = contexts_for(devices, first=ctx)
     elif (shard is None and (pieces is not None or n_pieces >= 2) and fs_out >= 8 * n_pieces
           and not os.environ.get("SCRI_AMD_NO_PIPELINE")):
-        # a long series in host memory: uploads, kernels and downloads of consecutive time shards side by side
-        rc = _lib.load().bms_transform_abd_pipelined(
-            ctx.handle, dptr(u), vptr(raw), n, int(ell_max), ctypes.byref(transformation), n_pieces, dptr(u_out), vptr(out),
-            ctypes.byref(n_new),
-        )
-        try:
-            ctx.check(rc, "bms_transform_abd_pipelined")
-        except NotImplementedError:
-            rc = None  # graded time steps are not sharded: the one-call path below takes them
-        if rc is not None:
-            if n_new.value != out.shape[1]:
-                raise RuntimeError(f"pipelined ABD transform produced {n_new.value} rows, expected {out.shape[1]}")
-            return u_out, out
+        ctxs = [ctx]  # a long series in host memory: uploads, kernels and downloads of consecutive time shards side by side
+    # (graded time steps are not sharded: the one-call path below takes them)
+    if ctxs and _run_pipelined(ctxs, "bms_transform_abd_pipelined", "bms_transform_abd_multi", dptr(u), vptr(raw), n, int(ell_max),
+                               ctypes.byref(transformation), n_pieces, dptr(u_out), vptr(out), ctypes.byref(n_new)):
+        if n_new.value != out.shape[1]:
+            raise RuntimeError(f"the pipelined ABD transform produced {n_new.value} rows, expected {out.shape[1]}")
+        return u_out, out
     rc = _lib.load().bms_transform_abd_shard(
         ctx.handle, dptr(u), vptr(raw), BMS_HOST, n, int(ell_max), ctypes.byref(transformation), shp, dptr(u_out), vptr(out),
         ctypes.byref(n_new), ctypes.byref(first),

@@ -1,7 +1,7 @@
 // Host-side sanitizer run (no GPU sanitizer exists on this pool: ASan / UBSan cover what runs on the host).
 // `make -C scri_amd/csrc SAN=1` compiles this file -- which INCLUDES the host side of the engine (engine_*.hip, split by entry family
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
-// parts, chunk walks, rotor / harmonic / conformal tables and the frame integrator over the five BASELINE shapes, 1..8 shards,
+// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables and the frame integrator over the five BASELINE shapes, 1..8 shards,
 // 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
@@ -112,6 +112,28 @@ void run_shape(const Shape& s) {
       covered = o1;
     }
     REQUIRE(covered == i_hi);
+  }
+  // the pieces of the pipelined calls (plan_pieces) read the rows bms_shard_plan names for their output ranges
+  for (int pieces : {1, 3, 10, 20}) {
+    PiecePlan P;
+    plan_pieces(T, t.data(), s.n, i_lo, i_hi, pieces, 0, pieces, P);
+    if (i_hi == i_lo) {
+      REQUIRE(P.p0 == P.p1);
+      continue;
+    }
+    REQUIRE(1 <= P.pieces && P.pieces <= pieces && P.p0 == 0 && P.p1 == P.pieces);
+    REQUIRE(P.cut[0] == i_lo && P.cut[P.pieces] == i_hi);
+    int64_t max_rows = 0, max_out = 0;
+    for (int k = 0; k < P.pieces; ++k) {
+      REQUIRE(P.rows_out(k) >= 8 || P.pieces == 1);
+      int64_t need[2], win[2];
+      REQUIRE(bms_shard_plan(nullptr, t.data(), s.n, &tr, P.cut[k], P.cut[k + 1], need, win) == BMS_OK);
+      REQUIRE((win[0] <= P.cut[k] && P.cut[k + 1] <= win[1]) || s.abd);  // (the ABD window differs by the rounding of 1/gamma only)
+      if (win[0] <= P.cut[k] && P.cut[k + 1] <= win[1]) REQUIRE(need[0] == P.r0[k] && need[1] == P.r1[k]);
+      max_rows = std::max(max_rows, P.r1[k] - P.r0[k]);
+      max_out = std::max(max_out, P.rows_out(k));
+    }
+    REQUIRE(P.max_rows == max_rows && P.max_out == max_out);
   }
   // rotor grid, harmonics, conformal factors of the (boosted, rotated) grid through the ctx = NULL building blocks
   std::vector<double> rot((size_t)4 * T.n_pix);
