@@ -361,6 +361,19 @@ int bms_multishuffle(bms_ctx* ctx, const void* in, void* out, int mem, int64_t n
 /* fletcher32(data): 16-bit words, modulus 65535; returns c1 << 16 | c0 */
 int bms_fletcher32(bms_ctx* ctx, const void* data, int mem, int64_t n_bytes, uint32_t* checksum);
 
+/* ---- extrapolation of finite-radius waveforms to null infinity (scri/extrapolation.py:1270-1474, _Extrapolate) ------------
+ * For every time step t and order N = orders[o]: the constant term of the least-squares polynomial of degree N in x = 1/r through
+ * the n_radii points (1 / radii[i][t], series[i][t][m]), for each mode m -- numpy.polynomial.polynomial.polyfit(x, y, N)[0] of
+ * extrapolation.py:1434 (columns x^k scaled by their norms, Householder QR; one factorisation per step serves every order).
+ * series[i]: c16[n_times][ld[i]] (n_modes columns used); radii: f8[n_radii][n_times]; out: c16[n_orders][n_times][n_modes]; all three
+ * in `mem` (series and ld themselves are host arrays).  0 <= orders[o] < n_radii <= 64, orders[o] <= 15; negative orders (copies of
+ * one radius) are the caller's.  A step whose fit of order N is rank deficient (min |R_kk| <= n_radii eps max |R_kk|, numpy's rcond)
+ * gets NaN in that order's row, and is counted in n_deficient[o] (host int64[n_orders], may be NULL).  Host memory goes through the
+ * device in `blocks` pipelined blocks of time steps (0: chosen by size); the result does not depend on the number of blocks. */
+int bms_extrapolate(bms_ctx* ctx, int n_radii, const void* const* series, const int64_t* ld, int mem, int64_t n_times,
+                    int64_t n_modes, const double* radii, int n_orders, const int* orders, void* out, int blocks,
+                    int64_t* n_deficient);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,8 @@ from .bms_transformations import LorentzTransformation, BMSTransformation  # noq
 from . import flux  # noqa: E402,F401
 from . import utilities  # noqa: E402,F401
 from . import sample_waveforms  # noqa: E402,F401
+from . import extrapolation  # noqa: E402,F401
+from .extrapolation import _Extrapolate, extrapolate_waveforms  # noqa: E402,F401
 from .flux import energy_flux, momentum_flux, angular_momentum_flux, boost_flux, poincare_fluxes  # noqa: E402,F401
 from .mode_calculations import (  # noqa: E402,F401
     LdtVector, LVector, LLComparisonMatrix, LLMatrix, LLDominantEigenvector, angular_velocity, corotating_frame, inner_product,
@@ -77,7 +79,8 @@ WaveformModes.align_decomposition_frame_to_modes = align_decomposition_frame_to_
 
 def patch_scri(scri=None, ctx=None):
     """Graft the GPU implementations onto an installed `scri` (opt-in drop-in): the two rotation
-    kernels, `WaveformModes.transform` and `AsymptoticBondiData.transform`.  Returns the patched attribute names."""
+    kernels, `WaveformModes.transform`, `AsymptoticBondiData.transform` and, where `scri` has its `extrapolation` module,
+    `extrapolation._Extrapolate`.  Returns the patched attribute names."""
     if scri is None:
         import scri  # only available where the reference is installed
     from . import adapters

@@ -9,13 +9,14 @@ SURVEY section 8(b):
     `rotate_physical_system`, `to_inertial_frame` and everything else that reaches them keep the reference's argument
     checks, frame bookkeeping and history, and only the arithmetic moves to the GPU;
   * `scri.WaveformModes.transform` (waveform_modes.py:705-719 -> waveform_grid.py:615-630);
-  * `scri.AsymptoticBondiData.transform` (transformations.py:199-431).
+  * `scri.AsymptoticBondiData.transform` (transformations.py:199-431);
+  * `scri.extrapolation._Extrapolate` (extrapolation.py:1270-1474), when `scri` has an `extrapolation` submodule.
 
 The originals stay reachable as `<name>_reference`; `uninstall` puts them back.
 """
 import numpy as np
 
-from . import engine, waveform_grid
+from . import engine, extrapolation, waveform_grid
 from .asymptotic_bondi_data import _process_transformation_kwargs as _abd_kwargs
 from .waveform_modes import WaveformModes as _WM
 
@@ -106,6 +107,28 @@ def install(scri, ctx=None):
         scri.AsymptoticBondiData.transform_reference = scri.AsymptoticBondiData.transform
     scri.AsymptoticBondiData.transform = abd_transform
     patched.append("AsymptoticBondiData.transform")
+
+    # ---- scri.extrapolation._Extrapolate (extrapolation.py:1270-1474), the fit the file driver `extrapolate` calls (:839): the
+    # driver keeps its file I/O, frames and history, only the per-time-step fit runs on the GPU.  Its waveforms are scri's own, so
+    # they are wrapped on the way in and the results are scri.WaveformModes again.
+    if hasattr(scri, "extrapolation"):
+        ext = scri.extrapolation
+
+        def _Extrapolate(FiniteRadiusWaveforms, Radii, ExtrapolationOrders, Omegas=None, NoiseFloor=None):
+            ws = [_WM(t=W.t, data=W.data, ell_min=W.ell_min, ell_max=W.ell_max, dataType=W.dataType, frameType=W.frameType,
+                      frame=getattr(W, "frame", None), r_is_scaled_out=W.r_is_scaled_out, m_is_scaled_out=W.m_is_scaled_out,
+                      ctx=ctx) for W in FiniteRadiusWaveforms]
+            for w, W in zip(ws, FiniteRadiusWaveforms):
+                w.history = list(W.history)  # (without the wrapper's own constructor line)
+            out = extrapolation._Extrapolate(ws, Radii, ExtrapolationOrders, Omegas, NoiseFloor)
+            return [scri.WaveformModes(t=w.t, data=w.data, frame=w.frame, history=[h for h in w.history if not h.startswith(f"{w} = ")],
+                                       ell_min=w.ell_min, ell_max=w.ell_max, frameType=w.frameType, dataType=w.dataType,
+                                       r_is_scaled_out=w.r_is_scaled_out, m_is_scaled_out=w.m_is_scaled_out) for w in out]
+
+        if not hasattr(ext, "_Extrapolate_reference"):
+            ext._Extrapolate_reference = ext._Extrapolate
+        ext._Extrapolate = _Extrapolate
+        patched.append("extrapolation._Extrapolate")
     return patched
 
 
@@ -120,3 +143,7 @@ def uninstall(scri):
         if hasattr(cls, "transform_reference"):
             cls.transform = cls.transform_reference
             del cls.transform_reference
+    ext = getattr(scri, "extrapolation", None)
+    if ext is not None and hasattr(ext, "_Extrapolate_reference"):
+        ext._Extrapolate = ext._Extrapolate_reference
+        del ext._Extrapolate_reference

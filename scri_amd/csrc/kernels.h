@@ -350,4 +350,17 @@ hipError_t launch_abd_mix(hipStream_t stream, const AbdGrids& g, long long ld, i
 hipError_t launch_affine_cols(hipStream_t stream, double* Y, long long ld, int n_cols, long long n_rows,
                               const double* off, const double* scale);
 
+// ---- extrapolation to null infinity (scri/extrapolation.py:1394-1434; kernels_extrapolate.hip)
+constexpr int EXTRAP_MAX_RADII = 64;  // one radius per lane of a wavefront
+constexpr int EXTRAP_MAX_ORDER = 15;
+struct ExtrapSource {  // the series of one radius: c16 rows of stride ld
+  const double2* p;
+  long long ld;
+};
+// out[o][t][m] (o stride out_order_stride, row stride n_modes) = constant term of the fit of order orders[o] of src[i].p[t][m] against
+// 1 / radii[i * r_ld + t], i < n_radii; deficient[o] += the steps whose fit of order orders[o] is rank deficient (those rows are NaN)
+hipError_t launch_extrapolate(hipStream_t stream, const ExtrapSource* src, int n_radii, const double* radii, long long r_ld,
+                              long long n_times, int n_modes, const int* orders, int n_orders, double2* out, long long out_order_stride,
+                              unsigned long long* deficient);
+
 }  // namespace bms

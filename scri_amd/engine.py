@@ -698,6 +698,50 @@ def cubic_spline(x, y, x_new, ctx=None):
     return out.reshape((xn.shape[0],) + tail)
 
 
+def extrapolate(series, radii, orders, ctx=None, device=False, out=None, blocks=0):
+    """Constant term of the polynomial fit in 1/r of every mode at every time step, for each order (scri/extrapolation.py:1434:
+    numpy.polynomial.polynomial.polyfit(1 / radii[:, t], y[:, t, :], N)[0, :]), on the GPU (bms_extrapolate).
+
+    Host data: `series` holds n_radii arrays c16[n_times, n_modes] (row strides may differ), `radii` is f8[n_radii, n_times].
+    device=True: `series` holds n_radii device addresses of contiguous c16[n_times, n_modes], `radii` is (device address of
+    f8[n_radii][n_times], n_times, n_modes) and `out` the device address of c16[n_orders][n_times][n_modes].
+    orders: 0 <= N < n_radii.  blocks: pipelined blocks of time steps for host data (0: chosen by size).
+    Returns (out c16[n_orders, n_times, n_modes], or None with device=True; the number of rank-deficient steps per order, whose
+    rows are NaN)."""
+    ctx = _ctx(ctx)
+    orders_c = np.ascontiguousarray(orders, dtype=np.int32)
+    n_r = len(series)
+    counts = np.zeros(len(orders_c), dtype=np.int64)
+    ptrs = (ctypes.c_void_p * max(n_r, 1))()
+    lds = np.zeros(max(n_r, 1), dtype=np.int64)
+    if device:
+        r_ptr, n_times, n_modes = radii
+        for i, p in enumerate(series):
+            ptrs[i], lds[i] = int(p), n_modes
+        mem, out_ptr, r_arg, keep = BMS_DEVICE, c_vp(int(out)), c_vp(int(r_ptr)), None
+    else:
+        keep = [np.asarray(s) for s in series]
+        for i, s in enumerate(keep):
+            if s.dtype != np.complex128 or s.ndim != 2 or s.strides[1] != 16 or s.strides[0] % 16 or s.strides[0] < 16 * s.shape[1]:
+                keep[i] = s = np.ascontiguousarray(s, dtype=np.complex128)  # (a row view of stride ld >= n_modes is passed as it is)
+            ptrs[i], lds[i] = s.ctypes.data, s.strides[0] // 16
+        n_times, n_modes = keep[0].shape if n_r else (0, 0)
+        for s in keep:
+            if s.shape != (n_times, n_modes):
+                raise ValueError(f"every series must have shape ({n_times}, {n_modes}), got {s.shape}")
+        r_host = np.ascontiguousarray(radii, dtype=float)
+        if r_host.shape != (n_r, n_times):
+            raise ValueError(f"radii must have shape ({n_r}, {n_times}), got {r_host.shape}")
+        out = np.empty((len(orders_c), n_times, n_modes), dtype=np.complex128)
+        mem, out_ptr, r_arg = BMS_HOST, vptr(out), dptr(r_host)
+    rc = _lib.load().bms_extrapolate(
+        ctx.handle, n_r, ptrs, lds.ctypes.data_as(ctypes.POINTER(c_i64)), mem, int(n_times), int(n_modes), r_arg, len(orders_c),
+        orders_c.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), out_ptr, int(blocks), counts.ctypes.data_as(ctypes.POINTER(c_i64)),
+    )
+    ctx.check(rc, "bms_extrapolate")
+    return (None if device else out), counts
+
+
 def spline_derivative(x, y, x_new, order=0, ctx=None):
     """scipy CubicSpline(x, y, axis=0) differentiated (`order` 1..3) or integrated (`order` -1 .. -16; zero at x[0]) and
     evaluated at x_new, for complex y[N, ...]."""
