@@ -103,6 +103,61 @@ struct SynthesisPlan {
   int* d_meta = nullptr;
 };
 
+// ---------------------------------------------------------------------------------------------- set-up kept across calls
+// What a transformation sets up before its first heavy kernel depends on the time axis and on the pair (transformation, field
+// description) only, and a caller transforms h, Psi4 ... sigma with one transformation on one axis.  The context keeps
+// ONE entry of each kind from the last call that built it, found again BY CONTENT (never by address), in device blocks of their own
+// names ("tc_*", "pc_*") that no other route writes.  Route option NO_PLAN_CACHE switches both off; bms_ctx_set_option drops them.
+constexpr int64_t TIME_CACHE_MAX_SAMPLES = 1 << 21;   // 16 MiB of samples on the host, 200 bytes per sample on the device
+constexpr size_t SETUP_CACHE_MAX_BYTES = 256u << 20;  // per-direction block / synthesis matrices: larger ones are rebuilt by every call
+
+struct PixelTables {
+  int n_theta = 0, n_phi = 0, n_pix = 0;
+  std::vector<Quat> R;
+  std::vector<double> k, alpha, skew_a, skew_b;
+  double beta = 0, gamma = 1, tt = 0;
+  bool nontrivial = false;  // beta != 0 or any supertranslation mode beyond l = 0 nonzero
+  double uprm_scale_min = 0, uprm_scale_max = 0;
+};
+
+struct DevPixel {
+  double *rotors, *k, *alpha, *skew_a, *skew_b, *col_off, *col_scale, *xa, *xb, *ethk, *etha, *ethetha, *ik, *ik3;
+  const int* col_of_pixel = nullptr;  // set when the grid is stored as a column plan (kernels_swsh.hip, pixel_sort_kernel)
+};
+
+struct TimeAxisCache {  // knots [lo, hi) of an axis of n samples with their B-spline tables for knots [j0, j1) (upload_times_bspline)
+  bool valid = false;   // the device blocks hold the tables of `host`
+  bool in_use = false;  // the running call reads the device blocks (found or built by it)
+  bool hit = false;     // ... and found them
+  uint64_t gen = 0;     // counts the builds
+  int64_t n = 0, lo = 0, hi = 0, j0 = 0, j1 = 0;
+  std::vector<double> host;         // t[lo, hi) as uploaded
+  const double* pending = nullptr;  // built in the running call from these samples; copied to `host` where the host waits anyway (time_axis_commit)
+  bool walked = false, regular = true;  // outcome of walk_time_axis over [lo, hi), once a call has walked them
+  double* d_x = nullptr;                // all three indexed by GLOBAL knot number
+  BsplineTable* d_tab = nullptr;
+  BsplineForward* d_fwd = nullptr;
+};
+struct PixelCache {  // per-direction tables of one (transformation, field description) (device_pixel_tables)
+  bool valid = false, in_use = false, hit = false;
+  uint64_t gen = 0;
+  std::string key;  // every input of device_pixel_tables, by value
+  PixelTables T;
+  DevPixel D;
+  // the dense synthesis matrix of the WaveformModes route, built behind the tables (Bsyn0 with its offset row)
+  bool B_valid = false;
+  int B_spin = 0, B_ell_min = 0, B_ell_max = 0, B_cols = 0;
+  double* d_B = nullptr;
+  // the five of the AsymptoticBondiData route (with sigma's offset row in the spin-2 one when B_sigma)
+  bool B5_valid = false, B5_sigma = false;
+  int B5_ell_max = 0, B5_cols = 0;
+  double* d_B5[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // output window of (axis entry, this entry): a function of the two alone
+  bool win_valid = false, win_abd = false;
+  uint64_t win_tgen = 0, win_pgen = 0;
+  int64_t win_lo = 0, win_hi = 0;
+};
+
 struct bms_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -162,6 +217,8 @@ struct bms_ctx {
   std::vector<hipEvent_t> event_pool;
   double tag_ms[BMS_TAG_COUNT] = {0};
   long long tag_calls[BMS_TAG_COUNT] = {0};
+  TimeAxisCache tcache;  // set-up kept across calls (above)
+  PixelCache pcache;
 };
 
 static inline void note_alloc_failure(bms_ctx* c) {
@@ -432,15 +489,6 @@ constexpr int ROW_MARGIN = SPLINE_HALO + 2;
 
 inline long long round_up(long long a, long long b) { return (a + b - 1) / b * b; }
 
-struct PixelTables {
-  int n_theta = 0, n_phi = 0, n_pix = 0;
-  std::vector<Quat> R;
-  std::vector<double> k, alpha, skew_a, skew_b;
-  double beta = 0, gamma = 1, tt = 0;
-  bool nontrivial = false;  // beta != 0 or any supertranslation mode beyond l = 0 nonzero
-  double uprm_scale_min = 0, uprm_scale_max = 0;
-};
-
 struct FieldPlan {  // one field to synthesise: input modes, its SWSH matrix
   const double* d_data = nullptr;  // device c16[n][ld]
   int64_t ld = 0;
@@ -454,11 +502,6 @@ struct FieldPlan {  // one field to synthesise: input modes, its SWSH matrix
 // 8 x 1e5-step series uploads and checks 1e5 + 128 samples, not 8e5 (the host still sees the global array: window
 // search and chunk planning are binary searches on it).
 constexpr int64_t TIME_MARGIN = 64;
-
-struct DevPixel {
-  double *rotors, *k, *alpha, *skew_a, *skew_b, *col_off, *col_scale, *xa, *xb, *ethk, *etha, *ethetha, *ik, *ik3;
-  const int* col_of_pixel = nullptr;  // set when the grid is stored as a column plan (kernels_swsh.hip, pixel_sort_kernel)
-};
 
 struct PieceTables {  // tables shared by the pieces of one pipelined call: per direction, and per knot of the WHOLE series
   PixelTables T;
@@ -528,6 +571,18 @@ BMS_INTERNAL int upload_times(bms_ctx* c, const double* t, int64_t n, int64_t lo
                         SplineTable** d_tab);
 BMS_INTERNAL int upload_times_bspline(bms_ctx* c, const double* t, int64_t n, int64_t lo, int64_t hi, int64_t j0, int64_t j1, double** d_x,
                                 BsplineTable** d_tab, BsplineForward** d_fwd);
+// (the kept entries serve a call only once its own set-up has found or built them)
+inline void begin_setup_reuse(bms_ctx* c) {
+  c->tcache.in_use = c->tcache.hit = false;
+  c->tcache.pending = nullptr;
+  c->pcache.in_use = c->pcache.hit = false;
+}
+// the `reuse` argument of device_pixel_tables for a transformation under this shard description: never 0, one value per column part
+inline int reuse_tag(const bms_shard* sh) { return 1 + ((sh && sh->col_parts > 1 && sh->col_part >= 0) ? 1 + (sh->col_part & 0x7fff) + ((sh->col_parts & 0x7fff) << 15) : 0); }
+BMS_INTERNAL void time_axis_commit(bms_ctx* c, bool walked, bool regular);
+BMS_INTERNAL void drop_setup_caches(bms_ctx* c);
+BMS_INTERNAL bool cached_window(bms_ctx* c, bool abd, int64_t& i_lo, int64_t& i_hi);
+BMS_INTERNAL void keep_window(bms_ctx* c, bool abd, int64_t i_lo, int64_t i_hi);
 BMS_INTERNAL int stage_in(bms_ctx* c, const char* name, const void* src, int mem, size_t bytes, const double** dev);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
@@ -550,7 +605,7 @@ BMS_INTERNAL int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, P
                                const std::vector<cplx>* coef0, const std::vector<cplx>* coef1, const cplx cv[4], DevPixel& D,
                                int plan, hipStream_t PS = nullptr,
                                const std::function<int(hipStream_t, const DevPixel&, int)>& behind_tables = nullptr,
-                               const std::function<void()>& while_waiting = nullptr);
+                               const std::function<void()>& while_waiting = nullptr, int reuse = 0);
 BMS_INTERNAL int tables_and_window(bms_ctx* c, const bms_transformation* tr, const double* t, int64_t n, bool abd, PixelTables& T, int64_t& i_lo,
                                    int64_t& i_hi);
 BMS_INTERNAL int column_range(bms_ctx* c, const bms_shard* sh, int n_cols, int& cA, int& cB);

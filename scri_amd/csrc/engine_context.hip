@@ -188,6 +188,7 @@ extern "C" int bms_ctx_set_option(bms_ctx* c, const char* name, int64_t value) t
   c->syn_plans.clear();
   c->syn_plans_axis.clear();
   c->ring_verdict = -1;
+  drop_setup_caches(c);
   return BMS_OK;
 } BMS_CATCH(c)
 extern "C" int bms_ctx_get_option(bms_ctx* c, const char* name, int64_t* value) try {

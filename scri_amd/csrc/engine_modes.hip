@@ -311,17 +311,23 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   int rc;
   const bool times_ahead = n >= 8 && in->t && !c->async_pieces && !c->opt.on(OPT_NO_BSPLINE) &&
                            (!sh || (sh->data_row0 >= 0 && sh->data_rows >= 0 && sh->data_row0 + sh->data_rows <= n));
+  begin_setup_reuse(c);
+  bool axis_known = false;  // the axis is one the context has tables for AND has walked: neither is done again
   if (times_ahead) {
     const int64_t r0 = sh ? sh->data_row0 : 0, r1 = r0 + (sh ? sh->data_rows : n);
     if ((rc = upload_times_bspline(c, in->t, n, t_lo, t_hi, r0, r1, &d_x, &d_bstab, &d_bsfwd))) return rc;
+    axis_known = c->tcache.hit && c->tcache.walked;
   }
   // The walk itself is put off as well, to the moment the host would otherwise sit waiting for the per-direction tables: until then
   // the axis is taken to be what it nearly always is (increasing, not graded).  A walk that finds otherwise drains what was queued
   // and either fails the call as it always did or starts it again, walk first.
-  const bool walk_later = times_ahead && c->aux && !walk_first && !c->opt.on(OPT_WALK_FIRST);
+  const bool walk_later = times_ahead && c->aux && !walk_first && !c->opt.on(OPT_WALK_FIRST) && !axis_known;
   int walk_rc = BMS_OK;
   bool walked = false, walk_regular = true;
-  if (walk_later) {
+  if (axis_known) {
+    rc = validate_transformation(c, n, in->t, tr, 4);
+    regular_mesh = c->tcache.regular;
+  } else if (walk_later) {
     rc = validate_transformation(c, n, in->t, tr, 4);
   } else
     rc = validate_common(c, n, in->t, tr, t_lo, t_hi, &regular_mesh);
@@ -576,11 +582,21 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
         f.ldb = round_up(2LL * n_cols_, 128);
         const long long rows = round_up(f.K, 16);
         int rc2;
-        if ((rc2 = dev_buf_t(c, "Bsyn0", (size_t)rows * f.ldb, &f.d_B))) return rc2;
+        // (kept with the per-direction tables it is built from, in a block of its own name: PixelCache)
+        PixelCache& pc = c->pcache;
+        const bool keep = pc.in_use && sizeof(double) * (size_t)rows * f.ldb <= SETUP_CACHE_MAX_BYTES;
+        if (keep && pc.B_valid && pc.B_spin == f.spin && pc.B_ell_min == f.ell_min && pc.B_ell_max == f.ell_max && pc.B_cols == n_cols_) {
+          f.d_B = pc.d_B;
+          B_built = true;
+          return BMS_OK;
+        }
+        if (keep) pc.B_valid = false;
+        if ((rc2 = dev_buf_t(c, keep ? "pc_Bsyn0" : "Bsyn0", (size_t)rows * f.ldb, &f.d_B))) return rc2;
         HIP_TRY(c, hipMemsetAsync(f.d_B, 0, sizeof(double) * rows * f.ldb, PS));
         TIMED_ON(c, PS, BMS_TAG_SETUP, launch_swsh_matrix_complex(PS, D.rotors, n_cols_, f.spin, f.ell_min, f.ell_max, f.d_B, f.ldb));
         TIMED_ON(c, PS, BMS_TAG_SETUP, launch_negated_row(PS, D.col_off, f.d_B + (size_t)(f.K / 2) * f.ldb, 2 * n_cols_));
         B_built = true;
+        if (keep) pc.B_valid = true, pc.B_spin = f.spin, pc.B_ell_min = f.ell_min, pc.B_ell_max = f.ell_max, pc.B_cols = n_cols_, pc.d_B = f.d_B;
         return BMS_OK;
       };
     }
@@ -591,7 +607,7 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
         walked = true;
       };
     rc = device_pixel_tables(c, tr, T, psi ? 1 : 0, s, in->conformal_weight, coef0.empty() ? nullptr : &coef0, nullptr, cv, DP, col_plan, c->aux, build_B,
-                             walk);
+                             walk, reuse_tag(sh));
     if (walk_later) {
       if (!walked) walk();  // (device_pixel_tables left before its wait)
       if (walk_rc) return walk_rc;
@@ -616,7 +632,10 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   if ((rc = column_range(c, sh, n_cols, cA, cB))) return rc;
   const int n_pix = cB - cA;  // columns this call synthesises and splines
   int64_t i_lo, i_hi;
-  output_window(T, in->t, n, i_lo, i_hi);
+  if (!cached_window(c, false, i_lo, i_hi)) {
+    output_window(T, in->t, n, i_lo, i_hi);
+    keep_window(c, false, i_lo, i_hi);
+  }
   // produce outputs with global index in [out_i0, out_i1)
   if (sh) {
     i_lo = std::max(i_lo, sh->out_i0);
@@ -856,6 +875,8 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
     HIP_TRY(c, hipMemcpyAsync(data_out, d_out, (size_t)n_new * n_out * 16, hipMemcpyDeviceToHost, S));
   // the new time axis is host work: done while the GPU runs
   for (int64_t i = 0; i < n_new; ++i) t_out[i] = (1 / T.gamma) * (in->t[i_lo + i] - T.tt);
+  // (the walk of this call covered the kept axis entry's range exactly when the entry was asked for ahead of it)
+  time_axis_commit(c, times_ahead, regular_mesh);
   // host tables above are stack/vector memory: wait for the uploads (and results) before returning
   if (!c->async_pieces) HIP_TRY(c, hipStreamSynchronize(S));
   trace.mark("final synchronize");

@@ -474,21 +474,85 @@ int upload_times(bms_ctx* c, const double* t, int64_t n, int64_t lo, int64_t hi,
   return BMS_OK;
 }
 
-// the same for the B-spline form of the spline (kernels_bspline.hip)
+// the same for the B-spline form of the spline (kernels_bspline.hip).  The context keeps the last axis it built these for
+// (TimeAxisCache, engine.h): a call with the same ranges whose samples compare equal BYTE FOR BYTE gets the blocks back without an
+// upload or a kernel; any other call rebuilds them in place.  The blocks have names of their own, so no other route overwrites them;
+// an axis too long to keep (or NO_PLAN_CACHE) goes through the shared names as it always did and leaves the kept entry alone.
 int upload_times_bspline(bms_ctx* c, const double* t, int64_t n, int64_t lo, int64_t hi, int64_t j0, int64_t j1, double** d_x,
                                 BsplineTable** d_tab, BsplineForward** d_fwd) {
+  TimeAxisCache& K = c->tcache;
+  K.in_use = K.hit = false;
+  K.pending = nullptr;
+  const bool keep = !c->opt.on(OPT_NO_PLAN_CACHE) && hi > lo && hi - lo <= TIME_CACHE_MAX_SAMPLES;
+  if (keep && K.valid && K.n == n && K.lo == lo && K.hi == hi && K.j0 == j0 && K.j1 == j1 &&
+      std::memcmp(K.host.data(), t + lo, sizeof(double) * (size_t)(hi - lo)) == 0) {
+    *d_x = K.d_x, *d_tab = K.d_tab, *d_fwd = K.d_fwd;
+    K.in_use = K.hit = true;
+    return BMS_OK;
+  }
+  if (keep) {
+    K.valid = false;
+    ++K.gen;
+  }
   void* vp;
-  int rc = upload(c, "times", t + lo, 8 * (size_t)(hi - lo), &vp);
+  int rc = upload(c, keep ? "tc_times" : "times", t + lo, 8 * (size_t)(hi - lo), &vp);
   if (rc) return rc;
   *d_x = (double*)vp - lo;
   BsplineTable* tab;
   BsplineForward* fwd;
-  if ((rc = dev_buf_t(c, "bspline_table", (size_t)(hi - lo), &tab))) return rc;
-  if ((rc = dev_buf_t(c, "bspline_forward", (size_t)(hi - lo), &fwd))) return rc;
+  if ((rc = dev_buf_t(c, keep ? "tc_bspline_table" : "bspline_table", (size_t)(hi - lo), &tab))) return rc;
+  if ((rc = dev_buf_t(c, keep ? "tc_bspline_forward" : "bspline_forward", (size_t)(hi - lo), &fwd))) return rc;
   *d_tab = tab - lo;
   *d_fwd = fwd - lo;
   TIMED(c, BMS_TAG_SETUP, launch_bspline_table(c->stream, *d_x, n, *d_tab, *d_fwd, lo, std::max(j0, lo), std::min(j1, hi)));
+  if (keep) {
+    K.n = n, K.lo = lo, K.hi = hi, K.j0 = j0, K.j1 = j1;
+    K.d_x = *d_x, K.d_tab = *d_tab, K.d_fwd = *d_fwd;
+    K.walked = false, K.regular = true;
+    K.pending = t + lo;  // (the entry becomes valid once its samples are copied: time_axis_commit)
+    K.in_use = true;
+  }
   return BMS_OK;
+}
+
+// Called where a transformation is about to wait for its kernels: the samples of an entry built by this call are copied into the
+// context there (0.8 MB per 1e5 samples, beside milliseconds of kernels: a cold call is no longer for it), and the outcome of the
+// call's walk over the entry's range [lo, hi), if it made one, is kept with them.  A call that fails before this point leaves no entry.
+void time_axis_commit(bms_ctx* c, bool walked, bool regular) {
+  TimeAxisCache& K = c->tcache;
+  if (!K.in_use) return;
+  if (K.pending) {
+    K.host.assign(K.pending, K.pending + (K.hi - K.lo));
+    K.pending = nullptr;
+    K.valid = true;
+  }
+  if (walked && K.valid) K.walked = true, K.regular = regular;
+}
+
+void drop_setup_caches(bms_ctx* c) {
+  c->tcache.valid = c->tcache.in_use = c->tcache.hit = false;
+  c->tcache.pending = nullptr;
+  c->pcache.valid = c->pcache.in_use = c->pcache.hit = false;
+  c->pcache.B_valid = c->pcache.B5_valid = c->pcache.win_valid = false;
+}
+
+// The output window is a function of the per-direction tables and the WHOLE axis: kept when both entries serve the running call and
+// the axis entry holds every sample (a shard clamps the window to its own range afterwards).
+static bool window_keepable(const bms_ctx* c) {
+  const TimeAxisCache& A = c->tcache;
+  return A.in_use && c->pcache.in_use && A.lo == 0 && A.hi == A.n;
+}
+bool cached_window(bms_ctx* c, bool abd, int64_t& i_lo, int64_t& i_hi) {
+  const PixelCache& P = c->pcache;
+  if (!window_keepable(c) || !c->tcache.hit || !P.hit || !P.win_valid || P.win_abd != abd || P.win_tgen != c->tcache.gen || P.win_pgen != P.gen)
+    return false;
+  i_lo = P.win_lo, i_hi = P.win_hi;
+  return true;
+}
+void keep_window(bms_ctx* c, bool abd, int64_t i_lo, int64_t i_hi) {
+  PixelCache& P = c->pcache;
+  if (!window_keepable(c)) return;
+  P.win_valid = true, P.win_abd = abd, P.win_tgen = c->tcache.gen, P.win_pgen = P.gen, P.win_lo = i_lo, P.win_hi = i_hi;
 }
 
 int stage_in(bms_ctx* c, const char* name, const void* src, int mem, size_t bytes, const double** dev) {
@@ -807,10 +871,41 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
                                const std::vector<cplx>* coef0, const std::vector<cplx>* coef1, const cplx cv[4], DevPixel& D,
                                int plan, hipStream_t PS,
                                const std::function<int(hipStream_t, const DevPixel&, int)>& behind_tables,
-                               const std::function<void()>& while_waiting) {
+                               const std::function<void()>& while_waiting, int reuse) {
   if (!PS) PS = c->stream;
+  const int lst = tr->ell_max_supertranslation, nst = (lst + 1) * (lst + 1);
+  // reuse != 0: the transformations keep the tables of their last (transformation, field description) in the context (PixelCache, engine.h).
+  // The key is every input of this function by value; a call that matches gets the device block, the column permutation and the host
+  // copies back -- nothing for the auxiliary stream, no wait -- and `behind_tables` is asked on the MAIN stream (it keeps what it builds
+  // itself).  `reuse` is part of the key: the transformations pass reuse_tag(shard), so a context that moves to another column part starts
+  // afresh.  Callers that only plan (tables_and_window) pass 0 and write the shared names, never the kept blocks.
+  PixelCache& K = c->pcache;
+  std::string key;
+  const bool keep = reuse != 0 && !c->opt.on(OPT_NO_PLAN_CACHE) && sizeof(double) * 24 * (size_t)tr->n_theta * tr->n_phi <= SETUP_CACHE_MAX_BYTES;
+  if (reuse) K.in_use = K.hit = false;
+  if (keep) {
+    auto put = [&key](const void* p, size_t bytes) { key.append((const char*)p, bytes); };
+    const int ints[11] = {tr->ell_max_supertranslation, tr->n_theta, tr->n_phi, tr->ell_max_out, mode, spin, cw, plan, coef0 ? 1 : 0, coef1 ? 1 : 0, reuse};
+    put(ints, sizeof ints);
+    put(tr->frame_rotation, sizeof tr->frame_rotation);
+    put(tr->boost_velocity, sizeof tr->boost_velocity);
+    put(tr->supertranslation, sizeof(cplx) * nst);
+    if (coef0) put(coef0->data(), sizeof(cplx) * nst);
+    if (coef1) put(coef1->data(), sizeof(cplx) * nst);
+    const cplx cv0[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    put(cv ? cv : cv0, sizeof cv0);
+    if (K.valid && K.key == key) {
+      T = K.T;
+      D = K.D;
+      K.in_use = K.hit = true;
+      return behind_tables ? behind_tables(c->stream, D, T.n_pix) : BMS_OK;
+    }
+    K.valid = K.B_valid = K.B5_valid = K.win_valid = false;
+    K.in_use = true;  // (what is built behind the tables below may already be kept with them)
+    ++K.gen;
+  }
   init_pixel_tables(tr, T);
-  const int n_pix = T.n_pix, lst = tr->ell_max_supertranslation, nst = (lst + 1) * (lst + 1);
+  const int n_pix = T.n_pix;
   const int n_cols = plan ? n_pix - 2 * (tr->n_phi - 1) : n_pix;
   PixelSpec P = base_pixel_spec(tr, T);
   P.mode = mode;
@@ -824,7 +919,7 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
   if (coef0) std::memcpy(coefs.data() + nst, coef0->data(), sizeof(cplx) * nst);
   if (coef1) std::memcpy(coefs.data() + 2 * nst, coef1->data(), sizeof(cplx) * nst);
   cplx* d_coefs;
-  int rc = dev_buf_t(c, "pix_coefs", (size_t)3 * nst, &d_coefs);
+  int rc = dev_buf_t(c, keep ? "pc_coefs" : "pix_coefs", (size_t)3 * nst, &d_coefs);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(d_coefs, coefs.data(), sizeof(cplx) * 3 * nst, hipMemcpyHostToDevice, PS));
   P.st = d_coefs;
@@ -832,7 +927,7 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
   P.c1 = coef1 ? d_coefs + 2 * nst : nullptr;
   // one device block for all per-pixel outputs: 4 (rotor) + 4 scalars + 4 (off, scale) + 4 (xa, xb) + 6 + 2 doubles per pixel
   double* blk;
-  if ((rc = dev_buf_t(c, "pix_block", (size_t)24 * n_pix, &blk))) return rc;
+  if ((rc = dev_buf_t(c, keep ? "pc_block" : "pix_block", (size_t)24 * n_pix, &blk))) return rc;
   D.rotors = blk;
   D.k = blk + 4 * (size_t)n_pix;
   D.alpha = D.k + n_pix;
@@ -853,7 +948,7 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
   O.ethk = D.ethk, O.etha = D.etha, O.ethetha = D.ethetha, O.ik = D.ik, O.ik3 = D.ik3;
   int* d_perm = nullptr;
   if (plan) {
-    if ((rc = dev_buf_t(c, "pix_perm", (size_t)2 * n_pix, &d_perm))) return rc;
+    if ((rc = dev_buf_t(c, keep ? "pc_perm" : "pix_perm", (size_t)2 * n_pix, &d_perm))) return rc;
     TIMED_ON(c, PS, BMS_TAG_SETUP, launch_pixel_sort(PS, P, tr->n_theta, tr->n_phi, plan == 2, d_perm, d_perm + n_pix));
     D.col_of_pixel = d_perm + n_pix;
   }
@@ -889,6 +984,12 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
   T.alpha.assign(back + n_pix, back + n_pix + n_cols);
   T.skew_a.assign(back + 2 * (size_t)n_pix, back + 2 * (size_t)n_pix + n_cols);
   T.skew_b.assign(back + 3 * (size_t)n_pix, back + 3 * (size_t)n_pix + n_cols);
+  if (keep) {
+    K.key = std::move(key);
+    K.T = T;
+    K.D = D;
+    K.valid = K.in_use = true;
+  }
   return BMS_OK;
 }
 
