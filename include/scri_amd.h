@@ -351,6 +351,47 @@ int bms_angular_velocity(bms_ctx* ctx, const double* t, int64_t n_times, const v
 int bms_integrate_angular_velocity(bms_ctx* ctx, const double* t, int64_t n_times, const double* omega, const double R0[4],
                                    double tolerance, double* R_out);
 
+/* ---- frame construction on the device (DESIGN: "Frames as scans") ---------------------------------------------------------
+ * The chain behind to_corotating_frame / to_coprecessing_frame (scri/rotations.py:14-103, scri/mode_calculations.py:316-491) as GPU
+ * kernels: every sequential step of the host versions is a prefix scan.  t is always a host array (n >= 4, strictly increasing);
+ * the per-step arrays live in `mem`.  Rotors are f8[n][4] = (w, x, y, z). */
+/* The frame of bms_integrate_angular_velocity -- same sub-step rule, same Magnus step -- with the interval rotors E_j formed
+ * independently and R_j = E_{j-1} ... E_0 R0 as a prefix product; every R_j is normalised once (R_out[0] = R0 as given).
+ * omega f8[n][3], R_out f8[n][4].  tolerance <= 0: 1e-12.  One difference from the host routine: an interval is cut into at most 2^20
+ * sub-steps (the host routine has no cap), so a series that turns by more than about 2e5 radians between two samples is integrated
+ * less accurately than the host routine would; no status reports it. */
+int bms_frame_from_angular_velocity(bms_ctx* ctx, const double* t, int64_t n_times, const double* omega, int mem, const double R0[4],
+                                    double tolerance, double* R_out);
+/* Unit eigenvector of the largest eigenvalue of each symmetric matrix ll f8[n][9] (cyclic Jacobi), made continuous in time by the
+ * rule of LLDominantEigenvector (scri/mode_calculations.py:316-363): at rough_index (0 <= rough_index < n) the axis points along
+ * `rough`, and going outwards a vector is flipped when it is further from its neighbour than its own length.  axis_out f8[n][3].
+ * n >= 1. */
+int bms_dominant_axis(bms_ctx* ctx, const double* ll, int64_t n_times, int mem, const double rough[3], int64_t rough_index,
+                      double* axis_out);
+/* numpy-quaternion's minimal_rotation: R' = R exp(gamma z / 2) with gamma-dot / 2 = Re[Rdot z R^-1], derivative and integral by
+ * not-a-knot cubic splines, `iterations` >= 1 times.  R_out may be R. */
+int bms_minimal_rotation(bms_ctx* ctx, const double* t, int64_t n_times, const double* R, int mem, int iterations, double* R_out);
+/* omega f8[n][3] = vector part of 2 Rdot R^-1, Rdot from the not-a-knot cubic spline through the components (quaternion.angular_velocity) */
+int bms_rotor_angular_velocity(bms_ctx* ctx, const double* t, int64_t n_times, const double* R, int mem, double* omega_out);
+/* In place on frame f8[n][4]: frame <- frame * right (right may be NULL), normalised; with truncate_tolerance > 0 then
+ * frame <- exp(round(log(frame) 2^k) / 2^k), k = -floor(log2(2 truncate_tolerance)) (scri/rotations.py:86-90), the rounded logarithm
+ * to log_out f8[n][4] (may be NULL).  spinors_out (may be NULL): c16[n][2] = (w + i z, y + i x), what bms_rotate_series takes.  All
+ * arrays in `mem`. */
+int bms_frame_adjust(bms_ctx* ctx, double* frame, int64_t n_times, int mem, const double right[4], double truncate_tolerance,
+                     double* log_out, void* spinors_out);
+/* corotating_frame (scri/mode_calculations.py:435-491) of modes data c16[n][ld] in `mem`: the kernels of bms_angular_velocity, the
+ * spline of omega, the interval rotors and their prefix product, without leaving the device.  The frame goes to frame_dev (DEVICE
+ * f8[n][4], whatever `mem` is), and to the host arrays frame_out f8[n][4] and omega_out f8[n][3] where those are not NULL. */
+int bms_corotating_frame(bms_ctx* ctx, const double* t, int64_t n_times, const void* data, int64_t ld, int ell_min, int ell_max, int mem,
+                         const double R0[4], double tolerance, double* frame_dev, double* frame_out, double* omega_out);
+/* The coprecessing frame (scri/rotations.py:14-49) of modes data c16[n][ld] in `mem`: <LL>, its dominant axis v (as
+ * bms_dominant_axis), the rotor sqrt(-v z) taking z to v and `iterations` >= 1 rounds of bms_minimal_rotation.  frame_dev (DEVICE
+ * f8[n][4]) and the host arrays frame_out f8[n][4], axis_out f8[n][3] may be NULL; with neither frame asked for only the axis is
+ * computed (LLDominantEigenvector), which needs no spline: then n >= 1 and t, iterations are not read. */
+int bms_coprecessing_frame(bms_ctx* ctx, const double* t, int64_t n_times, const void* data, int64_t ld, int ell_min, int ell_max, int mem,
+                           const double rough[3], int64_t rough_index, int iterations, double* frame_dev, double* frame_out,
+                           double* axis_out);
+
 /* ---- bit transforms of the storage formats (scri/utilities.py:194-406), bit-exact ------------ */
 /* xor_timeseries (reverse = 0) / xor_timeseries_reverse (reverse = 1), in place: data viewed as uint64[n_rows][words_per_row],
  * time along the rows; row 0 is unchanged, row i becomes row[i-1] ^ row[i] (forward) or the running XOR (reverse). */

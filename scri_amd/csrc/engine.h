@@ -7,6 +7,7 @@
 //   engine_modes.hip     WaveformModes transform: one call, shard, pipelined, series, grid                   (bms_transform_modes*, ...)
 //   engine_abd.hip       AsymptoticBondiData transform                                                       (bms_transform_abd*)
 //   engine_blocks.hip    building blocks, series and bit operators               (bms_rotor_grid ... bms_grid_multiply, bms_xor_timeseries ...)
+//   engine_frames.hip    corotating / coprecessing frames built on the device                                (bms_corotating_frame ..., bms_dominant_axis ...)
 #pragma once
 #include <algorithm>
 #include <array>

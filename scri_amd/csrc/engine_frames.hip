@@ -1,0 +1,305 @@
+// Frame construction: the corotating and the coprecessing frame of a waveform, built on the device from modes that are already there
+// (kernels_frames.hip; the spline solves are those of kernels_spline.hip / kernels_series.hip on series of one or two complex columns)
+// (engine.h: the split of the engine by entry family; include/scri_amd.h: the C ABI)
+#include "engine.h"
+
+namespace {
+
+struct FrameAxis {  // the time axis of one call on the device, with the tables of its not-a-knot spline
+  double* d_x = nullptr;
+  SplineTable* d_tab = nullptr;
+  int tile = SPLINE_TILE;
+};
+
+int check_time_axis(bms_ctx* c, const double* t, int64_t n) {
+  if (n < 4) return fail(c, BMS_ERR_UNSUPPORTED, "the splines of the frame need at least 4 time steps, got %lld", (long long)n);
+  for (int64_t i = 1; i < n; ++i)
+    if (!(t[i] > t[i - 1])) return fail(c, BMS_ERR_INVALID, "time array must be strictly increasing (index %lld)", (long long)i);
+  return BMS_OK;
+}
+
+int frame_axis(bms_ctx* c, const double* t, int64_t n, FrameAxis& ax) {
+  int rc = upload_times(c, t, n, 0, n, 0, n, &ax.d_x, &ax.d_tab);
+  ax.tile = spline_tile_for(t, n);
+  return rc;
+}
+
+// knot slopes d_S of the series d_y f8[n][2 n_cols] (n_cols complex columns): the forward pass goes through `fw`
+int knot_slopes(bms_ctx* c, const FrameAxis& ax, int64_t n, const double* d_y, int n_cols, const char* fw, double* d_S) {
+  double* d_F;
+  int rc = dev_buf_t(c, fw, (size_t)n * 2 * n_cols, &d_F);
+  if (rc) return rc;
+  TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(c->stream, d_y, d_F, 2 * n_cols, n_cols, 0, n, n, ax.d_x, ax.d_tab, ax.tile, SPLINE_HALO));
+  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_slopes(c->stream, d_F, d_S, 2 * n_cols, n_cols, n, ax.d_tab, ax.tile, SPLINE_HALO));
+  return BMS_OK;
+}
+
+// d_R f8[n][4] from d_om f8[n][3] (both on the device): slopes of omega, interval rotors, prefix product, R0 and normalisation
+int frame_from_omega(bms_ctx* c, const FrameAxis& ax, int64_t n, const double* d_om, const double R0[4], double tolerance, double* d_R) {
+  if (!(tolerance > 0)) tolerance = 1e-12;
+  const double amax = std::min(0.2, std::max(1e-3, 2.0 * std::pow(tolerance, 0.2)));  // as bms_integrate_angular_velocity
+  int rc;
+  double *d_w4, *d_s4, *d_Q, *d_tot;
+  if ((rc = dev_buf_t(c, "fr_w4", (size_t)n * 4, &d_w4))) return rc;
+  if ((rc = dev_buf_t(c, "fr_s4", (size_t)n * 4, &d_s4))) return rc;
+  if ((rc = dev_buf_t(c, "fr_Q", (size_t)n * 4, &d_Q))) return rc;
+  if ((rc = dev_buf_t(c, "fr_totals", (size_t)frame_scan_blocks(n) * 4, &d_tot))) return rc;
+  hipStream_t S = c->stream;
+  TIMED(c, BMS_TAG_POINTWISE, launch_pad_omega(S, d_om, d_w4, n));
+  if ((rc = knot_slopes(c, ax, n, d_w4, 2, "fr_fw", d_s4))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_interval_rotors(S, d_w4, d_s4, ax.d_x, n, amax, d_Q));
+  TIMED(c, BMS_TAG_POINTWISE, launch_scan_quat(S, d_Q, n, d_tot));
+  Vec4 r0 = {{R0[0], R0[1], R0[2], R0[3]}};
+  TIMED(c, BMS_TAG_POINTWISE, launch_frame_finish(S, d_Q, n, r0, d_R));
+  return BMS_OK;
+}
+
+// d_axis f8[n][3] from d_ll f8[n][9] (device): Jacobi per step, the two scans of sign maps out of the anchor, normalisation
+int dominant_axis(bms_ctx* c, int64_t n, const double* d_ll, const double rough[3], int64_t anchor, double* d_axis) {
+  int rc;
+  double* d_raw;
+  unsigned *d_fwd, *d_bwd, *d_tot;
+  if ((rc = dev_buf_t(c, "fr_axis_raw", (size_t)n * 3, &d_raw))) return rc;
+  if ((rc = dev_buf_t(c, "fr_sign_fwd", (size_t)n, &d_fwd))) return rc;
+  if ((rc = dev_buf_t(c, "fr_sign_bwd", (size_t)n, &d_bwd))) return rc;
+  if ((rc = dev_buf_t(c, "fr_sign_totals", (size_t)frame_scan_blocks(n), &d_tot))) return rc;
+  hipStream_t S = c->stream;
+  Vec4 rg = {{rough[0], rough[1], rough[2], 0.0}};
+  TIMED(c, BMS_TAG_POINTWISE, launch_dominant_axis(S, d_ll, n, d_raw));
+  TIMED(c, BMS_TAG_POINTWISE, launch_axis_sign_maps(S, d_raw, n, anchor, rg, d_fwd, d_bwd));
+  TIMED(c, BMS_TAG_POINTWISE, launch_scan_sign_maps(S, d_fwd, n - anchor, d_tot));
+  TIMED(c, BMS_TAG_POINTWISE, launch_scan_sign_maps(S, d_bwd, anchor + 1, d_tot));
+  TIMED(c, BMS_TAG_POINTWISE, launch_axis_apply_signs(S, d_raw, n, anchor, d_fwd, d_bwd, d_axis));
+  return BMS_OK;
+}
+
+// in place on d_R f8[n][4] (device)
+int minimal_rotation(bms_ctx* c, const FrameAxis& ax, int64_t n, double* d_R, int iterations) {
+  int rc;
+  double *d_Rdot, *d_h, *d_hs, *d_P1, *d_carry;
+  if ((rc = dev_buf_t(c, "fr_Rdot", (size_t)n * 4, &d_Rdot))) return rc;
+  if ((rc = dev_buf_t(c, "fr_h", (size_t)n * 2, &d_h))) return rc;
+  if ((rc = dev_buf_t(c, "fr_hs", (size_t)n * 2, &d_hs))) return rc;
+  if ((rc = dev_buf_t(c, "fr_P1", (size_t)n * 2, &d_P1))) return rc;
+  if ((rc = dev_buf_t(c, "fr_carry", (size_t)spline_prefix_carry_size(n, 1), &d_carry))) return rc;
+  hipStream_t S = c->stream;
+  for (int it = 0; it < iterations; ++it) {
+    if ((rc = knot_slopes(c, ax, n, d_R, 2, "fr_fw", d_Rdot))) return rc;
+    TIMED(c, BMS_TAG_POINTWISE, launch_halfgammadot(S, d_R, d_Rdot, n, d_h));
+    if ((rc = knot_slopes(c, ax, n, d_h, 1, "fr_fw", d_hs))) return rc;
+    TIMED(c, BMS_TAG_POINTWISE, launch_spline_prefix(S, d_h, d_hs, 2, 1, n, ax.d_x, d_P1, nullptr, d_carry, 1));
+    TIMED(c, BMS_TAG_POINTWISE, launch_spin_about_z(S, d_R, d_P1, n, d_R));
+  }
+  return BMS_OK;
+}
+
+int rotor_omega(bms_ctx* c, const FrameAxis& ax, int64_t n, const double* d_R, double* d_om) {
+  int rc;
+  double* d_Rdot;
+  if ((rc = dev_buf_t(c, "fr_Rdot", (size_t)n * 4, &d_Rdot))) return rc;
+  if ((rc = knot_slopes(c, ax, n, d_R, 2, "fr_fw", d_Rdot))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_rotor_omega(c->stream, d_R, d_Rdot, n, d_om));
+  return BMS_OK;
+}
+
+// a per-step input array of `mem` on the device, and the device array an output of `mem` is computed into
+int in_array(bms_ctx* c, const char* name, const double* src, int mem, size_t count, const double** dev) {
+  return stage_in(c, name, src, mem, 8 * count, dev);
+}
+int out_array(bms_ctx* c, const char* name, double* dst, int mem, size_t count, double** dev) {
+  if (mem == BMS_DEVICE) {
+    *dev = dst;
+    return BMS_OK;
+  }
+  return dev_buf_t(c, name, count, dev);
+}
+
+int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, int* n_modes) {
+  if (ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bad ell range");
+  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
+  *n_modes = LM_total_size(ell_min, ell_max);
+  if (ld < *n_modes) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
+  return BMS_OK;
+}
+
+}  // namespace
+
+extern "C" int bms_frame_from_angular_velocity(bms_ctx* c, const double* t, int64_t n, const double* omega, int mem, const double R0[4],
+                                               double tolerance, double* R_out) try {
+  if (!c || !t || !omega || !R0 || !R_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = check_time_axis(c, t, n))) return rc;
+  FrameAxis ax;
+  if ((rc = frame_axis(c, t, n, ax))) return rc;
+  const double* d_om;
+  double* d_R;
+  if ((rc = in_array(c, "fr_in", omega, mem, (size_t)n * 3, &d_om))) return rc;
+  if ((rc = out_array(c, "fr_out", R_out, mem, (size_t)n * 4, &d_R))) return rc;
+  if ((rc = frame_from_omega(c, ax, n, d_om, R0, tolerance, d_R))) return rc;
+  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(R_out, d_R, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_dominant_axis(bms_ctx* c, const double* ll, int64_t n, int mem, const double rough[3], int64_t rough_index,
+                                 double* axis_out) try {
+  if (!c || !ll || !rough || !axis_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n < 1) return fail(c, BMS_ERR_INVALID, "need at least one time step, got %lld", (long long)n);
+  if (rough_index < 0 || rough_index >= n) return fail(c, BMS_ERR_INVALID, "rough_index %lld outside [0, %lld)", (long long)rough_index, (long long)n);
+  int rc;
+  const double* d_ll;
+  double* d_axis;
+  if ((rc = in_array(c, "fr_in", ll, mem, (size_t)n * 9, &d_ll))) return rc;
+  if ((rc = out_array(c, "fr_out", axis_out, mem, (size_t)n * 3, &d_axis))) return rc;
+  if ((rc = dominant_axis(c, n, d_ll, rough, rough_index, d_axis))) return rc;
+  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(axis_out, d_axis, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_minimal_rotation(bms_ctx* c, const double* t, int64_t n, const double* R, int mem, int iterations, double* R_out) try {
+  if (!c || !t || !R || !R_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (iterations < 1) return fail(c, BMS_ERR_INVALID, "iterations must be positive, got %d", iterations);
+  int rc;
+  if ((rc = check_time_axis(c, t, n))) return rc;
+  FrameAxis ax;
+  if ((rc = frame_axis(c, t, n, ax))) return rc;
+  double* d_R;
+  if ((rc = out_array(c, "fr_out", R_out, mem, (size_t)n * 4, &d_R))) return rc;
+  if (mem == BMS_HOST)
+    HIP_TRY(c, hipMemcpyAsync(d_R, R, sizeof(double) * 4 * n, hipMemcpyHostToDevice, c->stream));
+  else if (R != R_out)
+    HIP_TRY(c, hipMemcpyAsync(d_R, R, sizeof(double) * 4 * n, hipMemcpyDeviceToDevice, c->stream));
+  if ((rc = minimal_rotation(c, ax, n, d_R, iterations))) return rc;
+  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(R_out, d_R, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_rotor_angular_velocity(bms_ctx* c, const double* t, int64_t n, const double* R, int mem, double* omega_out) try {
+  if (!c || !t || !R || !omega_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = check_time_axis(c, t, n))) return rc;
+  FrameAxis ax;
+  if ((rc = frame_axis(c, t, n, ax))) return rc;
+  const double* d_R;
+  double* d_om;
+  if ((rc = in_array(c, "fr_in", R, mem, (size_t)n * 4, &d_R))) return rc;
+  if ((rc = out_array(c, "fr_out", omega_out, mem, (size_t)n * 3, &d_om))) return rc;
+  if ((rc = rotor_omega(c, ax, n, d_R, d_om))) return rc;
+  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(omega_out, d_om, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_frame_adjust(bms_ctx* c, double* frame, int64_t n, int mem, const double right[4], double truncate_tolerance,
+                                double* log_out, void* spinors_out) try {
+  if (!c || !frame) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n < 0) return fail(c, BMS_ERR_INVALID, "negative size");
+  if (n == 0) return BMS_OK;
+  double pow2 = 0.0;
+  if (truncate_tolerance > 0) {
+    if (!std::isfinite(truncate_tolerance)) return fail(c, BMS_ERR_INVALID, "truncate_tolerance must be finite");
+    pow2 = std::exp2(-std::floor(std::log2(2 * truncate_tolerance)));
+  }
+  int rc;
+  double *d_frame = frame, *d_log = log_out, *d_sp = (double*)spinors_out;
+  if (mem == BMS_HOST) {
+    void* vp;
+    if ((rc = upload(c, "fr_in", frame, sizeof(double) * 4 * n, &vp))) return rc;
+    d_frame = (double*)vp;
+    if (log_out && (rc = dev_buf_t(c, "fr_out", (size_t)n * 4, &d_log))) return rc;
+    if (spinors_out && (rc = dev_buf_t(c, "fr_spinors", (size_t)n * 4, &d_sp))) return rc;
+  }
+  Vec4 rt = {{1.0, 0.0, 0.0, 0.0}};
+  if (right)
+    for (int i = 0; i < 4; ++i) rt.v[i] = right[i];
+  hipStream_t S = c->stream;
+  TIMED(c, BMS_TAG_POINTWISE, launch_frame_adjust(S, d_frame, n, rt, right != nullptr, pow2, d_log, d_sp));
+  if (mem == BMS_HOST) {
+    HIP_TRY(c, hipMemcpyAsync(frame, d_frame, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
+    if (log_out) HIP_TRY(c, hipMemcpyAsync(log_out, d_log, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
+    if (spinors_out) HIP_TRY(c, hipMemcpyAsync(spinors_out, d_sp, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
+  }
+  HIP_TRY(c, hipStreamSynchronize(S));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_corotating_frame(bms_ctx* c, const double* t, int64_t n, const void* data, int64_t ld, int ell_min, int ell_max, int mem,
+                                    const double R0[4], double tolerance, double* frame_dev, double* frame_out, double* omega_out) try {
+  if (!c || !t || !data || !R0 || !frame_dev) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc, n_modes;
+  if ((rc = check_time_axis(c, t, n))) return rc;
+  if ((rc = modes_checks(c, ell_min, ell_max, ld, &n_modes))) return rc;
+  FrameAxis ax;
+  if ((rc = frame_axis(c, t, n, ax))) return rc;
+  // the kernels of bms_angular_velocity, in its work space
+  const double* d_y;
+  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n - 1) * ld + n_modes) * 16, &d_y))) return rc;
+  double *d_R, *d_S, *d_res;
+  if ((rc = dev_buf_t(c, "R", (size_t)n * ld * 2, &d_R))) return rc;
+  if ((rc = dev_buf_t(c, "S", (size_t)n * ld * 2, &d_S))) return rc;
+  if ((rc = dev_buf_t(c, "av_out", (size_t)n * 15, &d_res))) return rc;
+  hipStream_t S = c->stream;
+  TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_y, d_R, 2 * ld, n_modes, 0, n, n, ax.d_x, ax.d_tab, ax.tile, SPLINE_HALO));
+  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_slopes(S, d_R, d_S, 2 * ld, n_modes, n, ax.d_tab, ax.tile, SPLINE_HALO));
+  double *d_ldt = d_res, *d_ll = d_res + 3 * n, *d_om = d_res + 12 * n;
+  TIMED(c, BMS_TAG_POINTWISE, launch_angular_velocity(S, d_y, d_S, 2 * ld, n, ell_min, n_modes, d_ldt, d_ll, d_om));
+  if ((rc = frame_from_omega(c, ax, n, d_om, R0, tolerance, frame_dev))) return rc;
+  if (frame_out) HIP_TRY(c, hipMemcpyAsync(frame_out, frame_dev, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
+  if (omega_out) HIP_TRY(c, hipMemcpyAsync(omega_out, d_om, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, S));
+  HIP_TRY(c, hipStreamSynchronize(S));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_coprecessing_frame(bms_ctx* c, const double* t, int64_t n, const void* data, int64_t ld, int ell_min, int ell_max,
+                                      int mem, const double rough[3], int64_t rough_index, int iterations, double* frame_dev,
+                                      double* frame_out, double* axis_out) try {
+  if (!c || !data || !rough) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const bool want_frame = frame_dev || frame_out;
+  int rc, n_modes;
+  if (want_frame) {
+    if (!t) return fail(c, BMS_ERR_INVALID, "NULL argument");
+    if (iterations < 1) return fail(c, BMS_ERR_INVALID, "iterations must be positive, got %d", iterations);
+    if ((rc = check_time_axis(c, t, n))) return rc;
+  } else if (n < 1) {
+    return fail(c, BMS_ERR_INVALID, "need at least one time step, got %lld", (long long)n);
+  }
+  if (rough_index < 0 || rough_index >= n) return fail(c, BMS_ERR_INVALID, "rough_index %lld outside [0, %lld)", (long long)rough_index, (long long)n);
+  if ((rc = modes_checks(c, ell_min, ell_max, ld, &n_modes))) return rc;
+  const double* d_y;
+  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n - 1) * ld + n_modes) * 16, &d_y))) return rc;
+  double *d_ll, *d_axis;
+  if ((rc = dev_buf_t(c, "av_out", (size_t)n * 15, &d_ll))) return rc;
+  if ((rc = dev_buf_t(c, "fr_axis", (size_t)n * 3, &d_axis))) return rc;
+  hipStream_t S = c->stream;
+  // <LL> alone needs no time derivative: the kernel reads the modes in its place, and nothing of <Ldt> or omega is written
+  TIMED(c, BMS_TAG_POINTWISE, launch_angular_velocity(S, d_y, d_y, 2 * ld, n, ell_min, n_modes, nullptr, d_ll, nullptr));
+  if ((rc = dominant_axis(c, n, d_ll, rough, rough_index, d_axis))) return rc;
+  if (axis_out) HIP_TRY(c, hipMemcpyAsync(axis_out, d_axis, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, S));
+  if (want_frame) {
+    FrameAxis ax;
+    if ((rc = frame_axis(c, t, n, ax))) return rc;
+    double* d_R = frame_dev;
+    if (!d_R && (rc = dev_buf_t(c, "fr_out", (size_t)n * 4, &d_R))) return rc;
+    TIMED(c, BMS_TAG_POINTWISE, launch_axis_rotor(S, d_axis, n, d_R));
+    if ((rc = minimal_rotation(c, ax, n, d_R, iterations))) return rc;
+    if (frame_out) HIP_TRY(c, hipMemcpyAsync(frame_out, d_R, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
+  }
+  HIP_TRY(c, hipStreamSynchronize(S));
+  return BMS_OK;
+} BMS_CATCH(c)

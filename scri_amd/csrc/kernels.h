@@ -322,6 +322,44 @@ hipError_t launch_cmul(hipStream_t stream, const double* a, const double* b, dou
 hipError_t launch_angular_velocity(hipStream_t stream, const double* F, const double* Fdot, long long ld, long long n_times,
                                    int ell_min, int n_modes, double* ldt_out, double* ll_out, double* omega_out);
 
+// ---- frame construction (kernels_frames.hip): rotors f8[n][4] = (w, x, y, z)
+struct Vec4 {
+  double v[4];
+};
+// time-parallel inclusive scans in place (wave shuffles, LDS, a second pass over the block totals; totals: frame_scan_blocks(n) elements)
+long long frame_scan_blocks(long long n);
+// ordered quaternion product: q[j] <- q[j] q[j-1] ... q[0] (later elements multiply on the left)
+hipError_t launch_scan_quat(hipStream_t stream, double* q, long long n, double* totals);
+// composition of maps {+1, -1} -> {+1, -1} stored as 2 bits: m[j] <- m[j] o m[j-1] o ... o m[0]
+hipError_t launch_scan_sign_maps(hipStream_t stream, unsigned* m, long long n, unsigned* totals);
+// om3 f8[n][3] -> w4 f8[n][4] = (x, y, z, 0): two complex columns for the spline kernels
+hipError_t launch_pad_omega(hipStream_t stream, const double* om3, double* w4, long long n);
+// Q[0] = 1, Q[j + 1] = E_j: the rotor of sampling interval j from omega (w4) and its spline slopes (s4) at the knots
+hipError_t launch_interval_rotors(hipStream_t stream, const double* w4, const double* s4, const double* x, long long n, double amax,
+                                  double* Q);
+// out[j] = P[j] R0 normalised (out[0] = R0 as given); out may be P
+hipError_t launch_frame_finish(hipStream_t stream, const double* P, long long n, Vec4 R0, double* out);
+// raw unit eigenvector of the largest eigenvalue of ll f8[n][9]
+hipError_t launch_dominant_axis(hipStream_t stream, const double* ll, long long n, double* axis);
+// the sign maps of the continuity rule in scan order: fwd[k] for step anchor + k (n - anchor maps), bwd[k] for step anchor - k
+// (anchor + 1 maps); element 0 of both is the constant map to the anchor's sign
+hipError_t launch_axis_sign_maps(hipStream_t stream, const double* axis, long long n, long long anchor, Vec4 rough, unsigned* fwd,
+                                 unsigned* bwd);
+hipError_t launch_axis_apply_signs(hipStream_t stream, const double* axis, long long n, long long anchor, const unsigned* fwd,
+                                   const unsigned* bwd, double* out);
+// R = sqrt(-v z): the rotor taking z to the unit vector v (-1 -> rotation about x, as quaternions.sqrt)
+hipError_t launch_axis_rotor(hipStream_t stream, const double* axis, long long n, double* R);
+// h[j] = ((Rdot z R^-1).w, 0): one complex column
+hipError_t launch_halfgammadot(hipStream_t stream, const double* R, const double* Rdot, long long n, double* h);
+// out = R (cos g + z sin g), g = halfgamma[j][0] (one complex column); out may be R
+hipError_t launch_spin_about_z(hipStream_t stream, const double* R, const double* halfgamma, long long n, double* out);
+// om3 = vector part of 2 Rdot R^-1
+hipError_t launch_rotor_omega(hipStream_t stream, const double* R, const double* Rdot, long long n, double* om3);
+// frame <- normalised frame * right (with_right), then exp(round(log frame * pow2) / pow2) (pow2 > 0), rounded log to log_out,
+// (w + i z, y + i x) to spinors; log_out, spinors may be null
+hipError_t launch_frame_adjust(hipStream_t stream, double* frame, long long n, Vec4 right, int with_right, double pow2, double* log_out,
+                               double* spinors);
+
 // ---- bit transforms of the storage formats (kernels_bits.hip; scri/utilities.py:194-406)
 // rows of n_cols 64-bit words; forward: out[i] = in[i-1] ^ in[i]; reverse: running XOR (carry: xor_carry_words words)
 long long xor_carry_words(long long n_rows, long long n_cols);

@@ -47,6 +47,12 @@ def empty(ctx, shape):
     return torch.empty(tuple(int(x) for x in shape), dtype=torch.complex128, device=attach(ctx))
 
 
+def empty_real(ctx, shape):
+    """float64 work array on the device (per-step frame quantities: rotors [n, 4], vectors [n, 3])"""
+    torch = _torch()
+    return torch.empty(tuple(int(x) for x in shape), dtype=torch.float64, device=attach(ctx))
+
+
 def to_device(ctx, array):
     """numpy (complex) array -> device tensor"""
     torch = _torch()

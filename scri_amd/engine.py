@@ -837,22 +837,183 @@ def row_norm(data, take_sqrt=False, ctx=None, device_tensor=None):
     return out
 
 
+def _modes_arg(data, n, ell_min, ell_max):
+    """(address, row stride, memory kind, object to keep alive) of modes [n, n_modes]: a numpy array on the host, or a torch tensor
+    (complex128, unit column stride) for modes resident on the GPU"""
+    n_modes = LM_total_size(ell_min, ell_max)
+    if hasattr(data, "data_ptr"):
+        if tuple(data.shape) != (n, n_modes) or (n_modes > 1 and data.stride(1) != 1):
+            raise ValueError(f"device modes of shape {tuple(data.shape)} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
+        return c_vp(data.data_ptr()), (data.stride(0) if n > 1 else n_modes), BMS_DEVICE, data
+    data = _lib.as_c16(data)
+    if data.shape != (n, n_modes):
+        raise ValueError(f"data shape {data.shape} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
+    return vptr(data), data.shape[1], BMS_HOST, data
+
+
 def angular_velocity(t, data, ell_min, ell_max, ctx=None, parts=False):
-    """omega[N, 3] = -<LL>^-1 <Ldt> of modes data[N, n_modes]; parts=True returns (<Ldt>[N, 3], <LL>[N, 3, 3], omega)."""
+    """omega[N, 3] = -<LL>^-1 <Ldt> of modes data[N, n_modes] (numpy, or a device tensor: the modes then stay where they are);
+    parts=True returns (<Ldt>[N, 3], <LL>[N, 3, 3], omega).  The results are host arrays."""
     ctx = _ctx(ctx)
     t = np.ascontiguousarray(t, dtype=float)
-    data = _lib.as_c16(data)
     n = t.shape[0]
-    if data.shape != (n, LM_total_size(ell_min, ell_max)):
-        raise ValueError(f"data shape {data.shape} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
+    ptr, ld, mem, _keep = _modes_arg(data, n, ell_min, ell_max)
     ldt = np.empty((n, 3))
     ll = np.empty((n, 3, 3))
     om = np.empty((n, 3))
-    rc = _lib.load().bms_angular_velocity(
-        ctx.handle, dptr(t), n, vptr(data), data.shape[1], int(ell_min), int(ell_max), BMS_HOST, dptr(ldt), dptr(ll), dptr(om)
-    )
+    rc = _lib.load().bms_angular_velocity(ctx.handle, dptr(t), n, ptr, ld, int(ell_min), int(ell_max), mem, dptr(ldt), dptr(ll), dptr(om))
     ctx.check(rc, "bms_angular_velocity")
     return (ldt, ll, om) if parts else om
+
+
+# ---- the frame chain on the device (bms_frame_from_angular_velocity ... bms_coprecessing_frame).  Per-step arrays are numpy arrays on
+# the host or torch tensors (float64, contiguous) on the device; a result lives where its input does.
+
+
+def _step_arg(x, n, width, what):
+    """(address, memory kind, the array) of a per-step array f8[n][width]"""
+    if hasattr(x, "data_ptr"):
+        import torch
+
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != n * width:
+            raise ValueError(f"{what}: expected a contiguous float64 device array of {n} x {width} values, got {x.dtype} of shape "
+                             f"{tuple(x.shape)} on {x.device}")
+        return c_vp(x.data_ptr()), BMS_DEVICE, x
+    a = np.ascontiguousarray(x, dtype=float)
+    if a.shape != (n, width):
+        raise ValueError(f"{what} must have shape ({n}, {width}); it has shape {a.shape}")
+    return vptr(a), BMS_HOST, a
+
+
+def _step_out(like, n, width, out=None):
+    """the result array f8[n][width] beside `like` (a device tensor or a numpy array)"""
+    if hasattr(like, "data_ptr"):
+        import torch
+
+        if out is None:
+            out = torch.empty((n, width), dtype=torch.float64, device=like.device)
+        elif out.dtype != torch.float64 or out.device != like.device or not out.is_contiguous() or out.numel() != n * width:
+            raise ValueError(f"out: expected a contiguous float64 array of {n} x {width} values on {like.device}")
+        return c_vp(out.data_ptr()), out
+    if out is not None:
+        raise ValueError("out= names a device array; with a host input the result is a new host array")
+    out = np.empty((n, width))
+    return vptr(out), out
+
+
+def _on_device_of(ctx, *arrays):
+    for x in arrays:
+        if hasattr(x, "data_ptr") and x.device.index != ctx.device:
+            raise ValueError(f"a device array on {x.device} was passed to a context on device {ctx.device}")
+
+
+def frame_from_angular_velocity(t, omega, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12, ctx=None, out=None):
+    """R[N, 4] with R[0] = R0 and dR/dt = (1/2) Omega R for the cubic spline Omega through omega[N, 3], on the GPU: interval rotors
+    and their prefix product.  `out` (device input only): the device tensor [N, 4] the frame is written to."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, omega, out)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    om_ptr, mem, om = _step_arg(omega, n, 3, "omega")
+    R0 = np.ascontiguousarray(R0, dtype=float).reshape(4)
+    out_ptr, out = _step_out(om, n, 4, out)
+    rc = _lib.load().bms_frame_from_angular_velocity(ctx.handle, dptr(t), n, om_ptr, mem, dptr(R0), float(tolerance), out_ptr)
+    ctx.check(rc, "bms_frame_from_angular_velocity")
+    return out
+
+
+def dominant_axis(ll, rough=(0.0, 0.0, 1.0), rough_index=0, ctx=None):
+    """Continuous unit principal axis [N, 3] of the symmetric matrices ll[N, 3, 3] (bms_dominant_axis)."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, ll)
+    n = int(ll.shape[0])
+    ll_ptr, mem, ll = _step_arg(ll.reshape(n, 9), n, 9, "ll")
+    rough = np.ascontiguousarray(rough, dtype=float).reshape(3)
+    out_ptr, out = _step_out(ll, n, 3)
+    rc = _lib.load().bms_dominant_axis(ctx.handle, ll_ptr, n, mem, dptr(rough), int(rough_index), out_ptr)
+    ctx.check(rc, "bms_dominant_axis")
+    return out
+
+
+def minimal_rotation(t, R, iterations=2, ctx=None):
+    """numpy-quaternion's minimal_rotation of the rotor series R[N, 4] (bms_minimal_rotation); a new array beside R."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, R)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    R_ptr, mem, R = _step_arg(R, n, 4, "R")
+    out_ptr, out = _step_out(R, n, 4)
+    rc = _lib.load().bms_minimal_rotation(ctx.handle, dptr(t), n, R_ptr, mem, int(iterations), out_ptr)
+    ctx.check(rc, "bms_minimal_rotation")
+    return out
+
+
+def rotor_angular_velocity(t, R, ctx=None):
+    """omega[N, 3] = vector part of 2 Rdot R^-1 of the rotor series R[N, 4] (bms_rotor_angular_velocity)."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, R)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    R_ptr, mem, R = _step_arg(R, n, 4, "R")
+    out_ptr, out = _step_out(R, n, 3)
+    rc = _lib.load().bms_rotor_angular_velocity(ctx.handle, dptr(t), n, R_ptr, mem, out_ptr)
+    ctx.check(rc, "bms_rotor_angular_velocity")
+    return out
+
+
+def frame_adjust(frame, right=None, truncate_tolerance=0.0, want_log=False, want_spinors=False, ctx=None):
+    """In place on frame[N, 4] (bms_frame_adjust): times the constant rotor `right`, normalised, optionally exp of its logarithm rounded
+    to the bits above truncate_tolerance.  Returns (rounded log-frame or None, spinors [N, 4 doubles] = (w + i z, y + i x) or None),
+    beside the frame."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, frame)
+    n = int(frame.shape[0])
+    if not hasattr(frame, "data_ptr") and not (isinstance(frame, np.ndarray) and frame.dtype == float and frame.flags.c_contiguous):
+        raise ValueError("frame_adjust works in place: a contiguous float array or a device tensor")
+    f_ptr, mem, frame = _step_arg(frame, n, 4, "frame")
+    log_ptr, log = _step_out(frame, n, 4) if want_log else (None, None)
+    sp_ptr, sp = _step_out(frame, n, 4) if want_spinors else (None, None)
+    rt = None if right is None else np.ascontiguousarray(right, dtype=float).reshape(4)
+    rc = _lib.load().bms_frame_adjust(ctx.handle, f_ptr, n, mem, None if rt is None else dptr(rt), float(truncate_tolerance), log_ptr, sp_ptr)
+    ctx.check(rc, "bms_frame_adjust")
+    return log, sp
+
+
+def corotating_frame(t, data, ell_min, ell_max, frame_dev, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12, want_frame=False, want_omega=False, ctx=None):
+    """bms_corotating_frame: the corotating frame of modes data[N, n_modes] (numpy or device tensor) into the device tensor frame_dev
+    [N, 4]; returns (host copy of the frame or None, host omega [N, 3] or None)."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, data, frame_dev)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    ptr, ld, mem, _keep = _modes_arg(data, n, ell_min, ell_max)
+    f_ptr, _, _ = _step_arg(frame_dev, n, 4, "frame_dev")
+    R0 = np.ascontiguousarray(R0, dtype=float).reshape(4)
+    frame = np.empty((n, 4)) if want_frame else None
+    om = np.empty((n, 3)) if want_omega else None
+    rc = _lib.load().bms_corotating_frame(ctx.handle, dptr(t), n, ptr, ld, int(ell_min), int(ell_max), mem, dptr(R0), float(tolerance), f_ptr,
+                                          None if frame is None else dptr(frame), None if om is None else dptr(om))
+    ctx.check(rc, "bms_corotating_frame")
+    return frame, om
+
+
+def coprecessing_frame(t, data, ell_min, ell_max, rough=(0.0, 0.0, 1.0), rough_index=0, iterations=3, frame_dev=None, want_frame=False,
+                       want_axis=False, ctx=None):
+    """bms_coprecessing_frame: dominant axis of <LL> of modes data[N, n_modes] (numpy or device tensor), and with frame_dev (device
+    tensor [N, 4]) or want_frame the minimally rotating frame that takes z to it; returns (host frame or None, host axis [N, 3] or None)."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, data, frame_dev)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    ptr, ld, mem, _keep = _modes_arg(data, n, ell_min, ell_max)
+    f_ptr = None if frame_dev is None else _step_arg(frame_dev, n, 4, "frame_dev")[0]
+    rough = np.ascontiguousarray(rough, dtype=float).reshape(3)
+    frame = np.empty((n, 4)) if want_frame else None
+    axis = np.empty((n, 3)) if want_axis else None
+    rc = _lib.load().bms_coprecessing_frame(ctx.handle, dptr(t), n, ptr, ld, int(ell_min), int(ell_max), mem, dptr(rough), int(rough_index),
+                                            int(iterations), f_ptr, None if frame is None else dptr(frame), None if axis is None else dptr(axis))
+    ctx.check(rc, "bms_coprecessing_frame")
+    return frame, axis
 
 
 def integrate_angular_velocity(t, omega, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12):

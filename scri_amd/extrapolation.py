@@ -176,7 +176,6 @@ def extrapolate_waveforms(Ws, Radii, ExtrapolationOrders=[-1, 2, 3, 4, 5, 6], Ou
     if lo < -len(Ws):
         raise ValueError("Not enough data sets ({}) for min extrapolation order (N={}).".format(len(Ws), lo))
     by_radius = np.argsort([np.mean(np.asarray(r, dtype=float)) for r in Radii], kind="stable")
-    resident = all(_resident(W) for W in Ws)
     common, radii = list(Ws), list(Radii)
     set_common_time(common, radii, MinTimeStep, EarliestTime, LatestTime)
     frame_source = common[by_radius[-1]]
@@ -186,15 +185,10 @@ def extrapolate_waveforms(Ws, Radii, ExtrapolationOrders=[-1, 2, 3, 4, 5, 6], Ou
     for k in by_radius[:-1]:
         common[k].rotate_decomposition_basis(frame_source.frame)
         common[k].frameType = Corotating
-    if resident:  # (the frame of the outermost waveform is computed from its modes on the host)
-        for W in common:
-            W.to_device()
     results = _Extrapolate(common, radii, ExtrapolationOrders, [], None)
     for W in results:
         if OutputFrame in (Inertial, Corotating):
             W.to_inertial_frame()
             if OutputFrame == Corotating:
                 W.to_corotating_frame()
-        if resident:
-            W.to_device()
     return results

@@ -2,21 +2,34 @@
 :298-313 LLMatrix, :403-432 angular_velocity), SURVEY 8(f) rank 3.  One GPU pass (bms_angular_velocity): the cubic-spline
 time derivative of the modes, the <Ldt> and <LL> sums over modes per time step, and the 3 x 3 solve.
 
-corotating_frame (:435-491) integrates that angular velocity with the library's host integrator
-(bms_integrate_angular_velocity: the frame is four numbers marching in time).
+corotating_frame (:435-491) integrates that angular velocity on the device (bms_corotating_frame: the rotors of the sampling
+intervals are independent, the frame is their prefix product).
 
-LLDominantEigenvector (:316-399) takes the <LL> matrices from the GPU and finishes on the host (3 x 3 symmetric
-eigenproblems and the sequential sign choice that makes the axis continuous).
+LLDominantEigenvector (:316-399) is bms_coprecessing_frame without the frame: a Jacobi eigensolve per time step and the sign
+choice that makes the axis continuous as a scan of sign maps.
 
-Not provided: the frame-velocity term (needs numpy-quaternion's `derivative`).
+The modes of a device-resident waveform are read where they are: only per-step quantities (vectors, 3 x 3 matrices, rotors) come
+to the host.
 """
 import numpy as np
 
 from . import engine, quaternions
 
 
+def _modes(W):
+    """the modes as the engine takes them: the device tensor of a resident waveform, else the host array"""
+    return W._dev if getattr(W, "is_device_resident", False) else W.data
+
+
+def _context(W):
+    from . import _lib
+
+    ctx = getattr(W, "_ctx", None)
+    return ctx if ctx is not None else _lib.default_context()
+
+
 def _parts(W):
-    return engine.angular_velocity(W.t, W.data, W.ell_min, W.ell_max, ctx=getattr(W, "_ctx", None), parts=True)
+    return engine.angular_velocity(W.t, _modes(W), W.ell_min, W.ell_max, ctx=getattr(W, "_ctx", None), parts=True)
 
 
 def LdtVector(W):
@@ -29,7 +42,12 @@ def LLMatrix(W):
     n = W.n_times
     if 0 < n < 4:
         # the kernel also forms <Ldt>, whose spline needs four samples; <LL> needs none: pad the series with copies of its last row
-        data = np.concatenate([W.data, np.repeat(W.data[-1:], 4 - n, axis=0)], axis=0)
+        if getattr(W, "is_device_resident", False):
+            from . import device_series
+
+            data = device_series._torch().cat([W._dev, W._dev[-1:].expand(4 - n, -1)], dim=0).contiguous()
+        else:
+            data = np.concatenate([W.data, np.repeat(W.data[-1:], 4 - n, axis=0)], axis=0)
         return engine.angular_velocity(np.arange(4.0), data, W.ell_min, W.ell_max, ctx=getattr(W, "_ctx", None), parts=True)[1][:n]
     return _parts(W)[1]
 
@@ -39,34 +57,27 @@ def angular_velocity(W, include_frame_velocity=False):
     omega = _parts(W)[2]
     if include_frame_velocity and len(W.frame) == W.n_times:
         # + 2 Rdot R^-1 of the frame, its derivative from a cubic spline (scri/mode_calculations.py:426-430)
-        from . import quaternions
-
-        omega = omega + quaternions.angular_velocity(W.frame, W.t)
+        omega = omega + engine.rotor_angular_velocity(W.t, W.frame, ctx=getattr(W, "_ctx", None))
     return omega
 
 
-def _make_continuous(dpa, rough, i_index):
-    """Sign choice of scri/mode_calculations.py:316-363: the axis at i_index points along `rough` rather than against
-    it, and going outwards from there a vector is flipped when it is further from its (already fixed) neighbour than its
-    own length; every vector is normalised."""
-    dpa = np.array(dpa, dtype=float)
-    if np.dot(rough, dpa[i_index]) < 0.0:
-        dpa[i_index] *= -1
-    for rng, d in ((range(i_index - 1, -1, -1), -1), (range(i_index + 1, dpa.shape[0]), 1)):
-        for i in rng:
-            diff = dpa[i] - dpa[i - d]
-            if diff @ diff > dpa[i] @ dpa[i]:
-                dpa[i] *= -1
-    norms = np.linalg.norm(dpa, axis=1)
-    ok = norms != 0.0
-    dpa[ok] /= norms[ok, np.newaxis]
-    return dpa
+def _dominant_axis(W, rows, rough, i_index):
+    """continuous principal axis of <LL> on the time steps rows = (i1, i2), anchored at step i1 + i_index on the side of `rough`"""
+    i1, i2 = rows
+    modes = _modes(W)[i1:i2]
+    return engine.coprecessing_frame(W.t[i1:i2], modes, W.ell_min, W.ell_max, rough=rough, rough_index=i_index, want_axis=True,
+                                     ctx=getattr(W, "_ctx", None))[1]
 
 
 def LLDominantEigenvector(W, RoughDirection=np.array([0.0, 0.0, 1.0]), RoughDirectionIndex=0):
     """Principal axis of the <LL> matrix at every time step, made continuous in time (mode frame)."""
-    _, eigenvecs = np.linalg.eigh(LLMatrix(W))
-    return _make_continuous(eigenvecs[:, :, 2], np.asarray(RoughDirection, dtype=float), RoughDirectionIndex)  # largest eigenvalue last
+    n = W.n_times
+    if n == 0:
+        return np.zeros((0, 3))
+    i_index = int(RoughDirectionIndex)
+    if i_index < 0:
+        i_index += n
+    return _dominant_axis(W, (0, n), np.asarray(RoughDirection, dtype=float), i_index)
 
 
 def _qsqrt(q):
@@ -76,33 +87,47 @@ def _qsqrt(q):
     return p / np.linalg.norm(p)
 
 
-def corotating_frame(W, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12, z_alignment_region=None, return_omega=False):
-    """Rotor taking the current mode frame into the corotating frame: the integral of the waveform's angular velocity
-    starting from R0 (scri/mode_calculations.py:435-491).  z_alignment_region = (f1, f2): additionally align the dominant
-    eigenvector of <LL>, averaged over that fraction of the inspiral, with the z axis."""
-    omega = angular_velocity(W)
+def _corotating_frame_on_device(W, R0, tolerance, z_alignment_region, want_omega):
+    """The frame as a device array [n_times, 4] (not yet normalised), the constant rotor that z_alignment_region asks to multiply it by
+    on the right (or None), and the angular velocity on the host (or None)."""
+    from . import device_series
+
+    ctx = _context(W)
+    frame_dev = device_series.empty_real(ctx, (W.n_times, 4))
     R0 = np.asarray(getattr(R0, "components", R0), dtype=float)
-    frame = engine.integrate_angular_velocity(W.t, omega, R0=R0, tolerance=tolerance)
+    _, omega = engine.corotating_frame(W.t, _modes(W), W.ell_min, W.ell_max, frame_dev, R0=R0, tolerance=tolerance,
+                                       want_omega=want_omega or z_alignment_region is not None, ctx=ctx)
+    correction = None
     if z_alignment_region is not None:
         initial_time = W.t[0]
         n4 = W.n_times // 4  # WaveformBase.max_norm_time: skips the first quarter (scri/waveform_base.py:553-575)
-        inspiral_time = W.t[n4 + int(np.argmax((np.abs(W.data[n4:]) ** 2).sum(axis=1)))] - initial_time
+        norm = engine.row_norm(None, ctx=ctx, device_tensor=W._dev[n4:]) if getattr(W, "is_device_resident", False) else engine.row_norm(W.data[n4:], ctx=ctx)
+        inspiral_time = W.t[n4 + int(np.argmax(norm))] - initial_time
         t1 = initial_time + z_alignment_region[0] * inspiral_time
         t2 = initial_time + z_alignment_region[1] * inspiral_time
         i1 = int(np.argmin(np.abs(W.t - t1)))
         i2 = int(np.argmin(np.abs(W.t - t2)))
-        R = frame[i1:i2]
+        if i2 <= i1:
+            raise ValueError(f"z_alignment_region={z_alignment_region} selects no time steps")
+        R = frame_dev[i1:i2].cpu().numpy()
         i1m = max(0, i1 - 10)
         rough = omega[i1m + 10]
-        _, vecs = np.linalg.eigh(LLMatrix(W)[i1:i2])
-        Vhat = _make_continuous(vecs[:, :, 2], rough, 0)
+        Vhat = _dominant_axis(W, (i1, i2), rough, 0)
         V = np.concatenate([np.zeros((Vhat.shape[0], 1)), Vhat], axis=1)
         Vhat_corot = quaternions.multiply(quaternions.multiply(quaternions.conjugate(R), V), R)[:, 1:]
         mean = np.concatenate([[0.0], np.mean(Vhat_corot, axis=0)])
         mean /= np.linalg.norm(mean)
         correction = quaternions.conjugate(_qsqrt(quaternions.multiply(np.array([0.0, 0.0, 0.0, -1.0]), mean)))  # sqrt(-z V)^-1
-        frame = quaternions.multiply(frame, correction)
-    frame = frame / np.linalg.norm(frame, axis=1)[:, np.newaxis]
+    return frame_dev, correction, (omega if want_omega else None)
+
+
+def corotating_frame(W, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12, z_alignment_region=None, return_omega=False):
+    """Rotor taking the current mode frame into the corotating frame: the integral of the waveform's angular velocity
+    starting from R0 (scri/mode_calculations.py:435-491).  z_alignment_region = (f1, f2): additionally align the dominant
+    eigenvector of <LL>, averaged over that fraction of the inspiral, with the z axis."""
+    frame_dev, correction, omega = _corotating_frame_on_device(W, R0, tolerance, z_alignment_region, return_omega)
+    engine.frame_adjust(frame_dev, right=correction, ctx=_context(W))
+    frame = frame_dev.cpu().numpy()
     return (frame, omega) if return_omega else frame
 
 

@@ -150,9 +150,15 @@ def sqrt(q):
     return out
 
 
-def angular_velocity(R, t):
+def angular_velocity(R, t, ctx=None):
     """omega(t) = 2 Rdot R^-1 (vector part) of a rotor series, with the derivative of a cubic spline through the components
-    (quaternion.angular_velocity)."""
+    (quaternion.angular_velocity).  With an engine context `ctx` (or R a device array) this is the GPU entry
+    bms_rotor_angular_velocity, which the waveform methods use; without one, the same statement with scipy's spline on the host --
+    this module's helpers also serve callers that have no device."""
+    if ctx is not None or hasattr(R, "data_ptr"):
+        from . import engine
+
+        return engine.rotor_angular_velocity(t, R, ctx=ctx)
     from scipy.interpolate import CubicSpline
 
     R = np.asarray(R, dtype=float)
@@ -160,11 +166,16 @@ def angular_velocity(R, t):
     return 2.0 * multiply(Rdot, conjugate(R))[..., 1:]
 
 
-def minimal_rotation(R, t, iterations=2):
+def minimal_rotation(R, t, iterations=2, ctx=None):
     """Adjust a frame R(t) by rotations about its own z axis so that the adjusted frame has no angular velocity along that
     axis (numpy-quaternion's `minimal_rotation`, which scri/rotations.py:38 applies to the coprecessing frame):
     R' = R exp(gamma z / 2) with  gamma-dot / 2 = Re[ Rdot z R^-1 ],  the time derivative and integral taken with cubic
-    splines, iterated because the spline of R' differs from the rotated spline of R."""
+    splines, iterated because the spline of R' differs from the rotated spline of R.  With an engine context `ctx` (or R a device
+    array) this is the GPU entry bms_minimal_rotation; without one, the same statement with scipy's splines on the host."""
+    if ctx is not None or hasattr(R, "data_ptr"):
+        from . import engine
+
+        return engine.minimal_rotation(t, R, iterations=iterations, ctx=ctx)
     from scipy.interpolate import CubicSpline
 
     R = np.asarray(R, dtype=float)

@@ -16,11 +16,13 @@ def rotate_physical_system(W, R_phys):
     return W
 
 
-def rotate_decomposition_basis(W, R_basis):
+def rotate_decomposition_basis(W, R_basis, _spinors_dev=None):
     """Rotate a Waveform in place (scri/rotations.py:284-343).
 
     `R_basis`: a quaternion, or a list/array of 1 or n_times quaternions (np.quaternion objects or
     float components [..., 4]).  The change of basis is recorded in `W.frame` by right-multiplication.
+    (_spinors_dev: the same n_times rotors as spinors already on the device -- the frame functions below build them there -- so
+    that a device-resident waveform is rotated without an upload.)
     """
     is_q_obj = quaternions.is_quaternion_object(R_basis)
     if isinstance(R_basis, (list, tuple)) and len(R_basis) and not np.isscalar(R_basis[0]):
@@ -43,7 +45,7 @@ def rotate_decomposition_basis(W, R_basis):
         if on_device:
             from . import device_series
 
-            sp = device_series.to_device(W._ctx, quaternions.as_spinor_array(R))
+            sp = _spinors_dev if _spinors_dev is not None else device_series.to_device(W._ctx, quaternions.as_spinor_array(R))
             engine.rotate_device(W._dev.data_ptr(), W.n_times, W.n_modes, W.ell_min, W.ell_max, spinors_ptr=sp.data_ptr(), ctx=W._ctx)
             W._ctx.synchronize()  # (the rotor tensor goes out of scope)
         else:
@@ -69,28 +71,41 @@ def rotate_decomposition_basis(W, R_basis):
     return W
 
 
+def _frame_context(W):
+    from . import _lib
+
+    if W._ctx is None:
+        W._ctx = _lib.default_context()
+    return W._ctx
+
+
 def to_coprecessing_frame(W, RoughDirection=np.array([0.0, 0.0, 1.0]), RoughDirectionIndex=None, transition_times=None):
     """Transform a waveform (in place) to a coprecessing frame (scri/rotations.py:14-49): the dominant eigenvector of <LL>
-    (GPU) becomes the z axis, and the remaining freedom about it is fixed by the minimal-rotation condition."""
-    from . import Coprecessing
-    from .mode_calculations import LLDominantEigenvector
+    becomes the z axis, and the remaining freedom about it is fixed by the minimal-rotation condition.  The frame is built on the GPU
+    from the modes where they are (bms_coprecessing_frame) and rotates them from there; it comes to the host once, for W.frame.
+    (A host-resident waveform crosses the link twice: its modes go up for the frame, and the rotation of a host array is the pipelined
+    host route, which takes its rotors from the host copy of the frame.  Move the waveform to the device first to avoid both.)"""
+    from . import Coprecessing, device_series
+    from .mode_calculations import _modes
 
     if RoughDirectionIndex is None:
         RoughDirectionIndex = W.n_times // 8
-    dpa = LLDominantEigenvector(W, RoughDirection=RoughDirection, RoughDirectionIndex=RoughDirectionIndex)
-    v = dpa / np.linalg.norm(dpa, axis=-1)[:, None]
-    # sqrt(-v z): the rotor taking z to v
-    minus_vz = np.concatenate([v[:, 2:3], -np.cross(v, np.array([0.0, 0.0, 1.0]))], axis=-1)
-    R = quaternions.minimal_rotation(quaternions.sqrt(minus_vz), W.t, iterations=3)
+    ctx = _frame_context(W)
+    i_index = int(RoughDirectionIndex) + (W.n_times if RoughDirectionIndex < 0 else 0)
+    frame_dev = device_series.empty_real(ctx, (W.n_times, 4))
+    engine.coprecessing_frame(W.t, _modes(W), W.ell_min, W.ell_max, rough=np.asarray(RoughDirection, dtype=float), rough_index=i_index,
+                              iterations=3, frame_dev=frame_dev, ctx=ctx)
     if transition_times is not None:
         from .utilities import transition_function
 
-        i0, i1 = np.argmin(np.abs(W.t - transition_times[0])), np.argmin(np.abs(W.t - transition_times[1]))
+        i0, i1 = int(np.argmin(np.abs(W.t - transition_times[0]))), int(np.argmin(np.abs(W.t - transition_times[1])))
         transition = transition_function(W.t[i0:], W.t[i0], W.t[i1], y0=1.0, y1=0.0)
-        omega = quaternions.angular_velocity(R[i0:], W.t[i0:]) * transition[:, np.newaxis]
-        slowing = engine.integrate_angular_velocity(W.t[i0:], omega, R[i0])
-        R = np.concatenate((R[:i0], slowing))
-    rotate_decomposition_basis(W, R)
+        # the angular velocity of the frame, faded out over the transition, and the frame it integrates to from R[i0]
+        omega = engine.rotor_angular_velocity(W.t[i0:], frame_dev[i0:], ctx=ctx)
+        omega *= device_series._torch().from_numpy(np.ascontiguousarray(transition[:, np.newaxis])).to(omega.device)
+        engine.frame_from_angular_velocity(W.t[i0:], omega, R0=frame_dev[i0].cpu().numpy(), ctx=ctx, out=frame_dev[i0:])
+    _, spinors = engine.frame_adjust(frame_dev, want_spinors=True, ctx=ctx)
+    rotate_decomposition_basis(W, frame_dev.cpu().numpy(), _spinors_dev=spinors)
     W._append_history(f"{W}.to_coprecessing_frame({RoughDirection}, {RoughDirectionIndex}, {transition_times})")
     W.frameType = Coprecessing
     return W
@@ -109,22 +124,21 @@ def to_inertial_frame(W):
 
 def to_corotating_frame(W, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12, z_alignment_region=None, return_omega=False,
                         truncate_log_frame=False):
-    """Transform the waveform (in place) to a corotating frame (scri/rotations.py:52-103)."""
+    """Transform the waveform (in place) to a corotating frame (scri/rotations.py:52-103).  The frame is built on the GPU from the
+    modes where they are (bms_corotating_frame) and rotates them from there; it comes to the host once, for W.frame.  (For a
+    host-resident waveform see the note in to_coprecessing_frame: two passes over the link.)"""
     from . import Corotating
-    from .mode_calculations import corotating_frame
+    from .mode_calculations import _corotating_frame_on_device
 
-    frame, omega = corotating_frame(W, R0=R0, tolerance=tolerance, z_alignment_region=z_alignment_region, return_omega=True)
-    log_frame = None
-    if truncate_log_frame:
-        # keep only the bits of log(frame) above the tolerance: exp(truncated(log(frame))) rotates the waveform (:86-90)
-        log_frame = quaternions.log(frame)
-        power_of_2 = 2 ** int(-np.floor(np.log2(2 * tolerance)))
-        log_frame = np.round(log_frame * power_of_2) / power_of_2
-        frame = quaternions.exp(log_frame)
-    W.rotate_decomposition_basis(frame)
+    ctx = _frame_context(W)
+    frame_dev, correction, omega = _corotating_frame_on_device(W, R0, tolerance, z_alignment_region, return_omega)
+    # truncate_log_frame keeps only the bits of log(frame) above the tolerance: exp(truncated(log(frame))) rotates the waveform (:86-90)
+    log_frame, spinors = engine.frame_adjust(frame_dev, right=correction, truncate_tolerance=tolerance if truncate_log_frame else 0.0,
+                                             want_log=bool(truncate_log_frame), want_spinors=True, ctx=ctx)
+    rotate_decomposition_basis(W, frame_dev.cpu().numpy(), _spinors_dev=spinors)
     W._append_history(f"{W}.to_corotating_frame({R0}, {tolerance}, {z_alignment_region}, {return_omega}, {truncate_log_frame})")
     W.frameType = Corotating
-    out = (W,) + ((omega,) if return_omega else ()) + ((log_frame,) if truncate_log_frame else ())
+    out = (W,) + ((omega,) if return_omega else ()) + ((log_frame.cpu().numpy(),) if truncate_log_frame else ())
     return out if len(out) > 1 else W
 
 

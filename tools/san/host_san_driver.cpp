@@ -1,7 +1,7 @@
 // Host-side sanitizer run (no GPU sanitizer exists on this pool: ASan / UBSan cover what runs on the host).
 // `make -C scri_amd/csrc SAN=1` compiles this file -- which INCLUDES the host side of the engine (engine_*.hip, split by entry family
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
-// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables and the frame integrator over the five BASELINE shapes, 1..8 shards,
+// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables, the frame integrator and the argument checks of the device frame chain over the five BASELINE shapes, 1..8 shards,
 // 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
@@ -9,6 +9,7 @@
 #include "../../scri_amd/csrc/engine_modes.hip"
 #include "../../scri_amd/csrc/engine_abd.hip"
 #include "../../scri_amd/csrc/engine_blocks.hip"
+#include "../../scri_amd/csrc/engine_frames.hip"
 
 #include <cstdio>
 #include <random>
@@ -216,6 +217,26 @@ void frame_integration() {
   }
 }
 
+// The device frame chain (engine_frames.hip) refuses what it cannot run before it touches a device: no context, no arrays.
+void frame_chain_arguments() {
+  double t[4] = {0.0, 0.1, 0.2, 0.3}, v[16] = {0}, out[16];
+  const double R0[4] = {1, 0, 0, 0}, z[3] = {0, 0, 1};
+  REQUIRE(bms_frame_from_angular_velocity(nullptr, t, 4, v, BMS_HOST, R0, 1e-12, out) == BMS_ERR_INVALID);
+  REQUIRE(bms_dominant_axis(nullptr, v, 1, BMS_HOST, z, 0, out) == BMS_ERR_INVALID);
+  REQUIRE(bms_minimal_rotation(nullptr, t, 4, v, BMS_HOST, 3, out) == BMS_ERR_INVALID);
+  REQUIRE(bms_rotor_angular_velocity(nullptr, t, 4, v, BMS_HOST, out) == BMS_ERR_INVALID);
+  REQUIRE(bms_frame_adjust(nullptr, v, 4, BMS_HOST, nullptr, 0.0, nullptr, nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_corotating_frame(nullptr, t, 4, v, 1, 0, 0, BMS_HOST, R0, 1e-12, out, nullptr, nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_coprecessing_frame(nullptr, t, 4, v, 1, 0, 0, BMS_HOST, z, 0, 3, nullptr, nullptr, out) == BMS_ERR_INVALID);
+  bms_ctx dummy;
+  REQUIRE(check_time_axis(&dummy, t, 3) == BMS_ERR_UNSUPPORTED);
+  t[2] = t[1];
+  REQUIRE(check_time_axis(&dummy, t, 4) == BMS_ERR_INVALID);
+  int nm = 0;
+  REQUIRE(modes_checks(&dummy, 2, 8, 77, &nm) == BMS_OK && nm == 77);
+  REQUIRE(modes_checks(&dummy, 2, 8, 76, &nm) == BMS_ERR_INVALID);
+  REQUIRE(modes_checks(&dummy, 2, MAX_ELL + 1, 1 << 30, &nm) == BMS_ERR_UNSUPPORTED);
+}
 
 // The slab the named work-space buffers are carved from (bms_ctx_reserve): random grow / release sequences against a brute-force
 // picture of the address range -- regions never overlap, freed neighbours coalesce, what is free plus what is held is the slab.
@@ -278,6 +299,7 @@ int main() {
   for (const Shape& s : shapes) run_shape(s);
   short_series_and_odd_grids();
   frame_integration();
+  frame_chain_arguments();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
