@@ -392,6 +392,31 @@ int bms_coprecessing_frame(bms_ctx* ctx, const double* t, int64_t n_times, const
                            const double rough[3], int64_t rough_index, int iterations, double* frame_dev, double* frame_out,
                            double* axis_out);
 
+/* ---- time-and-phase alignment of two waveforms from correlation moments (scri_amd/alignment.py; DESIGN: "Alignment as moments") ----
+ * The moving waveform A: time axis ta[na] (host, na >= 4, strictly increasing), values ya and knot slopes sa of its not-a-knot cubic
+ * spline, both c16[na][ld_a] in `mem` (the slopes are bms_spline_derivative(order = 1) evaluated at ta itself).  The fixed waveform B:
+ * window times tw[nw] and quadrature weights w[nw] (host, nw >= 2), b = its first window row, c16[nw][ld_b] in `mem`.  Common column k
+ * (k < n_cols) is column col_a[k] of A and col_b[k] of B (host int32 tables).  The spline is evaluated in the local Hermite form of
+ * bms_spline_derivative; the interval of an argument is the last knot <= it (the last interval closed; an argument outside ta takes the
+ * end interval's cubic).
+ *
+ * bms_align_moments: for every offset dts[k] (host, nd of them, finite, ascending) and derivative order o <= order (0, 1 or 2)
+ *     out[o][k][0]             = (d/ddt)^o  sum_i w_i sum_c |A_c(tw_i + dt)|^2
+ *     out[o][k][1 + 2 s, + 1]  = Re, Im of (d/ddt)^o  sum_i w_i sum_{c: m_slot[c] = s} A_c(tw_i + dt) conj(B_ic)
+ * out: host f8[order + 1][nd][1 + 2 n_slots]; m_slot: host int32[n_cols] in [0, n_slots).  The sums are formed in a fixed order that
+ * does not depend on the other offsets of the call, nor on `mem`: an offset's moments are the same bits scanned alone or among
+ * thousands.  Limits (BMS_ERR_UNSUPPORTED): na <= 2^31, n_slots <= 16385; nothing else bounds the sizes (long offset lists and windows
+ * run as several launches).
+ *
+ * bms_align_residual: out[0] = sum_i w_i sum_c |A_c(tw_i + dt) e^{i m_of[c] dphi} - B_ic|^2 and out[1] = sum_i w_i sum_c |B_ic|^2,
+ * summed directly (non-negative, smooth at a perfect match); m_of: host int32[n_cols]. */
+int bms_align_moments(bms_ctx* ctx, const double* ta, int64_t na, const void* ya, const void* sa, int64_t ld_a, const int32_t* col_a,
+                      const double* tw, const double* w, int64_t nw, const void* b, int64_t ld_b, const int32_t* col_b, int n_cols,
+                      const int32_t* m_slot, int n_slots, int mem, const double* dts, int64_t nd, int order, double* out);
+int bms_align_residual(bms_ctx* ctx, const double* ta, int64_t na, const void* ya, const void* sa, int64_t ld_a, const int32_t* col_a,
+                       const double* tw, const double* w, int64_t nw, const void* b, int64_t ld_b, const int32_t* col_b, int n_cols,
+                       const int32_t* m_of, int mem, double dt, double dphi, double out[2]);
+
 /* ---- bit transforms of the storage formats (scri/utilities.py:194-406), bit-exact ------------ */
 /* xor_timeseries (reverse = 0) / xor_timeseries_reverse (reverse = 1), in place: data viewed as uint64[n_rows][words_per_row],
  * time along the rows; row 0 is unchanged, row i becomes row[i-1] ^ row[i] (forward) or the running XOR (reverse). */

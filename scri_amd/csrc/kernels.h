@@ -360,6 +360,36 @@ hipError_t launch_rotor_omega(hipStream_t stream, const double* R, const double*
 hipError_t launch_frame_adjust(hipStream_t stream, double* frame, long long n, Vec4 right, int with_right, double pow2, double* log_out,
                                double* spinors);
 
+// ---- time-and-phase alignment from correlation moments (kernels_align.hip; scri_amd/alignment.py)
+constexpr int ALIGN_TILE_OFFSETS = 16;    // offsets x rows of a workgroup's tile; the row tiling fixes the order of every sum
+constexpr int ALIGN_TILE_ROWS = 64;
+constexpr int ALIGN_CHUNK_COLS = 16;      // columns staged at a time
+constexpr int ALIGN_STRETCH_KNOTS = 112;  // knots of the moving waveform a tile stages in LDS; a longer stretch is read through L2
+constexpr long long ALIGN_MAX_KNOTS = 1LL << 31;  // a tile keeps the intervals of its arguments as 32-bit offsets into its stretch
+constexpr int ALIGN_MAX_SLOTS = 2 * 8192 + 1;     // one slot per m of the largest l the mode kernels carry (engine.h, MAX_ELL)
+inline long long align_row_tiles(long long nw) { return (nw + ALIGN_TILE_ROWS - 1) / ALIGN_TILE_ROWS; }
+struct AlignSeries {  // the two waveforms of one alignment, all device memory
+  const double* ta;   // [na] time axis of the moving waveform, strictly increasing
+  long long na;
+  const double2* Y;   // c16[na][ld_a] its values ...
+  const double2* S;   // ... and the slopes of its not-a-knot spline at the knots
+  long long ld_a;
+  const int* col_a;   // [n_cols] column of Y / S per common column
+  const double* tw;   // [nw] window times of the fixed waveform, strictly increasing
+  const double* w;    // [nw] quadrature weights
+  long long nw;
+  const double2* B;   // c16[nw][ld_b] window rows of the fixed waveform
+  long long ld_b;
+  const int* col_b;   // [n_cols]
+  int n_cols;
+};
+// out[o][d0 + d][1 + 2 n_slots] (o <= order, rows of nd_total offsets) = (N_a, Re C_0, Im C_0, ...) of the offsets dts[0 .. nd) and their
+// dt-derivatives; m_slot[n_cols] in [0, n_slots); dts ascending; partial: align_row_tiles(nw) (order + 1) nd (1 + 2 n_slots) doubles
+hipError_t launch_align_moments(hipStream_t stream, const AlignSeries& a, const int* m_slot, int n_slots, const double* dts, long long nd,
+                                long long d0, long long nd_total, int order, double* partial, double* out);
+// out2 = (sum_i w_i sum_c |A_c(t_i + dt) phase_c - B_ic|^2, sum_i w_i sum_c |B_ic|^2); phase c16[n_cols]; partial: 2 align_row_tiles(nw) doubles
+hipError_t launch_align_residual(hipStream_t stream, const AlignSeries& a, const double* phase, double dt, double* partial, double* out2);
+
 // ---- bit transforms of the storage formats (kernels_bits.hip; scri/utilities.py:194-406)
 // rows of n_cols 64-bit words; forward: out[i] = in[i-1] ^ in[i]; reverse: running XOR (carry: xor_carry_words words)
 long long xor_carry_words(long long n_rows, long long n_cols);

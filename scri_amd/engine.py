@@ -1016,6 +1016,101 @@ def coprecessing_frame(t, data, ell_min, ell_max, rough=(0.0, 0.0, 1.0), rough_i
     return frame, axis
 
 
+# ---- time-and-phase alignment from correlation moments (bms_align_moments, bms_align_residual; scri_amd/alignment.py)
+
+
+def _align_bulk(ctx, x, what):
+    """(address, row stride, the tensor) of a bulk array c16[n][ld]: a device tensor goes through untouched, a host array goes up once"""
+    from . import device_series
+
+    device_series.attach(ctx)
+    if not hasattr(x, "data_ptr"):
+        x = device_series.to_device(ctx, x)
+    import torch
+
+    if x.dtype != torch.complex128 or x.ndim != 2 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError(f"{what}: expected complex128 [n, n_cols] with unit column stride on the device, got {x.dtype} of shape {tuple(x.shape)}")
+    _on_device_of(ctx, x)
+    return c_vp(x.data_ptr()), (x.stride(0) if x.shape[0] > 1 else max(x.shape[1], 1)), x
+
+
+def _align_series(ctx, ta, ya, sa, col_a, tw, w, b, col_b):
+    """the arguments the two alignment entries share, and what has to stay alive while they run"""
+    ta = np.ascontiguousarray(ta, dtype=float)
+    tw = np.ascontiguousarray(tw, dtype=float)
+    w = np.ascontiguousarray(w, dtype=float)
+    col_a = np.ascontiguousarray(col_a, dtype=np.int32)
+    col_b = np.ascontiguousarray(col_b, dtype=np.int32)
+    if ta.ndim != 1 or tw.ndim != 1 or w.shape != tw.shape or col_a.ndim != 1 or col_a.shape != col_b.shape:
+        raise ValueError("alignment takes 1-d time axes, one weight per window row and column tables of one length")
+    ya_ptr, ld_a, ya = _align_bulk(ctx, ya, "values of the moving waveform")
+    sa_ptr, ld_s, sa = _align_bulk(ctx, sa, "slopes of the moving waveform")
+    b_ptr, ld_b, b = _align_bulk(ctx, b, "window rows of the fixed waveform")
+    if tuple(ya.shape) != tuple(sa.shape) or ld_s != ld_a or ya.shape[0] != ta.shape[0]:
+        raise ValueError("values and slopes of the moving waveform must have one shape and row stride, one row per time step")
+    if b.shape[0] != tw.shape[0]:
+        raise ValueError("the fixed waveform needs one row per window time")
+    if col_a.size and (col_a.min() < 0 or col_a.max() >= ya.shape[1] or col_b.min() < 0 or col_b.max() >= b.shape[1]):
+        raise ValueError("a column table names a column outside its array")
+    i32 = ctypes.POINTER(ctypes.c_int32)
+    args = (dptr(ta), ta.shape[0], ya_ptr, sa_ptr, ld_a, col_a.ctypes.data_as(i32), dptr(tw), dptr(w), tw.shape[0], b_ptr, ld_b,
+            col_b.ctypes.data_as(i32), col_a.shape[0])
+    return args, (ta, tw, w, col_a, col_b, ya, sa, b)
+
+
+def align_moments(ta, ya, sa, col_a, tw, w, b, col_b, m_slot, n_slots, dts, order=0, ctx=None):
+    """Correlation moments of the alignment cost at the time offsets `dts` (ascending) with their dt-derivatives up to `order` (0..2):
+    out[o, k, 0] = (d/ddt)^o sum_i w_i sum_c |A_c(tw_i + dts_k)|^2,  out[o, k, 1 + 2 s] + i out[o, k, 2 + 2 s] =
+    (d/ddt)^o sum_i w_i sum_{c: m_slot[c] = s} A_c(tw_i + dts_k) conj(b[i, col_b[c]]),  A_c = the cubic spline through (ta, ya[:, col_a[c]])
+    whose knot slopes are sa.  ya, sa [na, *] and b [nw, *] are device tensors (complex128) or host arrays, which are uploaded once.
+    Returns a host array [order + 1, len(dts), 1 + 2 n_slots]."""
+    ctx = _ctx(ctx)
+    args, _keep = _align_series(ctx, ta, ya, sa, col_a, tw, w, b, col_b)
+    m_slot = np.ascontiguousarray(m_slot, dtype=np.int32)
+    dts = np.ascontiguousarray(dts, dtype=float)
+    if m_slot.shape != (args[-1],) or dts.ndim != 1:
+        raise ValueError("align_moments takes one slot per common column and a 1-d array of offsets")
+    out = np.empty((int(order) + 1, dts.shape[0], 1 + 2 * int(n_slots)))
+    rc = _lib.load().bms_align_moments(ctx.handle, *args, m_slot.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(n_slots), BMS_DEVICE,
+                                       dptr(dts), dts.shape[0], int(order), dptr(out))
+    ctx.check(rc, "bms_align_moments")
+    return out
+
+
+def align_residual(ta, ya, sa, col_a, tw, w, b, col_b, m_of, dt, dphi, ctx=None):
+    """(sum_i w_i sum_c |A_c(tw_i + dt) e^{i m_of[c] dphi} - b[i, col_b[c]]|^2,  sum_i w_i sum_c |b[i, col_b[c]]|^2), both summed
+    directly on the GPU; arguments as align_moments."""
+    ctx = _ctx(ctx)
+    args, _keep = _align_series(ctx, ta, ya, sa, col_a, tw, w, b, col_b)
+    m_of = np.ascontiguousarray(m_of, dtype=np.int32)
+    if m_of.shape != (args[-1],):
+        raise ValueError("align_residual takes one azimuthal number per common column")
+    out = np.empty(2)
+    rc = _lib.load().bms_align_residual(ctx.handle, *args, m_of.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), BMS_DEVICE, float(dt), float(dphi),
+                                        dptr(out))
+    ctx.check(rc, "bms_align_residual")
+    return float(out[0]), float(out[1])
+
+
+def knot_slopes(t, y, ctx=None):
+    """Slopes at the knots of the not-a-knot cubic spline through (t, y) for a device tensor y [n, n_cols] (complex128, unit column
+    stride): bms_spline_derivative(order = 1) evaluated at the knots themselves, device to device.  A new tensor of y's shape."""
+    import torch
+
+    from . import device_series
+
+    ctx = _ctx(ctx)
+    device_series.attach(ctx)
+    _on_device_of(ctx, y)
+    t = np.ascontiguousarray(t, dtype=float)
+    n, n_cols = y.shape
+    out = torch.empty((n, n_cols), dtype=torch.complex128, device=y.device)
+    rc = _lib.load().bms_spline_derivative(ctx.handle, dptr(t), n, c_vp(y.data_ptr()), y.stride(0) if n > 1 else max(n_cols, 1), n_cols, BMS_DEVICE,
+                                           dptr(t), n, 1, c_vp(out.data_ptr()))
+    ctx.check(rc, "bms_spline_derivative")
+    return out
+
+
 def integrate_angular_velocity(t, omega, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12):
     """R[N, 4] with R[0] = R0 and dR/dt = (1/2) Omega R for the cubic spline Omega through omega[N, 3] (host routine)."""
     t = np.ascontiguousarray(t, dtype=float)

@@ -7,6 +7,7 @@ import numpy as np
 
 from . import engine
 from .bms_transformations import BMSTransformation
+from .alignment import strain_of
 from .mode_algebra import constant_as_ell_0_mode
 
 NORMAL = ["supertranslation", "frame_rotation", "boost_velocity"]
@@ -56,7 +57,7 @@ def map_to_abd_frame(
         """the time translation + turn about z that carries `strain` onto `target` on [t_a, t_b], and the alignment's error"""
         from .alignment import align2d
 
-        err, _, res = align2d(strain, target, t_a, t_b, n_brute_force_δt=None, n_brute_force_δϕ=None, include_modes=None, nprocs=nprocs)
+        err, _, res = align2d(strain, target, t_a, t_b, n_brute_force_δt=None, n_brute_force_δϕ=None, include_modes=None, nprocs=nprocs, ctx=ctx)
         half = 0.5 * res.x[1]
         return err, BMSTransformation(
             supertranslation=[constant_as_ell_0_mode(res.x[0])], frame_rotation=np.array([np.cos(half), 0.0, 0.0, np.sin(half)]), ctx=ctx
@@ -95,11 +96,11 @@ def map_to_abd_frame(
         abd_interp_superrest, transformation1, _ = abd_interp_prime.map_to_superrest_frame(**superrest_kw)
         between = BMSTransformation(ctx=ctx)
         if fix_time_phase_freedom:  # align in the super rest frame, where only time and phase are left free
-            _, between = time_phase(abd_interp_superrest.h, target_strain_superrest, t_0 - padding_time, t_0 + padding_time)
+            _, between = time_phase(strain_of(abd_interp_superrest), target_strain_superrest, t_0 - padding_time, t_0 + padding_time)
         BMS = (transformation2.inverse() * (between * (transformation1 * BMS))).reorder(NORMAL)
         abd_interp_prime = apply(abd_interp, BMS)
         if fix_time_phase_freedom:  # and once more in the target's frame
-            rel_err, again = time_phase(abd_interp_prime.h, target_strain, t_0 - padding_time, t_0 + padding_time)
+            rel_err, again = time_phase(strain_of(abd_interp_prime), target_strain, t_0 - padding_time, t_0 + padding_time)
             BMS = (again * BMS).reorder(NORMAL)
             abd_interp_prime = apply(abd_interp, BMS)
         else:

@@ -517,11 +517,11 @@ def map_to_superrest_frame(
                 # nothing (the reference re-applies whatever the previous step found, or fails when it is the first step).
                 new = BMSTransformation(ell_max=ell_max, ctx=ctx)
                 if target_strain is not None:
-                    from .alignment import align2d
+                    from .alignment import align2d, strain_of
 
                     rel_err, _, res = align2d(
-                        abd_sliced_prime.h, target_strain, 0 - padding_time, 0 + padding_time, n_brute_force_δt=None,
-                        n_brute_force_δϕ=None, include_modes=modes, nprocs=4,
+                        strain_of(abd_sliced_prime), target_strain, 0 - padding_time, 0 + padding_time, n_brute_force_δt=None,
+                        n_brute_force_δϕ=None, include_modes=modes, nprocs=4, ctx=ctx,
                     )
                     new = BMSTransformation(
                         supertranslation=[constant_as_ell_0_mode(res.x[0])], frame_rotation=_about_z(res.x[1]), ell_max=ell_max, ctx=ctx,

@@ -1,7 +1,7 @@
 // Host-side sanitizer run (no GPU sanitizer exists on this pool: ASan / UBSan cover what runs on the host).
 // `make -C scri_amd/csrc SAN=1` compiles this file -- which INCLUDES the host side of the engine (engine_*.hip, split by entry family
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
-// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables, the frame integrator and the argument checks of the device frame chain over the five BASELINE shapes, 1..8 shards,
+// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables, the frame integrator and the argument checks of the device frame chain and of the alignment entries over the five BASELINE shapes, 1..8 shards,
 // 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
@@ -10,6 +10,7 @@
 #include "../../scri_amd/csrc/engine_abd.hip"
 #include "../../scri_amd/csrc/engine_blocks.hip"
 #include "../../scri_amd/csrc/engine_frames.hip"
+#include "../../scri_amd/csrc/engine_align.hip"
 
 #include <cstdio>
 #include <random>
@@ -238,6 +239,29 @@ void frame_chain_arguments() {
   REQUIRE(modes_checks(&dummy, 2, MAX_ELL + 1, 1 << 30, &nm) == BMS_ERR_UNSUPPORTED);
 }
 
+// The alignment entries (engine_align.hip) do the same, and their checks of the host arrays run before anything is staged.
+void alignment_arguments() {
+  double ta[4] = {0.0, 0.1, 0.2, 0.3}, tw[2] = {0.1, 0.2}, w[2] = {0.05, 0.05}, v[16] = {0}, dts[2] = {0.0, 0.05}, out[16];
+  const int32_t col[1] = {0}, slot[1] = {0};
+  REQUIRE(bms_align_moments(nullptr, ta, 4, v, v, 1, col, tw, w, 2, v, 1, col, 1, slot, 1, BMS_HOST, dts, 2, 0, out) == BMS_ERR_INVALID);
+  REQUIRE(bms_align_residual(nullptr, ta, 4, v, v, 1, col, tw, w, 2, v, 1, col, 1, slot, BMS_HOST, 0.0, 0.0, out) == BMS_ERR_INVALID);
+  bms_ctx dummy;
+  AlignHost h = {ta, 4, v, v, 1, col, tw, w, 2, v, 1, col, 1, BMS_HOST};
+  REQUIRE(align_checks(&dummy, h) == BMS_OK);
+  h.na = 3;
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
+  h.na = 4, h.nw = 1;
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
+  h.nw = 2, h.n_cols = 0;
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
+  h.n_cols = 1, h.ld_a = 0;
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
+  h.ld_a = 1, h.ya = nullptr;
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
+  h.ya = v, ta[2] = ta[1];
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
+}
+
 // The slab the named work-space buffers are carved from (bms_ctx_reserve): random grow / release sequences against a brute-force
 // picture of the address range -- regions never overlap, freed neighbours coalesce, what is free plus what is held is the slab.
 void slab_allocator() {
@@ -300,6 +324,7 @@ int main() {
   short_series_and_odd_grids();
   frame_integration();
   frame_chain_arguments();
+  alignment_arguments();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
