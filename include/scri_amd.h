@@ -440,6 +440,37 @@ int bms_extrapolate(bms_ctx* ctx, int n_radii, const void* const* series, const 
                     int64_t n_modes, const double* radii, int n_orders, const int* orders, void* out, int blocks,
                     int64_t* n_deficient);
 
+/* ---- the precessing sample waveform (scri/sample_waveforms.py:383-533, fake_precessing_waveform) and its finite-radius family -----
+ * Strain modes l = 2 .. ell_max of a binary with leading-order PN phasing and amplitudes, a smooth merger and ringdown, in a frame that
+ * precesses and nutates, generated per time step on the device.  t: host f8[n], the caller's time axis (np.arange(t_0, t_1 + 0.99 dt,
+ * dt)), strictly increasing; the merger is at t_merger = t_1 - 100 and must be at least 20 steps in.  The amplitude of mode k is
+ * coef[k] x^power[k] with x = omega^(2/3) (pn_leading_order_amplitude, :536-593: host tables c16[n_modes], f8[n_modes], powers
+ * multiples of 1/2).  derive_*: take the reference's default for that parameter (:489-492) instead of the field.
+ * data_out: c16[n][ld] in `mem` (n_modes columns are written, the rest of a row is left alone) -- the modes in the corotating frame, or
+ * with inertial != 0 rotated back by the inverse of the frame (bms_rotate_series on the device).  frame_out: host f8[n][4], the
+ * corotating frame whatever `inertial` is (may be NULL).  The steps at which the piecewise definitions change (the reference's argmin
+ * searches) are found on the host; the three cumulative integrals are the spline antiderivatives of bms_spline_derivative(order = -1)
+ * over windows near the merger, which need at least 4 steps each (BMS_ERR_UNSUPPORTED otherwise). */
+typedef struct {
+  double mass_ratio;        /* > 0; a ratio below 1 is inverted */
+  double t_merger;
+  double opening_angle;     /* precession_opening_angle */
+  double opening_angle_dot; /* precession_opening_angle_dot */
+  double relative_rate;     /* precession_relative_rate */
+  double nutation_angle;    /* precession_nutation_angle */
+  int derive_opening_angle_dot; /* != 0: 2 opening_angle / (end of the ringdown transition - t[0]) */
+  int derive_nutation_angle;    /* != 0: opening_angle / 10 */
+  const void* coef;         /* host c16[n_modes] */
+  const double* power;      /* host f8[n_modes] */
+} bms_precessing_params;
+int bms_precessing_waveform(bms_ctx* ctx, const double* t, int64_t n, int ell_max, const bms_precessing_params* params, int inertial,
+                            void* data_out, int64_t ld, int mem, double* frame_out);
+/* One member of the finite-radius family built on it (:740-742, the docstring's model): out[t][c] = h0[t][c] + |h0[t][c]| sum_{k=1..n_terms}
+ * amp R^-k exp(i k (50 pi / n) t[t]).  h0 c16[n][ld_h0] and out c16[n][ld_out] (n_cols columns used) live in `mem` and must not overlap;
+ * t: host f8[n].  0 <= n_terms <= 16. */
+int bms_radius_terms(bms_ctx* ctx, const double* t, int64_t n, const void* h0, int64_t ld_h0, int64_t n_cols, int n_terms, double amp,
+                     double radius, void* out, int64_t ld_out, int mem);
+
 #ifdef __cplusplus
 }
 #endif

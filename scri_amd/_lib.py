@@ -63,6 +63,12 @@ class bms_shard(ctypes.Structure):
                 ("col_parts", ctypes.c_int32)]
 
 
+class bms_precessing_params(ctypes.Structure):
+    _fields_ = [("mass_ratio", ctypes.c_double), ("t_merger", ctypes.c_double), ("opening_angle", ctypes.c_double),
+                ("opening_angle_dot", ctypes.c_double), ("relative_rate", ctypes.c_double), ("nutation_angle", ctypes.c_double),
+                ("derive_opening_angle_dot", c_int), ("derive_nutation_angle", c_int), ("coef", c_vp), ("power", c_dp)]
+
+
 KERNEL_TAGS = ("rotate", "setup", "gemm_synthesis", "spline_forward", "spline_backward", "gemm_analysis", "pointwise", "theta_quadrature", "analysis_fused", "analysis_large")
 
 # every symbol include/scri_amd.h declares: (restype, argtypes)
@@ -152,6 +158,8 @@ SIGNATURES = {
     "bms_cubic_spline": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_i64, c_int, c_dp, c_i64, c_vp]),
     "bms_extrapolate": (c_int, [c_vp, c_int, c_vp, ctypes.POINTER(c_i64), c_int, c_i64, c_i64, c_vp, c_int, ctypes.POINTER(c_int), c_vp, c_int,
                                 ctypes.POINTER(c_i64)]),
+    "bms_precessing_waveform": (c_int, [c_vp, c_dp, c_i64, c_int, ctypes.POINTER(bms_precessing_params), c_int, c_vp, c_i64, c_int, c_dp]),
+    "bms_radius_terms": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_i64, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_int]),
     "bms_spline_derivative": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_i64, c_int, c_dp, c_i64, c_int, c_vp]),
     "bms_angular_velocity": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_dp, c_dp, c_dp]),
     "bms_integrate_angular_velocity": (c_int, [c_vp, c_dp, c_i64, c_dp, c_dp, ctypes.c_double, c_dp]),

@@ -9,6 +9,7 @@
 //   engine_blocks.hip    building blocks, series and bit operators               (bms_rotor_grid ... bms_grid_multiply, bms_xor_timeseries ...)
 //   engine_frames.hip    corotating / coprecessing frames built on the device                                (bms_corotating_frame ..., bms_dominant_axis ...)
 //   engine_align.hip     time-and-phase alignment from correlation moments                                   (bms_align_moments, bms_align_residual)
+//   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 #pragma once
 #include <algorithm>
 #include <array>

@@ -431,4 +431,30 @@ hipError_t launch_extrapolate(hipStream_t stream, const ExtrapSource* src, int n
                               long long n_times, int n_modes, const int* orders, int n_orders, double2* out, long long out_order_stride,
                               unsigned long long* deficient);
 
+// ---- the precessing sample waveform and its finite-radius family (scri/sample_waveforms.py:383-755; kernels_sample.hip)
+struct SamplePlan;   // sample_math.h: the steps at which the piecewise definitions change
+struct SampleMode {  // one column of the corotating modes: c_lm x^(twice_power / 2) (1 + sign_m modulation) ringdown
+  double re, im;
+  int twice_power, sign_m;
+};
+// phi_pn f8[n], omega f8[n] (blended), omega_col c16[n - i0] = (omega, 0) from step i0 on
+hipError_t launch_sample_phase(hipStream_t stream, const SamplePlan& P, const double* t, double* phi_pn, double* omega, double2* omega_col);
+// integrands c16[ib - ia] = (opening-angle series, precession-angle series) times the slope of the falling transition; I_omega c16[n - i0]:
+// the antiderivative of omega_col (zero at step i0)
+hipError_t launch_sample_window(hipStream_t stream, const SamplePlan& P, const double* t, const double* phi_pn, const double2* I_omega,
+                                double2* integrands);
+// frame f8[n][4], out c16[n][ld] (n_modes columns written), spinors f8[n][4] of conj(frame) (may be null); I_window c16[ib - ia]: the
+// antiderivative of the integrands (zero at step ia); left f8[4]: work space, receives conj(sqrt(frame[0]))
+hipError_t launch_sample_waveform(hipStream_t stream, const SamplePlan& P, const double* t, const double* phi_pn, const double* omega,
+                                  const double2* I_omega, const double2* I_window, double* left, const SampleMode* modes, int n_modes,
+                                  double2* out, long long ld, double* frame, double* spinors);
+constexpr int RADIUS_TERMS_MAX = 16;
+struct RadiusTerms {  // coef[k - 1] = amp R^-k, k = 1 .. n
+  int n;
+  double coef[RADIUS_TERMS_MAX];
+};
+// out[t][c] = h0[t][c] + |h0[t][c]| sum_k coef[k - 1] exp(i k (50 pi / n) t_t); out and h0 must not overlap
+hipError_t launch_radius_terms(hipStream_t stream, const double* t, long long n, const double2* h0, long long ld0, int n_cols,
+                               const RadiusTerms& terms, double2* out, long long ld_out);
+
 }  // namespace bms

@@ -742,6 +742,63 @@ def extrapolate(series, radii, orders, ctx=None, device=False, out=None, blocks=
     return (None if device else out), counts
 
 
+def precessing_waveform(t, ell_max, t_merger, mass_ratio, opening_angle, opening_angle_dot, relative_rate, nutation_angle, coef, power,
+                        inertial=False, out=None, ctx=None):
+    """The modes and the frame of scri's `fake_precessing_waveform` on the time axis t (bms_precessing_waveform): data[N, n_modes],
+    l = 2 .. ell_max, in the corotating frame or (inertial) rotated back from it, and the corotating frame [N, 4] (host).
+    opening_angle_dot / nutation_angle None: the reference's defaults.  coef, power: the amplitude tables of the modes.  `out`: a device
+    tensor [N, >= n_modes] (complex128, unit column stride) that receives the modes, or None for a new host array.  Returns (data, frame)."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, out)
+    t = np.ascontiguousarray(t, dtype=float)
+    n, n_modes = t.shape[0], LM_total_size(2, ell_max)
+    coef = np.ascontiguousarray(coef, dtype=np.complex128)
+    power = np.ascontiguousarray(power, dtype=float)
+    if coef.shape != (n_modes,) or power.shape != (n_modes,):
+        raise ValueError(f"the amplitude tables must hold {n_modes} modes, got {coef.shape} and {power.shape}")
+    p = _lib.bms_precessing_params(
+        mass_ratio=float(mass_ratio), t_merger=float(t_merger), opening_angle=float(opening_angle),
+        opening_angle_dot=0.0 if opening_angle_dot is None else float(opening_angle_dot), relative_rate=float(relative_rate),
+        nutation_angle=0.0 if nutation_angle is None else float(nutation_angle), derive_opening_angle_dot=int(opening_angle_dot is None),
+        derive_nutation_angle=int(nutation_angle is None), coef=coef.ctypes.data, power=dptr(power))
+    if out is None:
+        data = np.empty((n, n_modes), dtype=np.complex128)
+        ptr, ld, mem = vptr(data), n_modes, BMS_HOST
+    else:
+        data = out
+        if out.shape[0] != n or out.shape[1] < n_modes or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError(f"out of shape {tuple(out.shape)} cannot take {n} rows of {n_modes} modes")
+        ptr, ld, mem = c_vp(out.data_ptr()), (out.stride(0) if n > 1 else out.shape[1]), BMS_DEVICE
+    frame = np.empty((n, 4))
+    rc = _lib.load().bms_precessing_waveform(ctx.handle, dptr(t), n, int(ell_max), ctypes.byref(p), int(bool(inertial)), ptr, ld, mem, dptr(frame))
+    ctx.check(rc, "bms_precessing_waveform")
+    return data, frame
+
+
+def radius_terms(t, h0, n_terms, amp, radius, out, ctx=None):
+    """out = h0 + |h0| sum_{k=1..n_terms} amp radius^-k exp(i k (50 pi / N) t) (bms_radius_terms): one member of the finite-radius
+    family of scri's sample waveforms.  h0 and out: device tensors [N, n_cols] (complex128, unit column stride), or numpy arrays."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, h0, out)
+    t = np.ascontiguousarray(t, dtype=float)
+    n, n_cols = t.shape[0], int(h0.shape[1])
+    if tuple(h0.shape) != (n, n_cols) or tuple(out.shape) != (n, n_cols):
+        raise ValueError(f"h0 {tuple(h0.shape)} and out {tuple(out.shape)} must both be ({n}, {n_cols})")
+    if hasattr(h0, "data_ptr") != hasattr(out, "data_ptr"):
+        raise ValueError("h0 and out must live in the same memory")
+    if hasattr(h0, "data_ptr"):
+        args = (c_vp(h0.data_ptr()), h0.stride(0) if n > 1 else n_cols, n_cols, int(n_terms), float(amp), float(radius), c_vp(out.data_ptr()),
+                out.stride(0) if n > 1 else n_cols, BMS_DEVICE)
+    else:
+        h0 = _lib.as_c16(h0)
+        if out.dtype != np.complex128 or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous complex128 array")
+        args = (vptr(h0), n_cols, n_cols, int(n_terms), float(amp), float(radius), vptr(out), n_cols, BMS_HOST)
+    rc = _lib.load().bms_radius_terms(ctx.handle, dptr(t), n, *args)
+    ctx.check(rc, "bms_radius_terms")
+    return out
+
+
 def spline_derivative(x, y, x_new, order=0, ctx=None):
     """scipy CubicSpline(x, y, axis=0) differentiated (`order` 1..3) or integrated (`order` -1 .. -16; zero at x[0]) and
     evaluated at x_new, for complex y[N, ...]."""

@@ -1,7 +1,9 @@
-"""Sample waveforms with known behaviour (scri/sample_waveforms.py:12-381): the objects the reference's own tests are built on --
-constant and single-mode data, random data, and the single mode proportional to time with its analytically supertranslated
-counterpart (the known answer of tests/test_waveform_grid.py).  Host-side generators; what is done WITH them runs on the GPU.
-(`fake_precessing_waveform` and the finite-radius HDF5 writer of the reference are not restated here.)"""
+"""Sample waveforms with known behaviour (scri/sample_waveforms.py): the objects the reference's own tests are built on --
+constant and single-mode data, random data, the single mode proportional to time with its analytically supertranslated counterpart
+(the known answer of tests/test_waveform_grid.py), and the precessing binary `fake_precessing_waveform` (:383-593) with the
+finite-radius family the reference builds on it (:596-755).  The first group are host-side generators; what is done WITH them runs on
+the GPU.  The precessing waveform is generated on the GPU itself, per time step (bms_precessing_waveform), and may stay there.  Of
+`create_fake_finite_radius_strain_h5file` the in-memory core is here, `fake_finite_radius_waveforms`; the HDF5 file is not written."""
 import math
 import warnings
 from fractions import Fraction
@@ -165,3 +167,130 @@ def single_mode_proportional_to_time_supertranslated(**kwargs):
                     * wigner_3j(ellpp, ell, ellp, 0, -s, s) * wigner_3j(ellpp, ell, ellp, mpp, m, -mp))
             data[:, LM_index(ellp, mp, ell_min)] += -term if (s + mp) % 2 == 1 else term
     return make(data, ctx)
+
+
+def pn_leading_order_amplitude(ell, m, x, mass_ratio=1.0):
+    """Leading-order amplitude of r h / M in PN theory, Eqs. (330) of Blanchet's Living Review (2014), of the mode (ell, m) at
+    x = (orbital angular velocity)^(2/3)  (scri/sample_waveforms.py:536-593)"""
+    if m < 0:
+        return (-1) ** ell * np.conjugate(pn_leading_order_amplitude(ell, -m, x, mass_ratio=mass_ratio))
+    coefficient, power = _pn_amplitude_coefficient(ell, m, mass_ratio)
+    return coefficient * x**power * x
+
+
+def _pn_amplitude_coefficient(ell, m, mass_ratio):
+    """(c, p) with pn_leading_order_amplitude(ell, m, x) = c x^p x for m >= 0: the reference's expression, factor by factor, without x"""
+    f = lambda k: float(math.factorial(k))  # noqa: E731
+    f2 = lambda k: float(math.prod(range(k, 0, -2)))  # noqa: E731  (double factorial of an odd k >= 1)
+    if mass_ratio < 1.0:
+        mass_ratio = 1.0 / mass_ratio
+    nu = mass_ratio / (1 + mass_ratio) ** 2
+    X1 = mass_ratio / (mass_ratio + 1)
+    X2 = 1 / (mass_ratio + 1)
+    sigma = lambda k: X2 ** (k - 1) + (-1) ** k * X1 ** (k - 1)  # noqa: E731
+    if (ell + m) % 2 == 0:
+        amplitude = (
+            ((-1) ** ((ell - m + 2) // 2) / (2 ** (ell + 1) * f((ell + m) // 2) * f((ell - m) // 2) * f2(2 * ell - 1)))
+            * np.sqrt((5 * (ell + 1) * (ell + 2) * f(ell + m) * f(ell - m)) / (ell * (ell - 1) * (2 * ell + 1)))
+            * sigma(ell)
+            * (1j * m) ** ell
+        )
+        power = ell / 2 - 1
+    else:
+        amplitude = (
+            ((-1) ** ((ell - m - 1) // 2) / (2 ** (ell - 1) * f((ell + m - 1) // 2) * f((ell - m - 1) // 2) * f2(2 * ell + 1)))
+            * np.sqrt((5 * (ell + 2) * (2 * ell + 1) * f(ell + m) * f(ell - m)) / (ell * (ell - 1) * (ell + 1)))
+            * sigma(ell + 1)
+            * 1j
+            * (1j * m) ** ell
+        )
+        power = (ell - 1) / 2
+    return 8 * np.sqrt(np.pi / 5) * nu * amplitude, power
+
+
+def _pn_amplitude_tables(ell_max, mass_ratio):
+    """what the mode kernel takes: amplitude of column k = coef[k] x^power[k], l = 2 .. ell_max"""
+    coef, power = [], []
+    for ell in range(2, ell_max + 1):
+        for m in range(-ell, ell + 1):
+            c, p = _pn_amplitude_coefficient(ell, abs(m), mass_ratio)
+            coef.append((-1) ** ell * np.conjugate(c) if m < 0 else c)
+            power.append(p + 1)
+    return np.array(coef, dtype=complex), np.array(power, dtype=float)
+
+
+def fake_precessing_waveform(t_0=-20.0, t_1=20_000.0, dt=0.1, ell_max=8, mass_ratio=2.0, precession_opening_angle=np.pi / 6.0,
+                             precession_opening_angle_dot=None, precession_relative_rate=0.1, precession_nutation_angle=None, inertial=True,
+                             device=False, ctx=None):
+    """Strain waveform with realistic precession effects (scri/sample_waveforms.py:383-533): the lowest-order PN phasing up to a
+    constant merger frequency, leading-order mode amplitudes modulated antisymmetrically in m, a smooth transition to an exponential
+    ringdown, in a frame whose orbital rotation precesses about a cone of growing opening angle and nutates on it, settling after the
+    merger; `inertial` transforms it back to the inertial frame.  The merger is 100 time units before t_1.
+
+    t_0, t_1, dt: the time axis np.arange(t_0, t_1 + 0.99 dt, dt).  mass_ratio: for the phasing and the amplitudes (a ratio below 1 is
+    inverted).  precession_opening_angle [pi/6], precession_opening_angle_dot [2 opening angle / (end of the ringdown transition - t_0)],
+    precession_relative_rate [0.1], precession_nutation_angle [opening angle / 10].
+    Every step is computed on the GPU.  device=True leaves the mode weights there (`is_device_resident`); the values are the same."""
+    from . import _lib, device_series, engine, quaternions
+    from .waveform_modes import WaveformModes
+
+    statement = (f"fake_precessing_waveform(t_0={t_0}, t_1={t_1}, dt={dt}, ell_max={ell_max}, mass_ratio={mass_ratio}, "
+                 f"precession_opening_angle={precession_opening_angle}, precession_opening_angle_dot={precession_opening_angle_dot}, "
+                 f"precession_relative_rate={precession_relative_rate}, precession_nutation_angle={precession_nutation_angle}, "
+                 f"inertial={inertial}, device={device})")
+    if mass_ratio < 1.0:
+        mass_ratio = 1.0 / mass_ratio
+    ell_min = 2
+    t = np.arange(t_0, t_1 + 0.99 * dt, dt)
+    t_merger = t_1 - 100.0
+    i_merger = np.argmin(abs(t - t_merger))
+    if i_merger < 20:
+        raise ValueError(f"Insufficient space between initial time (t={t_merger}) and merger (t={t_0}).")
+    ctx = ctx if ctx is not None else _lib.default_context()
+    coef, power = _pn_amplitude_tables(ell_max, mass_ratio)
+    out = device_series.empty(ctx, (t.size, LM_total_size(ell_min, ell_max))) if device else None
+    data, frame = engine.precessing_waveform(t, ell_max, t_merger, mass_ratio, precession_opening_angle, precession_opening_angle_dot,
+                                             precession_relative_rate, precession_nutation_angle, coef, power, inertial=inertial, out=out, ctx=ctx)
+    W = WaveformModes(t=t, frame=frame, data=np.empty((0, LM_total_size(ell_min, ell_max)), dtype=complex) if device else data, ell_min=ell_min,
+                      ell_max=ell_max, history=["# Called from fake_precessing_waveform"], frameType=Corotating, dataType=h,
+                      r_is_scaled_out=True, m_is_scaled_out=True, constructor_statement=statement, ctx=ctx)
+    if device:
+        W._host, W._dev = None, data
+    if inertial:  # the bookkeeping of to_inertial_frame (scri/rotations.py:106-111, :313-321); the rotation itself ran on the GPU
+        W.frame = quaternions.multiply(W.frame, quaternions.conjugate(W.frame))
+        W.frameType = Inertial
+        W._append_history(f"{W}.to_inertial_frame()")
+    return W
+
+
+def fake_finite_radius_waveforms(n_subleading=3, amp=1.0, t_0=0.0, t_1=3000.0, dt=0.1, r_min=100.0, r_max=600.0, n_radii=24, ell_max=8,
+                                 avg_areal_radius_diff=1.0, mass_ratio=1.0, precession_opening_angle=0.0, device=False, ctx=None, **kwargs):
+    """The finite-radius strain waveforms of `create_fake_finite_radius_strain_h5file` (scri/sample_waveforms.py:596-755) in memory:
+    (Ws, Radii, h0) with h0 = fake_precessing_waveform(t_0, t_1, dt, ell_max, mass_ratio, precession_opening_angle, **kwargs) and, at the
+    areal radii R_i = coordinate radius + avg_areal_radius_diff, coordinate radii equally spaced in 1 / r from r_min to r_max,
+
+        Ws[i].data = h0.data + sum_{n = 1 .. n_subleading} amp R_i^-n exp(i n 50 pi t / N) |h0.data|      (N time steps),
+
+    Radii[i] the constant series R_i; what `_Extrapolate(Ws, Radii, orders)` takes.  The terms are added on the GPU; device=True
+    leaves h0 and every Ws[i] there.  Two differences from the reference are deliberate: the file, the warp to
+    coordinate time, the zero padding and the 1e-14 drift belong to the file writer and are absent; and every radius carries ITS OWN
+    terms on the one h0, as the reference's docstring says -- its loop adds them into h0 in place (and its call drops mass_ratio)."""
+    from . import _lib, device_series, engine
+    from .waveform_modes import WaveformModes
+
+    ctx = ctx if ctx is not None else _lib.default_context()
+    h0 = fake_precessing_waveform(t_0=t_0, t_1=t_1, dt=dt, ell_max=ell_max, mass_ratio=mass_ratio, precession_opening_angle=precession_opening_angle,
+                                  device=True, ctx=ctx, **kwargs)
+    coord_radii = (1 / np.linspace(1 / r_min, 1 / r_max, n_radii)).astype(int)
+    Ws, Radii = [], []
+    for coord_radius in coord_radii:
+        R = float(coord_radius + avg_areal_radius_diff)
+        data = engine.radius_terms(h0.t, h0._dev, n_subleading, amp, R, device_series.empty(ctx, h0._dev.shape), ctx=ctx)
+        W = WaveformModes(t=h0.t, frame=h0.frame, data=np.empty((0, h0.n_modes), dtype=complex), ell_min=h0.ell_min, ell_max=h0.ell_max,
+                          history=list(h0.history) + [f"# finite-radius terms: n_subleading={n_subleading}, amp={amp}, R={R}"], frameType=h0.frameType,
+                          dataType=h0.dataType, r_is_scaled_out=True, m_is_scaled_out=True, ctx=ctx)
+        W._host, W._dev = None, data
+        Ws.append(W if device else W.to_host())
+        Radii.append(np.full(h0.n_times, R))
+    ctx.synchronize()
+    return Ws, Radii, (h0 if device else h0.to_host())

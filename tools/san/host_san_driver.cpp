@@ -1,7 +1,7 @@
 // Host-side sanitizer run (no GPU sanitizer exists on this pool: ASan / UBSan cover what runs on the host).
 // `make -C scri_amd/csrc SAN=1` compiles this file -- which INCLUDES the host side of the engine (engine_*.hip, split by entry family
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
-// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables, the frame integrator and the argument checks of the device frame chain and of the alignment entries over the five BASELINE shapes, 1..8 shards,
+// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain and of the alignment entries, the planner and the per-step math of the precessing sample waveform over the five BASELINE shapes, 1..8 shards,
 // 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
@@ -11,6 +11,7 @@
 #include "../../scri_amd/csrc/engine_blocks.hip"
 #include "../../scri_amd/csrc/engine_frames.hip"
 #include "../../scri_amd/csrc/engine_align.hip"
+#include "../../scri_amd/csrc/engine_sample.hip"
 
 #include <cstdio>
 #include <random>
@@ -262,6 +263,92 @@ void alignment_arguments() {
   REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID);
 }
 
+// The precessing sample waveform (engine_sample.hip): the planner finds the steps the reference's argmin searches find (the expected
+// values are numpy's argmin results for these parameters), refuses what cannot be run, and the per-step math of sample_math.h gives
+// unit rotors and transitions inside their bounds.
+void sample_waveform_plan() {
+  struct Case {
+    double t_0, t_1, dt, mass_ratio;
+    long long n, i0, i1, im, ir;
+  };
+  const Case cases[] = {{-20.0, 400.0, 0.5, 2.0, 841, 625, 635, 640, 680},
+                        {-20.0, 236.0, 1.0, 1.0, 257, 148, 153, 156, 176},
+                        {-20.0, 300.0, 0.25, 0.5, 1281, 850, 870, 880, 960},
+                        {-20.0, 20000.0, 0.1, 2.0, 200201, 199124, 199174, 199200, 199400}};
+  bms_ctx dummy;
+  const int ell_max = 3;
+  std::vector<cplx> coef((size_t)LM_total_size(2, ell_max), cplx{0.25, -0.5});
+  std::vector<double> power(coef.size(), 1.5);
+  for (const Case& cs : cases) {
+    std::vector<double> t((size_t)cs.n);
+    for (long long i = 0; i < cs.n; ++i) t[(size_t)i] = cs.t_0 + (double)i * cs.dt;  // numpy.arange fills start + i * step
+    bms_precessing_params p = {cs.mass_ratio, cs.t_1 - 100.0, 0.5, 0.0, 0.1, 0.0, 1, 1, coef.data(), power.data()};
+    SamplePlan P;
+    REQUIRE(plan_precessing(&dummy, t.data(), cs.n, ell_max, &p, P) == BMS_OK);
+    REQUIRE(P.n == cs.n && P.i0 == cs.i0 && P.i1 == cs.i1 && P.im == cs.im && P.ir == cs.ir);
+    REQUIRE(P.ia() == cs.im + 1 && P.ib() == cs.ir && P.tb0 == t[(size_t)cs.i0] && P.tr1 == t[(size_t)cs.ir]);
+    REQUIRE(P.opening_dot == 2.0 * 0.5 / (t[(size_t)cs.ir] - t[0]) && P.nutation == 0.05);
+    std::vector<SampleMode> modes;
+    REQUIRE(sample_mode_table(&dummy, ell_max, &p, modes) == BMS_OK);
+    REQUIRE((int)modes.size() == 12 && modes[0].twice_power == 3 && modes[0].sign_m == -1 && modes[2].sign_m == 0 && modes[4].sign_m == 1);
+    double last = 0.0;
+    for (long long i = 0; i < cs.n; i += std::max<long long>(1, cs.n / 997)) {
+      const double ti = t[(size_t)i];
+      const double rising = sample_transition(ti, P.tr0, P.tr1, 0.0, 1.0), falling = sample_transition(ti, P.tr0, P.tr1, 1.0, 0.0);
+      REQUIRE(rising >= last && rising <= 1.0 && std::fabs(rising + falling - 1.0) < 1e-15);
+      REQUIRE(sample_transition_slope(ti, P.tr0, P.tr1, 1.0, 0.0) <= 0.0);
+      last = rising;
+      double phi, om;
+      sample_pn_phase(P, ti, phi, om);
+      om = sample_omega(P, i, ti, om);
+      REQUIRE(om > 0.0 && om <= SAMPLE_OMEGA_MERGER);
+      REQUIRE(sample_ringdown(P, i, ti, rising) > 0.0);
+      if (i >= P.i0) phi = -3.0;  // (the integrated phase is the device's)
+      const Quat q = sample_frame(phi, 0.4 * falling, phi / 0.1 * falling, P.nutation * rising);
+      const Quat r = qmul(sample_conj_sqrt(q), sample_conj_sqrt(q));
+      REQUIRE(std::fabs(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z - 1.0) < 1e-14);
+      REQUIRE(std::fabs(r.w - q.w) < 1e-14 && std::fabs(r.x + q.x) < 1e-14 && std::fabs(r.y + q.y) < 1e-14 && std::fabs(r.z + q.z) < 1e-14);
+    }
+  }
+  // refused before anything is staged
+  std::vector<double> t(400);
+  for (int i = 0; i < 400; ++i) t[(size_t)i] = (double)i;
+  bms_precessing_params good = {2.0, 299.0, 0.5, 0.0, 0.1, 0.0, 1, 1, coef.data(), power.data()};
+  SamplePlan P;
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &good, P) == BMS_OK);
+  REQUIRE(plan_precessing(&dummy, nullptr, 400, ell_max, &good, P) == BMS_ERR_INVALID);
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, nullptr, P) == BMS_ERR_INVALID);
+  REQUIRE(plan_precessing(&dummy, t.data(), 0, ell_max, &good, P) == BMS_ERR_INVALID);
+  REQUIRE(plan_precessing(&dummy, t.data(), 23, ell_max, &good, P) == BMS_ERR_INVALID);
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, 1, &good, P) == BMS_ERR_INVALID);
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, MAX_ELL + 1, &good, P) == BMS_ERR_UNSUPPORTED);
+  double bms_precessing_params::*const fields[] = {&bms_precessing_params::mass_ratio,        &bms_precessing_params::t_merger,
+                                                   &bms_precessing_params::opening_angle,     &bms_precessing_params::opening_angle_dot,
+                                                   &bms_precessing_params::relative_rate,     &bms_precessing_params::nutation_angle};
+  for (auto field : fields) {
+    bms_precessing_params bad = good;
+    bad.derive_opening_angle_dot = bad.derive_nutation_angle = 0;
+    bad.*field = std::nan("");
+    REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &bad, P) == BMS_ERR_INVALID);
+  }
+  bms_precessing_params bad = good;
+  bad.t_merger = 10.0;  // the merger is step 10
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &bad, P) == BMS_ERR_INVALID);
+  bad.t_merger = -5.0;  // ... or before the first step
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &bad, P) == BMS_ERR_INVALID);
+  bad.t_merger = 398.0;  // the ringdown transition has no room
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &bad, P) == BMS_ERR_UNSUPPORTED);
+  bad = good, bad.coef = nullptr;
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &bad, P) == BMS_ERR_INVALID);
+  t[200] = t[199];
+  REQUIRE(plan_precessing(&dummy, t.data(), 400, ell_max, &good, P) == BMS_ERR_INVALID);
+  power[3] = 1.25;
+  std::vector<SampleMode> modes;
+  REQUIRE(sample_mode_table(&dummy, ell_max, &good, modes) == BMS_ERR_INVALID);
+  REQUIRE(bms_precessing_waveform(nullptr, t.data(), 400, ell_max, &good, 0, t.data(), 12, BMS_HOST, nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_radius_terms(nullptr, t.data(), 400, t.data(), 1, 1, 3, 1.0, 100.0, t.data(), 1, BMS_HOST) == BMS_ERR_INVALID);
+}
+
 // The slab the named work-space buffers are carved from (bms_ctx_reserve): random grow / release sequences against a brute-force
 // picture of the address range -- regions never overlap, freed neighbours coalesce, what is free plus what is held is the slab.
 void slab_allocator() {
@@ -325,6 +412,7 @@ int main() {
   frame_integration();
   frame_chain_arguments();
   alignment_arguments();
+  sample_waveform_plan();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
