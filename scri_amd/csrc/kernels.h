@@ -227,6 +227,9 @@ struct SplineEval {
   int step = 0;          // rows a tile advances: 0 = automatic (64 with `side`, 61 without), 61 or 64 (the context's GEMM_EVAL_STEP option)
 };
 long long zgemm3m_eval_side_rows(long long M);
+// Preconditions (hipErrorInvalidValue otherwise): M >= 4; lda >= 2 K (the rows of A do not overlap: the kernel's range check on A takes
+// everything from a row's K entries to the next row for out of range); 64 rows of A and 8 rows + 64 columns of B span less than 2^31 bytes
+// (32-bit byte offsets behind buffer descriptors).  B holds 8 ceil(K / 8) rows (the rows >= K are read, and multiplied by zeros of A).
 hipError_t launch_zgemm3m_eval(hipStream_t stream, const double* A, long long lda, const double* B, long long ldb, long long M, int N,
                                int K, const double* col_scale, const SplineEval& e);
 

@@ -181,14 +181,15 @@ struct EvalFromLds {
   __device__ __forceinline__ lds_cdp tab(int jl) const { return t_lds + 16 * jl; }
   __device__ __forceinline__ bool has(int i) const { return (unsigned)(i - i_a) < (unsigned)E_XS; }
   __device__ __forceinline__ double samp(int i) const { return xs_lds[i - i_a]; }
-  // first i with u_eval(i) >= y, or -1 if the window cannot tell
-  __device__ __forceinline__ int first(double y, double sa, double sb, double tt, int n_i) const {
+  // first i with u_eval(i) >= y, or -1 if the window cannot tell; rinv = 1 / (1 + sa) (the column's, formed once by the caller)
+  __device__ __forceinline__ int first(double y, double sa, double sb, double tt, double rinv, int n_i) const {
     int lo = 0, hi = E_XS;
     if (inv_dx > 0.0) {
       // On a (nearly) uniform axis the row follows from the abscissa: u_eval(i) >= y <=> x_i >= (y - sb + sa tt) / (1 + sa).  The
       // guess is CHECKED against its two neighbours' exact u_eval and only narrows the search: right or one off on the benchmark
-      // axes, where it replaces nine dependent LDS round trips (and ~90 vector instructions) by two.
-      const double z = (y - (sb - sa * tt)) / (1.0 + sa);
+      // axes, where it replaces nine dependent LDS round trips (and ~90 vector instructions) by two.  Only the guess sees the
+      // rounding of rinv: a full division here was five instructions of the divide sequence and eight fused multiply-adds.
+      const double z = (y - (sb - sa * tt)) * rinv;
       const double gf = (z - xs_lds[0]) * inv_dx;
       int g = gf < 0.0 ? 0 : (gf > (double)(E_XS - 1) ? E_XS - 1 : (int)gf);
       const double xa = xs_lds[g], xb = xs_lds[g + 1 < E_XS ? g + 1 : E_XS - 1];
@@ -201,15 +202,19 @@ struct EvalFromLds {
         if (xc + (sa * (xc - tt) + sb) < y) lo = hi = g;
       }
     }
+    // (the steps are predicated per lane, never skipped: where the checked guess has settled every lane of the wave, a branch on the
+    // scalar unit takes the wave past all nine)
+    if (__builtin_amdgcn_ballot_w64(lo < hi) != 0) {
 #pragma unroll
-    for (int st = 0; st < 9; ++st) {  // E_XS = 2^8: 257 possible answers
-      const int mid = lo < hi ? (lo + hi) >> 1 : (lo < E_XS ? lo : E_XS - 1);  // (converged: any valid entry, the comparison changes nothing)
-      const double xi = xs_lds[mid];
-      if (lo < hi) {
-        if (xi + (sa * (xi - tt) + sb) < y)
-          lo = mid + 1;
-        else
-          hi = mid;
+      for (int st = 0; st < 9; ++st) {  // E_XS = 2^8: 257 possible answers
+        const int mid = lo < hi ? (lo + hi) >> 1 : (lo < E_XS ? lo : E_XS - 1);  // (converged: any valid entry, the comparison changes nothing)
+        const double xi = xs_lds[mid];
+        if (lo < hi) {
+          if (xi + (sa * (xi - tt) + sb) < y)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
       }
     }
     // inside the window the answer is exact; at its edges only if the window ends where the rows do
@@ -263,10 +268,10 @@ __device__ __forceinline__ void wave_min_max(double& mn, double& mx) {
 
 // The windows [fa, fb) (relative to kT, the knot of the caller's row 0) of one column; win(fl, q) returns C[kT + fl + q][p];
 // lds: the staged copies, if from_lds (by value: a struct whose address is taken lives in scratch memory, and a scratch load in
-// the loop waits, through vmcnt, for the previous turn's sample to reach memory).
+// the loop waits, through vmcnt, for the previous turn's sample to reach memory).  rinv = 1 / (1 + sa).
 template <class WIN>
-__device__ __forceinline__ void eval_windows(const EvalArgs& ev, const bool from_lds, const EvalFromLds lds, int col, double sa, double sb, long long kT,
-                                             int fa, int fb, WIN win) {
+__device__ __forceinline__ void eval_windows(const EvalArgs& ev, const bool from_lds, const EvalFromLds lds, int col, double sa, double sb, double rinv,
+                                             long long kT, int fa, int fb, WIN win) {
   const long long n = ev.n;
   {
     const long long cap = n - 3 - kT;  // window starts are 0 .. n - 4
@@ -288,7 +293,7 @@ __device__ __forceinline__ void eval_windows(const EvalArgs& ev, const bool from
   if (kT + m.jl == 0)
     i = 0;
   else if (from_lds)
-    i = lds.first(lds.knot(m.jl), m.sa, m.sb, m.tt, m.n_i);
+    i = lds.first(lds.knot(m.jl), m.sa, m.sb, m.tt, rinv, m.n_i);
   if (i < 0) {
     if (from_lds && ev.stats) atomicAdd(ev.stats + 1, 1ull);
     i = eval_lower_bound(bp, m.n_i, m.sa, m.sb, m.tt, ev.x[kT + m.jl], kT + m.jl - ev.i_lo, ev.search_halfwidth);
@@ -309,14 +314,16 @@ __device__ __forceinline__ void eval_windows(const EvalArgs& ev, const bool from
 template <int ROW_STEP>
 __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __restrict__ A, long long lda, const double* __restrict__ B,
                                                              long long ldb, long long M, int N, int K, int nbm, int nbn,
-                                                             int st_rows_log2, const double* __restrict__ col_scale, EvalArgs ev) {
+                                                             int st_rows_log2, unsigned nsn_magic, const double* __restrict__ col_scale, EvalArgs ev) {
   __shared__ __attribute__((aligned(16))) double2 lds[2 * E_ASZ + 2 * E_BSZ];
   static_assert(sizeof(double2) * (2 * E_ASZ + 2 * E_BSZ) >= sizeof(double2) * E_BM * E_PC, "the parked half tile must fit the operand LDS");
   __shared__ __attribute__((aligned(16))) double t_lds[64 * 16];
   __shared__ __attribute__((aligned(16))) double xk_lds[64];
   __shared__ __attribute__((aligned(16))) double xs_lds[E_XS];
   __shared__ __attribute__((aligned(16))) double2 sk_lds[E_BN];  // (skew_a, skew_b) of the tile's columns
-  __shared__ double win_lds[4];  // smallest / largest skew of the tile (eval_tile_window); 1 / mean step of its knots; of its staged abscissae
+  __shared__ __attribute__((aligned(16))) double rc_lds[E_BN];   // 1 / (1 + skew_a): the divisor of the search's first guess depends on the column alone
+  __shared__ double win_lds[1];  // 1 / (mean step of the staged abscissae), 0 without a guess
+  __shared__ int wini_lds[2];    // the tile's window of output rows: its first row i_a; whether every sample lies in it (from_lds)
   double2* As = lds;
   double2* Bs = lds + 2 * E_ASZ;
 
@@ -328,8 +335,11 @@ __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __re
   const int nsn = (nbn + (1 << st_cols_log2) - 1) >> st_cols_log2;
   const int S = (q >> 6) * 8 + xcd;
   const int r = q & 63;
-  const int bm = ((S / nsn) << st_rows_log2) + (r >> st_cols_log2);
-  const int bn = ((S % nsn) << st_cols_log2) + (r & ((1 << st_cols_log2) - 1));
+  // S / nsn and S % nsn on the scalar unit: nsn_magic = floor(2^32 / nsn) (the launcher's) gives the quotient or one less
+  unsigned s_q = __umulhi((unsigned)S, nsn_magic), s_r = (unsigned)S - s_q * (unsigned)nsn;
+  if (s_r >= (unsigned)nsn) ++s_q, s_r -= (unsigned)nsn;
+  const int bm = (int)(s_q << st_rows_log2) + (r >> st_cols_log2);
+  const int bn = (int)(s_r << st_cols_log2) + (r & ((1 << st_cols_log2) - 1));
   if (bm >= nbm || bn >= nbn) return;
   const long long m0 = (long long)bm * ROW_STEP;
   const int n0 = bn * E_BN;
@@ -351,16 +361,31 @@ __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __re
     const int col = n0 + tid < N ? n0 + tid : N - 1;
     const double sa = ev.skew_a ? ev.skew_a[col] : 0.0, sb = ev.skew_b ? ev.skew_b[col] : 0.0;
     sk_lds[tid] = double2{sa, sb};
+    rc_lds[tid] = 1.0 / (1.0 + sa);
+    double mn = 0.0, mx = 0.0;
     if (!eval_launch_wide_window(ev)) {
       // smallest and largest time skew of the tile's columns over its knots (affine in the knot: the ends decide)
       const double s0 = sa * (ev.x[kT] - ev.tt) + sb, s1 = sa * (ev.x[kT + rows_valid - 1] - ev.tt) + sb;
-      double mn = s0 < s1 ? s0 : s1, mx = s0 < s1 ? s1 : s0;
+      mn = s0 < s1 ? s0 : s1, mx = s0 < s1 ? s1 : s0;
       wave_min_max(mn, mx);
-      if (tid == 0) win_lds[0] = mn, win_lds[1] = mx;
     }
-    if (tid == 0) {  // the tile's own mean step (a graded axis: the launch's mean can be several times off)
+    // The window is the same for the whole workgroup: one lane places it (its ceil, floor and two fp64 divisions were issued by all
+    // four waves) and hands it over in LDS, behind the barrier that follows the first operand stores.
+    if (tid == 0) {
+      // the tile's own mean step (a graded axis: the launch's mean can be several times off)
       const double span = ev.x[kT + rows_valid - 1] - ev.x[kT];
-      win_lds[2] = (rows_valid > 1 && span > 0.0) ? (double)(rows_valid - 1) / span : ev.inv_dx;
+      const double inv_dx_tile = (rows_valid > 1 && span > 0.0) ? (double)(rows_valid - 1) / span : ev.inv_dx;
+      int ia;
+      const bool ok = eval_tile_window(ev, kT, (int)rows_valid, n_i, mn, mx, inv_dx_tile, &ia);
+      double inv_dx_win = 0.0;
+      if (ok) {  // mean step of the window of abscissae staged below: the first guess of a sample's row (EvalFromLds::first)
+        const int i_b = ia + E_XS - 1 < n_i - 1 ? ia + E_XS - 1 : n_i - 1;
+        const double wspan = ev.x[ev.i_lo + i_b] - ev.x[ev.i_lo + ia];
+        inv_dx_win = (ev.inv_dx > 0.0 && i_b > ia && wspan > 0.0) ? (double)(i_b - ia) / wspan : 0.0;
+      } else if (ev.stats)
+        atomicAdd(ev.stats, 1ull);
+      win_lds[0] = inv_dx_win;
+      wini_lds[0] = ia, wini_lds[1] = ok ? 1 : 0;
     }
   }
 
@@ -370,50 +395,52 @@ __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __re
 #pragma unroll
     for (int j = 0; j < 2; ++j) p1[i][j] = p2[i][j] = p3[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
 
+  // The operands of a turn come through buffer descriptors that the scalar unit moves on from turn to turn (base + 8 k-steps, for A
+  // the bytes left), with byte offsets per lane that never change: four requests back to back, no branch and no vector address
+  // arithmetic in the loop.  (Behind predicated pointer loads the compiler had lost track of the counters and made every turn wait
+  // for its A operands before it asked for B.)  A's descriptor ends with the K entries of the tile's last row inside M, so the
+  // range check returns the zeros of the rows >= M; the lanes whose k-step lies beyond K in the last turn ask past its end there.
+  // B's covers what a turn reads: eight rows (below 8 nk: the caller's padding) of the tile's 64 columns.
   const int a_row = tid >> 3, a_k = tid & 7;
   const int b_row = tid >> 6, b_col = tid & 63;
-  const double* a_ptr = A + (m0 + a_row) * lda + 2 * a_k;
-  const double* b_ptr = B + (long long)b_row * ldb + 2 * (n0 + b_col);
-  const bool a_ok0 = (m0 + a_row) < M, a_ok1 = (m0 + a_row + 32) < M;
-  const double2 zero2 = {0.0, 0.0};
-  double2 ra0, ra1, rb0, rb1;
   const int nk = (K + E_KC - 1) / E_KC;
+  constexpr int E_OOB = 0x7ffffff0;  // (beyond any descriptor of this kernel: the launcher bounds the tile's bytes)
+  const double* a_base = A + m0 * lda;
+  const double* b_base = B + 2LL * n0;
+  const long long a_bytes = ((rows_valid - 1) * lda + 2LL * K) * 8;
+  const int b_bytes = (int)(((E_KC - 1) * ldb + 2LL * E_BN) * 8);
+  const int a_off0 = (int)(a_row * lda * 8) + 16 * a_k, a_off1 = a_off0 + (int)(32 * lda * 8);
+  const int b_off0 = (int)(b_row * ldb * 8) + 16 * b_col, b_off1 = b_off0 + (int)(4 * ldb * 8);
+  const bool k_tail = (nk - 1) * E_KC + a_k >= K;
+  const int a_off0_last = k_tail ? E_OOB : a_off0, a_off1_last = k_tail ? E_OOB : a_off1;
+  double2 ra0, ra1, rb0, rb1;
+  const auto load_global = [&](int kt, bool last) __attribute__((always_inline)) {
+    const auto a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(a_base + 2 * E_KC * kt), 0, (int)(a_bytes - 16LL * E_KC * kt), 0x00020000);
+    const auto b_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(b_base + (long long)kt * E_KC * ldb), 0, b_bytes, 0x00020000);
+    ra0 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(a_rs, last ? a_off0_last : a_off0, 0, 0));
+    ra1 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(a_rs, last ? a_off1_last : a_off1, 0, 0));
+    rb0 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_off0, 0, 0));
+    rb1 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_off1, 0, 0));
+  };
+  double2* const as_w0 = As + a_row * E_PA + a_k;
+  double2* const bs_w0 = Bs + b_row * E_PB + b_col;
+  const auto store_lds = [&](int buf) __attribute__((always_inline)) {
+    double2* as_w = as_w0 + buf * E_ASZ;
+    as_w[0] = ra0;
+    as_w[32 * E_PA] = ra1;
+    double2* bs_w = bs_w0 + buf * E_BSZ;
+    bs_w[0] = rb0;
+    bs_w[4 * E_PB] = rb1;
+  };
 
-#define E_LOAD_GLOBAL(kt)                                                                      \
-  {                                                                                            \
-    const int k0 = (kt)*E_KC;                                                                  \
-    const bool kok = (k0 + a_k) < K;                                                           \
-    ra0 = (a_ok0 && kok) ? *reinterpret_cast<const double2*>(a_ptr + 2 * k0) : zero2;          \
-    ra1 = (a_ok1 && kok) ? *reinterpret_cast<const double2*>(a_ptr + 32 * lda + 2 * k0) : zero2; \
-    const double* bp_ = b_ptr + (long long)k0 * ldb;                                           \
-    rb0 = *reinterpret_cast<const double2*>(bp_);                                              \
-    rb1 = *reinterpret_cast<const double2*>(bp_ + 4 * ldb);                                    \
-  }
-#define E_STORE_LDS(buf)                                        \
-  {                                                             \
-    double2* as_w = As + (buf)*E_ASZ + a_row * E_PA + a_k;      \
-    as_w[0] = ra0;                                              \
-    as_w[32 * E_PA] = ra1;                                      \
-    double2* bs_w = Bs + (buf)*E_BSZ + b_row * E_PB + b_col;    \
-    bs_w[0] = rb0;                                              \
-    bs_w[4 * E_PB] = rb1;                                       \
-  }
-
-  E_LOAD_GLOBAL(0);
-  E_STORE_LDS(0);
+  load_global(0, nk == 1);
+  store_lds(0);
   __syncthreads();
   // (behind the first barrier: the tile's skew range is known to every thread; the copies requested here are in LDS long before the
   // K loop, whose every turn ends in a barrier, is through)
-  int i_a;
-  const bool wide = eval_launch_wide_window(ev);
-  const bool from_lds = eval_tile_window(ev, kT, (int)rows_valid, n_i, wide ? 0.0 : win_lds[0], wide ? 0.0 : win_lds[1], win_lds[2], &i_a);
-  if (!from_lds && tid == 0 && ev.stats) atomicAdd(ev.stats, 1ull);
+  const int i_a = __builtin_amdgcn_readfirstlane(wini_lds[0]);
+  const bool from_lds = __builtin_amdgcn_readfirstlane(wini_lds[1]) != 0;
   if (from_lds) {
-    if (tid == 0) {  // mean step of the window of abscissae staged below: the first guess of a sample's row (EvalFromLds::first)
-      const int i_b = i_a + E_XS - 1 < n_i - 1 ? i_a + E_XS - 1 : n_i - 1;
-      const double span = ev.x[ev.i_lo + i_b] - ev.x[ev.i_lo + i_a];
-      win_lds[3] = (ev.inv_dx > 0.0 && i_b > i_a && span > 0.0) ? (double)(i_b - i_a) / span : 0.0;
-    }
     {
       long long row = tid >> 2;
       if (row > rows_valid - 1) row = rows_valid - 1;
@@ -440,11 +467,13 @@ __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __re
   const bool narrow = n0 + 32 >= N;
   const int rbase = narrow ? wave * 16 : wm * 32, cbase = narrow ? 0 : wn * 32;
   const bool wave_has_columns = n0 + cbase < N;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) E_LOAD_GLOBAL(kt + 1);
-    const double2* as = As + buf * E_ASZ + (rbase + fi) * E_PA + fk;
-    const double2* bs = Bs + buf * E_BSZ + fk * E_PB + cbase + fi;
+  const double2* const as_r0 = As + (rbase + fi) * E_PA + fk;
+  const double2* const bs_r0 = Bs + fk * E_PB + cbase + fi;
+  // one turn: ask for the operands of the next (`more`; `last`: that one is turn nk - 1), the products of this one from buffer `buf`
+  const auto turn = [&](int kt, int buf, bool more, bool last) __attribute__((always_inline)) {
+    if (more) load_global(kt + 1, last);
+    const double2* as = as_r0 + buf * E_ASZ;
+    const double2* bs = bs_r0 + buf * E_BSZ;
 #pragma unroll
     for (int kk = 0; wave_has_columns && kk < E_KC / 4; ++kk) {
       const double2 a0 = as[kk * 4];
@@ -467,11 +496,17 @@ __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __re
         p3[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa1, sb1, p3[1][1], 0, 0, 0);
       }
     }
-    if (kt + 1 < nk) E_STORE_LDS(buf ^ 1);
+    if (more) store_lds(buf ^ 1);
     __syncthreads();
+  };
+  // Two turns per trip, so that the buffer of each is a constant and the LDS addresses are immediate offsets; the turns that ask
+  // for the last k-steps, or for nothing, follow one by one.
+  int kt = 0;
+  for (; kt + 3 < nk; kt += 2) {
+    turn(kt, 0, true, false);
+    turn(kt + 1, 1, true, false);
   }
-#undef E_LOAD_GLOBAL
-#undef E_STORE_LDS
+  for (; kt < nk; ++kt) turn(kt, kt & 1, kt + 1 < nk, kt + 2 == nk);
 
   unsigned long long tr_t1 = 0;
   if (EV_TRACE(ev)) tr_t1 = __builtin_readcyclecounter();
@@ -518,9 +553,9 @@ __global__ __launch_bounds__(256, 3) void zgemm3m_eval_kernel(const double* __re
       if (fb > f_own) fb = f_own;
       if (fb > f_rows) fb = f_rows;
       const auto win = [&](int fl, int qq) { return Cs[(fl + qq) * E_PC + ec]; };
-      const EvalFromLds src{(lds_cdp)t_lds, (lds_cdp)xk_lds, (lds_cdp)xs_lds, i_a, from_lds ? win_lds[3] : 0.0};
+      const EvalFromLds src{(lds_cdp)t_lds, (lds_cdp)xk_lds, (lds_cdp)xs_lds, i_a, win_lds[0]};
       const double2 sk = sk_lds[h * 32 + ec];
-      eval_windows(ev, from_lds, src, col, sk.x, sk.y, kT, fa, fb, win);
+      eval_windows(ev, from_lds, src, col, sk.x, sk.y, rc_lds[h * 32 + ec], kT, fa, fb, win);
     }
     if (h == 0) __syncthreads();
   }
@@ -551,6 +586,7 @@ __global__ __launch_bounds__(64) void spline_straddle_eval_kernel(int N, int n_r
   const long long k_last = ev.g0 + M - 1;
   const int colc = col < N ? col : N - 1;
   const double sa_t = ev.skew_a ? ev.skew_a[colc] : 0.0, sb_t = ev.skew_b ? ev.skew_b[colc] : 0.0;
+  const double rinv_t = 1.0 / (1.0 + sa_t);
   double smin = 0.0, smax = 0.0;
   if (!eval_launch_wide_window(ev)) {
     // skew range of the block's 64 columns over the six knots of the boundary
@@ -609,13 +645,15 @@ __global__ __launch_bounds__(64) void spline_straddle_eval_kernel(int N, int n_r
   }
   const auto win = [&](int fl, int qq) { return w_lds[fl + qq][tid]; };
   const EvalFromLds src{(lds_cdp)t_lds, (lds_cdp)xk_lds, (lds_cdp)xs_lds, i_a, inv_dx_win};
-  eval_windows(ev, from_lds, src, col, sa_t, sb_t, kT, 0, fb, win);
+  eval_windows(ev, from_lds, src, col, sa_t, sb_t, rinv_t, kT, 0, fb, win);
 }
 
 hipError_t launch_zgemm3m_eval(hipStream_t stream, const double* A, long long lda, const double* B, long long ldb, long long M, int N,
                                int K, const double* col_scale, const SplineEval& e) {
   if (M <= 0 || N <= 0 || e.i_hi <= e.i_lo) return hipSuccess;
   if (M < 4) return hipErrorInvalidValue;
+  // (the kernel addresses a tile's operands with 32-bit byte offsets behind buffer descriptors; the rows of A must not overlap)
+  if (lda < 2LL * K || lda * 8 * E_BM >= 0x7ffffff0LL || ldb * 8 * E_KC + 16LL * E_BN >= 0x7ffffff0LL) return hipErrorInvalidValue;
   EvalArgs ev;
   ev.table = e.table, ev.x = e.x, ev.skew_a = e.skew_a, ev.skew_b = e.skew_b, ev.tt = e.tt, ev.g0 = e.g0, ev.n = e.n_knots;
   ev.i_lo = e.i_lo, ev.i_hi = e.i_hi, ev.out = e.out, ev.ldo = e.ldo, ev.search_halfwidth = e.search_halfwidth;
@@ -637,6 +675,8 @@ hipError_t launch_zgemm3m_eval(hipStream_t stream, const double* A, long long ld
   const int sr = 1 << st_rows_log2, sc = 64 >> st_rows_log2;
   const long long n_super = (long long)((nbm + sr - 1) / sr) * ((nbn + sc - 1) / sc);
   const long long grid = ((n_super + 7) / 8) * 8 * 64;
+  const unsigned nsn = (unsigned)((nbn + sc - 1) / sc);
+  const unsigned nsn_magic = nsn == 1 ? 0xffffffffu : (unsigned)(0x100000000ULL / nsn);
   ev.trace = nullptr;
 #if BMS_PROBES
   const char* trace_path = BMS_PROBE_ENV("SCRI_AMD_GEMM_EVAL_TRACE");
@@ -647,10 +687,10 @@ hipError_t launch_zgemm3m_eval(hipStream_t stream, const double* A, long long ld
 #endif
   if (step == 61)
     hipLaunchKernelGGL(zgemm3m_eval_kernel<61>, dim3((unsigned)grid), dim3(256), 0, stream, A, lda, B, ldb, M, N, K, nbm, nbn, st_rows_log2,
-                       col_scale, ev);
+                       nsn_magic, col_scale, ev);
   else {
     hipLaunchKernelGGL(zgemm3m_eval_kernel<64>, dim3((unsigned)grid), dim3(256), 0, stream, A, lda, B, ldb, M, N, K, nbm, nbn, st_rows_log2,
-                       col_scale, ev);
+                       nsn_magic, col_scale, ev);
     // one block per (tile boundary, column panel), panels fastest, in a one-dimensional grid (a grid's y extent stops at 65 535:
     // a chunk of more than 4.19 M rows has more boundaries than that)
     const long long n_straddle = (long long)(nbm - 1) * nbn;
