@@ -2,7 +2,8 @@
 // macros, the tables of one transformation, and the helpers the entry-point families share.  The C ABI is include/scri_amd.h; this
 // file is not installed.  The engine is split by entry family:
 //   engine_context.hip   context, work-space slab, route options, page-locked host memory, timing            (bms_ctx_*, bms_host_*)
-//   engine_tables.hip    planners: per-direction tables, output window, shard plan, time-axis checks, analysis / synthesis plans
+//   engine_tables.hip    planners: per-direction tables, output window, shard plan, time-axis checks, analysis / synthesis plans; the set-up
+//                        steps both transforms take (knot tables, chunk plan, rotation into the grid frame, evaluating product's arguments)
 //   engine_rotate.hip    rotations of the decomposition basis                                               (bms_rotate_*, bms_wigner_D)
 //   engine_modes.hip     WaveformModes transform: one call, shard, pipelined, series, grid                   (bms_transform_modes*, ...)
 //   engine_abd.hip       AsymptoticBondiData transform                                                       (bms_transform_abd*)
@@ -582,6 +583,28 @@ inline void begin_setup_reuse(bms_ctx* c) {
 }
 // the `reuse` argument of device_pixel_tables for a transformation under this shard description: never 0, one value per column part
 inline int reuse_tag(const bms_shard* sh) { return 1 + ((sh && sh->col_parts > 1 && sh->col_part >= 0) ? 1 + (sh->col_part & 0x7fff) + ((sh->col_parts & 0x7fff) << 15) : 0); }
+// ---- steps the two transform implementations share (transform_modes_impl, transform_abd_impl), each called where its block stood
+struct KnotTables {  // the knot tables of one call: slope form (d_tab) or B-spline form (d_bstab, d_bsfwd), indexed by GLOBAL knot number
+  double* d_x = nullptr;
+  SplineTable* d_tab = nullptr;
+  BsplineTable* d_bstab = nullptr;
+  BsplineForward* d_bsfwd = nullptr;
+  bool times_ahead = false;  // on their way since the top of the call (knot_tables_ahead)
+  bool axis_known = false;   // the axis is one the context has tables for AND has walked: neither is done again
+};
+struct ChunkPlan {
+  int64_t chunk = 0;  // output samples per pass of the chunk loop
+  int spline_tile = SPLINE_TILE;
+};
+BMS_INTERNAL int knot_tables_ahead(bms_ctx* c, const double* t, int64_t n, const bms_shard* sh, int64_t t_lo, int64_t t_hi, KnotTables& kt);
+BMS_INTERNAL int knot_tables_of_call(bms_ctx* c, const double* t, int64_t n, int64_t t_lo, int64_t t_hi, int64_t row0, int64_t rows_avail, bool bsg, PieceTables* shared, KnotTables& kt);
+BMS_INTERNAL int refuse_sharded_graded_axis(bms_ctx* c, bool regular_mesh, const bms_shard* sh, int64_t n);
+BMS_INTERNAL int plan_chunks(bms_ctx* c, uint64_t ws_limit, double bytes_per_row, int64_t n_new, bool regular_mesh, int64_t n, const char* how_many, int n_cols, ChunkPlan& P);
+BMS_INTERNAL int chunk_rows(bms_ctx* c, const PixelTables& T, const double* t, int64_t n, bool regular_mesh, int64_t c0, int64_t c1, int64_t row0, int64_t rows_avail, int64_t& g0, int64_t& g1);
+BMS_INTERNAL int rotate_into_grid_frame(bms_ctx* c, const bms_transformation* tr, double* data, int64_t rows, int64_t ld, int ell_min, int ell_max);
+BMS_INTERNAL int rotated_input_in_grid_frame(bms_ctx* c, const bms_transformation* tr, const char* name, int mem, const double** d_data, int64_t rows, int64_t ld, int ell_min, int ell_max);
+BMS_INTERNAL int spline_eval_args(bms_ctx* c, const KnotTables& kt, const PixelTables& T, int cA, int cB, const double* t, int64_t n, int64_t g0, int64_t g1, int64_t c0, int64_t c1,
+                                  double* out, long long ldo, long long ldg, SplineEval& ev);
 BMS_INTERNAL void time_axis_commit(bms_ctx* c, bool walked, bool regular);
 BMS_INTERNAL void drop_setup_caches(bms_ctx* c);
 BMS_INTERNAL bool cached_window(bms_ctx* c, bool abd, int64_t& i_lo, int64_t& i_hi);

@@ -28,20 +28,10 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
   // The knot tables go first, as in the WaveformModes route: an axis the context has kept tables for (TimeAxisCache, engine.h) needs
   // neither them nor the walk again.  Speculative on a new axis: tables of samples the walk then rejects are never used nor kept.
   begin_setup_reuse(c);
-  double* d_x = nullptr;
-  SplineTable* d_tab = nullptr;
-  BsplineTable* d_bstab = nullptr;
-  BsplineForward* d_bsfwd = nullptr;
-  const bool times_ahead = n >= 8 && !c->async_pieces && !c->opt.on(OPT_NO_BSPLINE) &&
-                           (!sh || (sh->data_row0 >= 0 && sh->data_rows >= 0 && sh->data_row0 + sh->data_rows <= n));
-  bool axis_known = false;
-  if (times_ahead) {
-    const int64_t r0 = sh ? sh->data_row0 : 0, r1 = r0 + (sh ? sh->data_rows : n);
-    if ((rc = upload_times_bspline(c, u, n, t_lo, t_hi, r0, r1, &d_x, &d_bstab, &d_bsfwd))) return rc;
-    axis_known = c->tcache.hit && c->tcache.walked;
-  }
+  KnotTables kt;
+  if ((rc = knot_tables_ahead(c, u, n, sh, t_lo, t_hi, kt))) return rc;
   // (scipy's CubicSpline, the interpolant of this flavour, takes 2 and 3 samples too: line and parabola)
-  if (axis_known) {
+  if (kt.axis_known) {
     rc = validate_transformation(c, n, u, tr, 2);
     regular_mesh = c->tcache.regular;
   } else
@@ -50,10 +40,7 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
   const bool short_series = n < 4;
   if (short_series && sh && !(sh->data_row0 == 0 && sh->data_rows == n && sh->col_parts <= 1))
     return fail(c, BMS_ERR_UNSUPPORTED, "a series of %lld samples cannot be sharded", (long long)n);
-  if (!regular_mesh && sh && !(sh->data_row0 == 0 && sh->data_rows == n && sh->col_parts <= 1))
-    return fail(c, BMS_ERR_UNSUPPORTED,
-                "the time steps vary by more than 1e3 within 48 samples: such a series is transformed with exact untiled spline "
-                "recurrences, which a time shard cannot provide");
+  if ((rc = refuse_sharded_graded_axis(c, regular_mesh, sh, n))) return rc;
   if (ell_max < 0 || tr->ell_max_out < 0) return fail(c, BMS_ERR_INVALID, "bad ell_max");
   if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
   static const int spins[6] = {2, 1, 0, -1, -2, 2};  // psi0..psi4, sigma
@@ -141,20 +128,9 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
   if (short_series) {
     void* vp;
     if ((rc = upload(c, "times", u, 8 * (size_t)n, &vp))) return rc;
-    d_x = (double*)vp;
-  } else if (bsg && shared && shared->times_valid) {
-    d_x = shared->d_x, d_bstab = shared->d_bstab, d_bsfwd = shared->d_bsfwd;
-  } else if (bsg && shared) {
-    rc = upload_times_bspline(c, u, n, 0, n, 0, n, &d_x, &d_bstab, &d_bsfwd);
-    shared->d_x = d_x, shared->d_bstab = d_bstab, shared->d_bsfwd = d_bsfwd;
-    shared->times_valid = rc == BMS_OK;
-  } else if (bsg && times_ahead)
-    rc = BMS_OK;  // (on their way since the top of the call)
-  else if (bsg)
-    rc = upload_times_bspline(c, u, n, t_lo, t_hi, row0, row0 + rows_avail, &d_x, &d_bstab, &d_bsfwd);
-  else
-    rc = upload_times(c, u, n, t_lo, t_hi, row0, row0 + rows_avail, &d_x, &d_tab);
-  if (rc) return rc;
+    kt.d_x = (double*)vp;
+  } else if ((rc = knot_tables_of_call(c, u, n, t_lo, t_hi, row0, rows_avail, bsg, shared, kt)))
+    return rc;
 
   const long long P2 = 2LL * n_pix, ldg = round_up(P2, 16), ldb = round_up(2LL * n_cols, 128);
   const int K = 2 * nm;
@@ -207,26 +183,12 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
     if ((rc = dev_buf_t(c, "abd_Af", (size_t)6 * rows_avail * ld_af, &d_Af))) return rc;
     for (int f = 0; f < 6; ++f)
       TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, d_raw + (size_t)f * rows_avail * nm * 2, 2LL * nm, nm, d_Af + (size_t)f * rows_avail * ld_af,
-                                                                    ld_af, row0, rows_avail, n, d_bsfwd, SPLINE_TILE, SPLINE_HALO, 1));
-    const double* q = tr->frame_rotation;
-    if (!(q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) {
-      const double sp[4] = {q[0], q[3], q[2], q[1]};  // (w + i z, y + i x); the constant column stays
-      if ((rc = rotate_impl(c, d_Af, BMS_DEVICE, 6 * rows_avail, ld_af / 2, 0, ell_max, sp, false, false))) return rc;
-    }
+                                                                    ld_af, row0, rows_avail, n, kt.d_bsfwd, SPLINE_TILE, SPLINE_HALO, 1));
+    if ((rc = rotate_into_grid_frame(c, tr, d_Af, 6 * rows_avail, ld_af / 2, 0, ell_max))) return rc;  // (the constant column stays)
   } else if (sep) {
     // the six fields as seen from the rotated frame, sYlm(F G) = sum_m' D_{m m'}(F) sYlm'(G): [6][rows][nm] is one series of
     // 6 x rows steps for the rotation kernel -- in place in the staging copy of a host caller, in a copy of device data
-    const double* q = tr->frame_rotation;
-    if (!(q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) {
-      const double sp[4] = {q[0], q[3], q[2], q[1]};  // (w + i z, y + i x)
-      double* d_copy = const_cast<double*>(d_raw);
-      if (mem == BMS_DEVICE) {
-        if ((rc = dev_buf_t(c, "abd_rot_in", (size_t)6 * rows_avail * nm * 2, &d_copy))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(d_copy, d_raw, (size_t)6 * rows_avail * nm * 16, hipMemcpyDeviceToDevice, S));
-        d_raw = d_copy;
-      }
-      if ((rc = rotate_impl(c, d_copy, BMS_DEVICE, 6 * rows_avail, nm, 0, ell_max, sp, false, false))) return rc;
-    }
+    if ((rc = rotated_input_in_grid_frame(c, tr, "abd_rot_in", mem, &d_raw, 6 * rows_avail, nm, 0, ell_max))) return rc;
   }
 
   if (n_pix == 0) {  // more parts than column tiles: this part contributes nothing
@@ -244,7 +206,7 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
   if (sigma_eval) {
     if ((rc = dev_buf_t(c, "abd_As", (size_t)rows_avail * ld_af, &d_As))) return rc;
     TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_solve_modes(S, d_raw + (size_t)5 * rows_avail * nm * 2, 2LL * nm, nm, d_As, ld_af, row0, rows_avail,
-                                                                d_bsfwd, d_bstab, 1));
+                                                                kt.d_bsfwd, kt.d_bstab, 1));
     // row nm of the spin-2 harmonics (psi0 shares them and stops at row nm - 1) multiplies the solved constant series: -eth eth alpha.
     // Two invariants keep psi0's product, which shares the matrix, correct: the matrix has that row and the 8 rows a K chunk may read
     // past it (checked here), and launch_zgemm3m multiplies rows k >= K of B by ZERO-guarded A (kernels.h says so), because psi0's last
@@ -260,24 +222,13 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
   // ---- chunk loop: 6 fields x (Y, R, G)
   const BsplineSpread spread = skew_spread(T, cA, cB, u);
   const double bytes_per_row = 19.0 * ldg * 8.0;  // 6 x (Y, R, G) + F
-  int64_t chunk = (int64_t)((double)c->ws_limit / bytes_per_row - 4.0 * ROW_MARGIN);
-  if (chunk < 4 * ROW_MARGIN && chunk < n_new)
-    return fail(c, BMS_ERR_NOMEM, "work space limit of %llu bytes holds fewer than %d rows of the six %d-column grids (%.0f bytes each); raise it with bms_ctx_set_workspace_limit",
-                (unsigned long long)c->ws_limit, 8 * ROW_MARGIN, n_cols, bytes_per_row);
-  chunk = std::min<int64_t>(chunk, n_new);
-  if (!regular_mesh && chunk < n_new)
-    return fail(c, BMS_ERR_UNSUPPORTED, "irregular time axis (steps vary by more than 1e3 within 48 samples): the series does not fit the work space in one piece");
-  const int spline_tile = regular_mesh ? SPLINE_TILE : (int)std::min<int64_t>(n + 1, 0x7fffffff);  // one tile: exact recurrences
-  for (int64_t c0 = i_lo; c0 < i_hi; c0 += chunk) {
-    const int64_t c1_ = std::min<int64_t>(c0 + chunk, i_hi);
-    int64_t g0 = 0, g1 = n;  // (irregular time axis: the whole series)
-    if (regular_mesh) needed_rows(T, u, n, c0, c1_, g0, g1);
+  ChunkPlan plan;
+  if ((rc = plan_chunks(c, c->ws_limit, bytes_per_row, n_new, regular_mesh, n, "six ", n_cols, plan))) return rc;
+  for (int64_t c0 = i_lo; c0 < i_hi; c0 += plan.chunk) {
+    const int64_t c1_ = std::min<int64_t>(c0 + plan.chunk, i_hi);
+    int64_t g0, g1;
+    if ((rc = chunk_rows(c, T, u, n, regular_mesh, c0, c1_, row0, rows_avail, g0, g1))) return rc;
     const int64_t rows_in = g1 - g0, rows_out = c1_ - c0;
-    if (g0 < row0 || g1 > row0 + rows_avail)
-      return fail(c, BMS_ERR_INVALID,
-                  "shard holds rows [%lld, %lld) but outputs [%lld, %lld) need rows [%lld, %lld): halo too small "
-                  "(use bms_shard_plan)",
-                  (long long)row0, (long long)(row0 + rows_avail), (long long)c0, (long long)c1_, (long long)g0, (long long)g1);
     double *d_Y = nullptr, *d_R, *d_G;
     if (!fused_mix)
       if ((rc = dev_buf_t(c, "Y", (size_t)6 * rows_in * ldg, &d_Y))) return rc;
@@ -320,45 +271,33 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
     } else if (bsg) {  // mixing and elimination of the six fields in one pass over the grids
       AbdGrids elim;
       for (int f = 0; f < 6; ++f) elim.y[f] = d_R + (size_t)f * rows_in * ldg;
-      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_abd_mix_forward(S, grids, elim, ldg, n_pix, g0, rows_in, d_bsfwd, SPLINE_TILE, SPLINE_HALO, d_alpha, d_ethk,
+      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_abd_mix_forward(S, grids, elim, ldg, n_pix, g0, rows_in, kt.d_bsfwd, SPLINE_TILE, SPLINE_HALO, d_alpha, d_ethk,
                                                               d_etha, d_ethetha, d_ik, d_ik3, sigma_eval ? 5 : 6));
     } else {
       TIMED(c, BMS_TAG_POINTWISE,
-            launch_abd_mix(S, grids, ldg, n_pix, rows_in, d_x + g0, d_alpha, d_ethk, d_etha, d_ethetha, d_ik, d_ik3));
+            launch_abd_mix(S, grids, ldg, n_pix, rows_in, kt.d_x + g0, d_alpha, d_ethk, d_etha, d_ethetha, d_ik, d_ik3));
     }
     for (int f = 0; f < 6; ++f) {
       double* Rf = d_R + (size_t)f * rows_in * ldg;
       double* Gf = d_G + (size_t)f * rows_out * ldG;
       if (short_series) {
-        TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_short_series_eval(S, grids.y[f], ldg, n_pix, (int)n, d_x, d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG));
+        TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_short_series_eval(S, grids.y[f], ldg, n_pix, (int)n, kt.d_x, kt.d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG));
       } else if (f == 5 && sigma_eval) {
         SplineEval ev;
-        ev.table = d_bstab, ev.x = d_x, ev.skew_a = d_skewa, ev.skew_b = d_skewb, ev.tt = T.tt, ev.g0 = g0, ev.n_knots = n;
-        ev.i_lo = c0, ev.i_hi = c1_, ev.out = Gf, ev.ldo = ldG;
-        ev.search_halfwidth = eval_search_halfwidth(T, cA, cB, u, g0, g1);
-        ev.inv_dx = (g1 - g0 >= 2 && u[g1 - 1] > u[g0]) ? (double)(g1 - 1 - g0) / (u[g1 - 1] - u[g0]) : 0.0;
-        ev.side = nullptr, ev.side_ld = ldg;
-        if (!c->d_eval_stats) {
-          HIP_TRY(c, hipMalloc(&c->d_eval_stats, 16));
-          HIP_TRY(c, hipMemsetAsync(c->d_eval_stats, 0, 16, S));
-        }
-        ev.stats = c->d_eval_stats;
-        ev.step = c->opt.v[OPT_GEMM_EVAL_STEP] == 61 ? 61 : 64;
-        c->eval_tiles += eval_tile_count(rows_in, n_pix, ev.step);
-        if (ev.step != 61)
-          if ((rc = dev_buf_t(c, "Cside", (size_t)zgemm3m_eval_side_rows(rows_in) * ldg, &ev.side))) return rc;
+        ev.skew_a = d_skewa, ev.skew_b = d_skewb;
+        if ((rc = spline_eval_args(c, kt, T, cA, cB, u, n, g0, g1, c0, c1_, Gf, ldG, ldg, ev))) return rc;
         const int skip = 4 < nm ? 4 : 0;  // (spin 2: no modes below l = 2)
         TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m_eval(S, d_As + (g0 - row0) * ld_af + 2 * skip, ld_af, d_B[4] + 2 * cA + (size_t)skip * ldb, ldb, rows_in,
                                                              n_pix, nm - skip + 1, DP.col_scale + 2 * cA, ev));
       } else if (bsg) {
-        TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, Rf, ldg, n_pix, g0, rows_in, n, d_x, d_bstab, SPLINE_TILE, SPLINE_HALO,
-                                                                       d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG, &spread));
+        TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, Rf, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO,
+                                                                       kt.d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG, &spread));
       } else {
         TIMED(c, BMS_TAG_SPLINE_FORWARD,
-              launch_spline_forward(S, grids.y[f], Rf, ldg, n_pix, g0, rows_in, n, d_x, d_tab, spline_tile, SPLINE_HALO));
+              launch_spline_forward(S, grids.y[f], Rf, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO));
         TIMED(c, BMS_TAG_SPLINE_BACKWARD,
-              launch_spline_backward_eval(S, grids.y[f], Rf, ldg, n_pix, g0, rows_in, n, d_x, d_tab, spline_tile, SPLINE_HALO,
-                                          d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG));
+              launch_spline_backward_eval(S, grids.y[f], Rf, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO,
+                                          kt.d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG));
       }
       double* out_f = d_out + ((size_t)f * fs_out + (c0 - i_lo)) * n_out * 2;
       if (col_split) {
@@ -373,7 +312,7 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
       HIP_TRY(c, hipMemcpyAsync((char*)raw_out + (size_t)f * fs_out * n_out * 16, d_out + (size_t)f * fs_out * n_out * 2,
                                 (size_t)n_new * n_out * 16, hipMemcpyDeviceToHost, S));
   }
-  time_axis_commit(c, times_ahead, regular_mesh);  // (the walk covered the kept entry's range exactly when it was asked for ahead)
+  time_axis_commit(c, kt.times_ahead, regular_mesh);  // (the walk covered the kept entry's range exactly when it was asked for ahead)
   if (!c->async_pieces) HIP_TRY(c, hipStreamSynchronize(S));  // (a piece of a pipelined call returns without waiting)
   return BMS_OK;
 }

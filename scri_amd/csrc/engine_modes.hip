@@ -301,30 +301,17 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
       if (!skip) (void)hipStreamSynchronize(s);
     }
   } drain{c->stream, c->async_pieces};
-  // The time axis goes to the device and its spline tables are built BEFORE the host walks it (validate_common: 45 - 60 us per 1e5
-  // samples during which the GPU would have nothing of this call yet).  Speculative: what the walk can find -- samples out of
-  // order (the call fails; the tables built from them are never used) or a graded axis (the slope form uploads its own) -- is rare.
-  double* d_x = nullptr;
-  SplineTable* d_tab = nullptr;
-  BsplineTable* d_bstab = nullptr;
-  BsplineForward* d_bsfwd = nullptr;
+  KnotTables kt;  // on their way before the host walks the axis (knot_tables_ahead, engine_tables.hip)
   int rc;
-  const bool times_ahead = n >= 8 && in->t && !c->async_pieces && !c->opt.on(OPT_NO_BSPLINE) &&
-                           (!sh || (sh->data_row0 >= 0 && sh->data_rows >= 0 && sh->data_row0 + sh->data_rows <= n));
   begin_setup_reuse(c);
-  bool axis_known = false;  // the axis is one the context has tables for AND has walked: neither is done again
-  if (times_ahead) {
-    const int64_t r0 = sh ? sh->data_row0 : 0, r1 = r0 + (sh ? sh->data_rows : n);
-    if ((rc = upload_times_bspline(c, in->t, n, t_lo, t_hi, r0, r1, &d_x, &d_bstab, &d_bsfwd))) return rc;
-    axis_known = c->tcache.hit && c->tcache.walked;
-  }
+  if (in->t && (rc = knot_tables_ahead(c, in->t, n, sh, t_lo, t_hi, kt))) return rc;
   // The walk itself is put off as well, to the moment the host would otherwise sit waiting for the per-direction tables: until then
   // the axis is taken to be what it nearly always is (increasing, not graded).  A walk that finds otherwise drains what was queued
   // and either fails the call as it always did or starts it again, walk first.
-  const bool walk_later = times_ahead && c->aux && !walk_first && !c->opt.on(OPT_WALK_FIRST) && !axis_known;
+  const bool walk_later = kt.times_ahead && c->aux && !walk_first && !c->opt.on(OPT_WALK_FIRST) && !kt.axis_known;
   int walk_rc = BMS_OK;
   bool walked = false, walk_regular = true;
-  if (axis_known) {
+  if (kt.axis_known) {
     rc = validate_transformation(c, n, in->t, tr, 4);
     regular_mesh = c->tcache.regular;
   } else if (walk_later) {
@@ -399,11 +386,7 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   // once, by the back substitution + evaluation.
   const bool bsg = n >= 8 && regular_mesh && !c->opt.on(OPT_NO_BSPLINE);  // B-spline form (else: the slope form, kernels_spline.hip)
   const bool bs = bsg && !psi;                                                 // ... with the elimination commuted onto the modes
-  // (a "shard" that holds every row of every column is the whole series: only its output range is restricted)
-  if (!regular_mesh && sh != nullptr && !(sh->data_row0 == 0 && sh->data_rows == n && sh->col_parts <= 1))
-    return fail(c, BMS_ERR_UNSUPPORTED,
-                "the time steps vary by more than 1e3 within 48 samples: such a series is transformed with exact untiled spline "
-                "recurrences, which a time shard cannot provide");
+  if ((rc = refuse_sharded_graded_axis(c, regular_mesh, sh, n))) return rc;
   // Everything that depends on the time axis and the input modes only goes to the main stream first; the per-direction
   // tables, whose window the host has to wait for, are computed beside it on the auxiliary stream.
   FieldPlan F[5];
@@ -412,22 +395,8 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   F[0].spin = s;
   F[0].ld = in->ld;
   if ((rc = stage_in(c, "in_data", in->data, in->mem, (size_t)rows_avail * in->ld * 16, &F[0].d_data))) return rc;
-  // (pieces of a pipelined call: the knot tables depend on the time axis only and are built once, for the whole series --
-  // per piece they cost a blocking upload from pageable memory and two kernels that crawl while results leave over PCIe)
   PieceTables* shared = c->async_pieces ? static_cast<PieceTables*>(c->piece_tables) : nullptr;
-  if (bsg && shared && shared->times_valid) {
-    d_x = shared->d_x, d_bstab = shared->d_bstab, d_bsfwd = shared->d_bsfwd;
-  } else if (bsg && shared) {
-    rc = upload_times_bspline(c, in->t, n, 0, n, 0, n, &d_x, &d_bstab, &d_bsfwd);
-    shared->d_x = d_x, shared->d_bstab = d_bstab, shared->d_bsfwd = d_bsfwd;
-    shared->times_valid = rc == BMS_OK;
-  } else if (bsg && times_ahead)
-    rc = BMS_OK;  // (on their way since the top of the call)
-  else if (bsg)
-    rc = upload_times_bspline(c, in->t, n, t_lo, t_hi, row0, row0 + rows_avail, &d_x, &d_bstab, &d_bsfwd);
-  else
-    rc = upload_times(c, in->t, n, t_lo, t_hi, row0, row0 + rows_avail, &d_x, &d_tab);
-  if (rc) return rc;
+  if ((rc = knot_tables_of_call(c, in->t, n, t_lo, t_hi, row0, rows_avail, bsg, shared, kt))) return rc;
   const long long ld_af = round_up(2LL * (n_modes + 1), 16);  // rows on 128-byte lines
   double* d_Af = nullptr;
   trace.mark("input staging, time upload, spline factors (enqueue)");
@@ -505,11 +474,11 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
     if ((rc = dev_buf_t(c, "Afull", (size_t)rows_avail * ld_af, &d_Ac))) return rc;
     if (c->opt.on(OPT_TWO_SWEEPS)) {
       if ((rc = dev_buf_t(c, "Afwd", (size_t)rows_avail * ld_af, &d_Af))) return rc;
-      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, F[0].d_data, F[0].ld * 2, n_modes, d_Af, ld_af, row0, rows_avail, n, d_bsfwd,
+      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, F[0].d_data, F[0].ld * 2, n_modes, d_Af, ld_af, row0, rows_avail, n, kt.d_bsfwd,
                                                                     SPLINE_TILE, SPLINE_HALO, 1));
-      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_modes(S, d_Af, ld_af, n_modes + 1, d_Ac, ld_af, row0, rows_avail, d_bstab, SPLINE_TILE, SPLINE_HALO));
+      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_modes(S, d_Af, ld_af, n_modes + 1, d_Ac, ld_af, row0, rows_avail, kt.d_bstab, SPLINE_TILE, SPLINE_HALO));
     } else
-      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_solve_modes(S, F[0].d_data, F[0].ld * 2, n_modes, d_Ac, ld_af, row0, rows_avail, d_bsfwd, d_bstab, 1));
+      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_solve_modes(S, F[0].d_data, F[0].ld * 2, n_modes, d_Ac, ld_af, row0, rows_avail, kt.d_bsfwd, kt.d_bstab, 1));
     if (syn_eval && !coef0.empty()) {
       // C - off . 1 on the modes: column (l, m) of the solved modes loses coef0_lm times the solved constant column
       for (int l = in->ell_min; l <= std::min(lst, in->ell_max); ++l)
@@ -529,18 +498,11 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
     }
   } else if (bs && rows_avail > 0) {
     if ((rc = dev_buf_t(c, "Afwd", (size_t)rows_avail * ld_af, &d_Af))) return rc;
-    TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, F[0].d_data, F[0].ld * 2, n_modes, d_Af, ld_af, row0, rows_avail, n, d_bsfwd,
+    TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, F[0].d_data, F[0].ld * 2, n_modes, d_Af, ld_af, row0, rows_avail, n, kt.d_bsfwd,
                                                                   SPLINE_TILE, SPLINE_HALO, 1));
   }
   trace.mark("elimination / solve on the modes (enqueue)");
-  if (sep) {
-    const double* q = tr->frame_rotation;
-    if (!(q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) {
-      // sYlm(F G) = sum_m' D_{m m'}(F) sYlm'(G): the modes as seen from the rotated frame (the constant column stays)
-      const double sp[4] = {q[0], q[3], q[2], q[1]};  // (w + i z, y + i x)
-      if ((rc = rotate_impl(c, syn_eval ? d_Ac : d_Af, BMS_DEVICE, rows_avail, ld_af / 2, in->ell_min, in->ell_max, sp, false, false))) return rc;
-    }
-  }
+  if (sep && (rc = rotate_into_grid_frame(c, tr, syn_eval ? d_Ac : d_Af, rows_avail, ld_af / 2, in->ell_min, in->ell_max))) return rc;
   // The psi-mixing types (whose elimination stays on the grid) and the slope-form fallback of the others: without a boost every
   // field goes through the two-kernel separable synthesis of its own spin; mixing, offset and scale follow on the grid exactly
   // as they do behind the dense product.
@@ -686,30 +648,16 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
       double* d_e;
       snprintf(nm, sizeof nm, "psi_Af%d", fi);
       if ((rc = dev_buf_t(c, nm, (size_t)rows_avail * ld_e, &d_e))) return rc;
-      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, f.d_data, f.ld * 2, nmf, d_e, ld_e, row0, rows_avail, n, d_bsfwd, SPLINE_TILE, SPLINE_HALO, 0));
+      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, f.d_data, f.ld * 2, nmf, d_e, ld_e, row0, rows_avail, n, kt.d_bsfwd, SPLINE_TILE, SPLINE_HALO, 0));
       f.d_data = d_e;
       f.ld = ld_e / 2;
-      const double* q = tr->frame_rotation;
-      if (!(q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) {
-        const double sp[4] = {q[0], q[3], q[2], q[1]};  // (w + i z, y + i x)
-        if ((rc = rotate_impl(c, d_e, BMS_DEVICE, rows_avail, f.ld, f.ell_min, f.ell_max, sp, false, false))) return rc;
-      }
+      if ((rc = rotate_into_grid_frame(c, tr, d_e, rows_avail, f.ld, f.ell_min, f.ell_max))) return rc;
       continue;
     }
     if (sep_fields) {
       // the field as seen from the rotated frame: rotated in place in the staging copy (host callers), in a copy otherwise
-      const double* q = tr->frame_rotation;
-      if (!(q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) {
-        const double sp[4] = {q[0], q[3], q[2], q[1]};  // (w + i z, y + i x)
-        double* d_copy = const_cast<double*>(f.d_data);
-        if (in->mem == BMS_DEVICE) {
-          snprintf(nm, sizeof nm, "rot_in%d", fi);
-          if ((rc = dev_buf_t(c, nm, (size_t)rows_avail * f.ld * 2, &d_copy))) return rc;
-          HIP_TRY(c, hipMemcpyAsync(d_copy, f.d_data, (size_t)rows_avail * f.ld * 16, hipMemcpyDeviceToDevice, S));
-          f.d_data = d_copy;
-        }
-        if ((rc = rotate_impl(c, d_copy, BMS_DEVICE, rows_avail, f.ld, f.ell_min, f.ell_max, sp, false, false))) return rc;
-      }
+      snprintf(nm, sizeof nm, "rot_in%d", fi);
+      if ((rc = rotated_input_in_grid_frame(c, tr, nm, in->mem, &f.d_data, rows_avail, f.ld, f.ell_min, f.ell_max))) return rc;
       continue;
     }
     if (fi == 0 && B_built) continue;  // (built behind the per-direction tables on the auxiliary stream)
@@ -752,27 +700,13 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   const BsplineSpread spread = skew_spread(T, cA, cB, in->t);
   // bytes per output row ~ (Y + R + G [+ Yaux]) * ldg * 8
   const double bytes_per_row = (4.0 + (psi ? 1.0 : 0.0)) * ldg * 8.0;  // Y, R, G, F (+ Yaux)
-  // rows the work space limit allows; a chunk shorter than a few spline halos would spend its time re-synthesising them,
-  // so below that the limit is reported as too small rather than silently exceeded
-  int64_t chunk = (int64_t)((double)c->ws_limit / bytes_per_row - 4.0 * ROW_MARGIN);
-  if (chunk < 4 * ROW_MARGIN && chunk < n_new)
-    return fail(c, BMS_ERR_NOMEM, "work space limit of %llu bytes holds fewer than %d rows of the %d-column grids (%.0f bytes each); raise it with bms_ctx_set_workspace_limit",
-                (unsigned long long)c->ws_limit, 8 * ROW_MARGIN, n_cols, bytes_per_row);
-  chunk = std::min<int64_t>(chunk, n_new);
-  if (!regular_mesh && chunk < n_new)
-    return fail(c, BMS_ERR_UNSUPPORTED, "irregular time axis (steps vary by more than 1e3 within 48 samples): the series does not fit the work space in one piece");
-  const int spline_tile = regular_mesh ? SPLINE_TILE : (int)std::min<int64_t>(n + 1, 0x7fffffff);  // one tile: exact recurrences
-  for (int64_t c0 = i_lo; c0 < i_hi; c0 += chunk) {
-    const int64_t c1 = std::min<int64_t>(c0 + chunk, i_hi);
-    // (irregular time axis: the whole series, so that the single-tile recurrences start and end at the true ends)
-    int64_t g0 = 0, g1 = n;
-    if (regular_mesh) needed_rows(T, in->t, n, c0, c1, g0, g1);
+  ChunkPlan plan;
+  if ((rc = plan_chunks(c, c->ws_limit, bytes_per_row, n_new, regular_mesh, n, "", n_cols, plan))) return rc;
+  for (int64_t c0 = i_lo; c0 < i_hi; c0 += plan.chunk) {
+    const int64_t c1 = std::min<int64_t>(c0 + plan.chunk, i_hi);
+    int64_t g0, g1;
+    if ((rc = chunk_rows(c, T, in->t, n, regular_mesh, c0, c1, row0, rows_avail, g0, g1))) return rc;
     const int64_t rows_in = g1 - g0, rows_out = c1 - c0;
-    if (g0 < row0 || g1 > row0 + rows_avail)
-      return fail(c, BMS_ERR_INVALID,
-                  "shard holds rows [%lld, %lld) but outputs [%lld, %lld) need rows [%lld, %lld): halo too small "
-                  "(use bms_shard_plan)",
-                  (long long)row0, (long long)(row0 + rows_avail), (long long)c0, (long long)c1, (long long)g0, (long long)g1);
     double *d_Y = nullptr, *d_R = nullptr, *d_G, *d_Yaux = nullptr;
     if (!gemm_eval && !syn_eval)
       if ((rc = dev_buf_t(c, "Y", (size_t)rows_in * ldg, &d_Y))) return rc;
@@ -784,26 +718,13 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
       return rc;
     if (gemm_eval) {
       SplineEval ev;
-      ev.table = d_bstab, ev.x = d_x, ev.skew_a = d_skewa, ev.skew_b = d_skewb, ev.tt = T.tt, ev.g0 = g0, ev.n_knots = n;
-      ev.i_lo = c0, ev.i_hi = c1, ev.out = d_G, ev.ldo = ldG;
-      ev.search_halfwidth = eval_search_halfwidth(T, cA, cB, in->t, g0, g1);
-      ev.inv_dx = (g1 - g0 >= 2 && in->t[g1 - 1] > in->t[g0]) ? (double)(g1 - 1 - g0) / (in->t[g1 - 1] - in->t[g0]) : 0.0;
-      ev.side = nullptr, ev.side_ld = ldg;
-      if (!c->d_eval_stats) {
-        HIP_TRY(c, hipMalloc(&c->d_eval_stats, 16));
-        HIP_TRY(c, hipMemsetAsync(c->d_eval_stats, 0, 16, S));
-      }
-      ev.stats = c->d_eval_stats;
-      const int eval_step = c->opt.v[OPT_GEMM_EVAL_STEP] ? (int)c->opt.v[OPT_GEMM_EVAL_STEP] : 64;
-      ev.step = eval_step;
-      c->eval_tiles += eval_tile_count(rows_in, n_pix, eval_step);
-      if (eval_step != 61)
-        if ((rc = dev_buf_t(c, "Cside", (size_t)zgemm3m_eval_side_rows(rows_in) * ldg, &ev.side))) return rc;
+      ev.skew_a = d_skewa, ev.skew_b = d_skewb;
+      if ((rc = spline_eval_args(c, kt, T, cA, cB, in->t, n, g0, g1, c0, c1, d_G, ldG, ldg, ev))) return rc;
       TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m_eval(S, d_Ac + (g0 - row0) * ld_af, ld_af, F[0].d_B + 2 * cA, ldb, rows_in, n_pix, n_modes_in + 1,
                                                            d_scale, ev));
     } else if (syn_eval) {
       SplineEval ev;
-      ev.table = d_bstab, ev.x = d_x, ev.skew_a = nullptr, ev.skew_b = d_skewb, ev.tt = T.tt, ev.g0 = g0, ev.n_knots = n;
+      ev.table = kt.d_bstab, ev.x = kt.d_x, ev.skew_a = nullptr, ev.skew_b = d_skewb, ev.tt = T.tt, ev.g0 = g0, ev.n_knots = n;
       ev.i_lo = c0, ev.i_hi = c1, ev.out = d_G, ev.ldo = ldG;
       ev.search_halfwidth = 0, ev.inv_dx = 0.0, ev.side = nullptr, ev.side_ld = 0, ev.stats = nullptr;
       double s_min = 0.0, s_max = 0.0;
@@ -820,7 +741,7 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
       } else
       TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m(S, d_Af + (g0 - row0) * ld_af, ld_af, F[0].d_B + 2 * cA, ldb, d_Y, ldg, rows_in, n_pix,
                                                       n_modes_in + 1, nullptr, d_scale));
-      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_Y, ldg, n_pix, g0, rows_in, n, d_x, d_bstab, SPLINE_TILE, SPLINE_HALO, d_x, d_skewa,
+      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_Y, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO, kt.d_x, d_skewa,
                                                                      d_skewb, T.tt, c0, c1, d_G, ldG, &spread));
     } else {
     if (psi)
@@ -840,23 +761,23 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
         } else
         TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m(S, f.d_data + (g0 - row0) * f.ld * 2, f.ld * 2, f.d_B + 2 * cA, ldb, d_Yaux, ldg, rows_in, n_pix, f.K / 2,
                                 nullptr, nullptr));
-        TIMED(c, BMS_TAG_POINTWISE, launch_psi_mix(S, d_Y, d_Yaux, ldg, n_pix, rows_in, d_x + g0, d_alpha, d_xa, d_xb, in->aux_coeff[a],
+        TIMED(c, BMS_TAG_POINTWISE, launch_psi_mix(S, d_Y, d_Yaux, ldg, n_pix, rows_in, kt.d_x + g0, d_alpha, d_xa, d_xb, in->aux_coeff[a],
                                   in->aux_power[a]));
       }
       TIMED(c, BMS_TAG_POINTWISE, launch_affine_cols(S, d_Y, ldg, (int)P2, rows_in, d_off, d_scale));
     }
     // spline along time on the shared knots, evaluated on the distorted slices
     if (bsg && sep_fields && psi && no_boost) {  // (eliminated on the modes above: d_Y holds coefficients already)
-      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_Y, ldg, n_pix, g0, rows_in, n, d_x, d_bstab, SPLINE_TILE, SPLINE_HALO, d_x, d_skewa,
+      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_Y, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO, kt.d_x, d_skewa,
                                                                      d_skewb, T.tt, c0, c1, d_G, ldG, &spread));
     } else if (bsg) {  // mixing is time dependent: eliminate on the grid, then the coefficient-only back substitution
-      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, d_Y, ldg, n_pix, d_R, ldg, g0, rows_in, n, d_bsfwd, SPLINE_TILE, SPLINE_HALO, 0));
-      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_R, ldg, n_pix, g0, rows_in, n, d_x, d_bstab, SPLINE_TILE, SPLINE_HALO, d_x, d_skewa,
+      TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, d_Y, ldg, n_pix, d_R, ldg, g0, rows_in, n, kt.d_bsfwd, SPLINE_TILE, SPLINE_HALO, 0));
+      TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_R, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO, kt.d_x, d_skewa,
                                                                      d_skewb, T.tt, c0, c1, d_G, ldG, &spread));
     } else {
-    TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_Y, d_R, ldg, n_pix, g0, rows_in, n, d_x, d_tab, spline_tile, SPLINE_HALO));
-    TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_backward_eval(S, d_Y, d_R, ldg, n_pix, g0, rows_in, n, d_x, d_tab, spline_tile, SPLINE_HALO,
-                                           d_x, d_skewa, d_skewb, T.tt, c0, c1, d_G, ldG));
+    TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_Y, d_R, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO));
+    TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_backward_eval(S, d_Y, d_R, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO,
+                                           kt.d_x, d_skewa, d_skewb, T.tt, c0, c1, d_G, ldG));
     }
     }
     // analysis
@@ -876,7 +797,7 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   // the new time axis is host work: done while the GPU runs
   for (int64_t i = 0; i < n_new; ++i) t_out[i] = (1 / T.gamma) * (in->t[i_lo + i] - T.tt);
   // (the walk of this call covered the kept axis entry's range exactly when the entry was asked for ahead of it)
-  time_axis_commit(c, times_ahead, regular_mesh);
+  time_axis_commit(c, kt.times_ahead, regular_mesh);
   // host tables above are stack/vector memory: wait for the uploads (and results) before returning
   if (!c->async_pieces) HIP_TRY(c, hipStreamSynchronize(S));
   trace.mark("final synchronize");

@@ -319,9 +319,6 @@ int piece_produced(bms_ctx* c, const PiecePlan& P, int k, int64_t got, int64_t f
               (long long)got, (long long)first);
 }
 
-
-
-
 int build_analysis(bms_ctx* c, const char* tag, int n_theta, int n_phi, int spin, int ell_min_out, int ell_max_out,
                           AnalysisPlan& A) {
   hipStream_t S = c->stream;
@@ -1049,4 +1046,120 @@ uint64_t eval_tile_count(long long rows, int n_cols, int step) {
   if (step == 61) return (uint64_t)std::max<long long>(0, (rows - 3 + 60) / 61) * nbn;
   const uint64_t nbm = (uint64_t)((rows + 63) / 64);
   return nbm * nbn + (nbm > 0 ? nbm - 1 : 0) * nbn;
+}
+
+// ====================================================================================================== steps both transforms take
+// (transform_modes_impl and transform_abd_impl call each of these where the block stood; what differs between them stays at the call)
+
+// The time axis goes to the device and its spline tables are built BEFORE the host walks it (validate_common: 45 - 60 us per 1e5
+// samples during which the GPU would have nothing of this call yet).  Speculative: what the walk can find -- samples out of
+// order (the call fails; the tables built from them are never used) or a graded axis (the slope form uploads its own) -- is rare.
+int knot_tables_ahead(bms_ctx* c, const double* t, int64_t n, const bms_shard* sh, int64_t t_lo, int64_t t_hi, KnotTables& kt) {
+  kt.times_ahead = n >= 8 && !c->async_pieces && !c->opt.on(OPT_NO_BSPLINE) &&
+                   (!sh || (sh->data_row0 >= 0 && sh->data_rows >= 0 && sh->data_row0 + sh->data_rows <= n));
+  if (!kt.times_ahead) return BMS_OK;
+  const int64_t r0 = sh ? sh->data_row0 : 0, r1 = r0 + (sh ? sh->data_rows : n);
+  const int rc = upload_times_bspline(c, t, n, t_lo, t_hi, r0, r1, &kt.d_x, &kt.d_bstab, &kt.d_bsfwd);
+  kt.axis_known = rc == BMS_OK && c->tcache.hit && c->tcache.walked;
+  return rc;
+}
+
+// (pieces of a pipelined call: the knot tables depend on the time axis only and are built once, for the whole series --
+// per piece they cost a blocking upload from pageable memory and two kernels that crawl while results leave over PCIe)
+int knot_tables_of_call(bms_ctx* c, const double* t, int64_t n, int64_t t_lo, int64_t t_hi, int64_t row0, int64_t rows_avail, bool bsg,
+                        PieceTables* shared, KnotTables& kt) {
+  if (bsg && shared && shared->times_valid) {
+    kt.d_x = shared->d_x, kt.d_bstab = shared->d_bstab, kt.d_bsfwd = shared->d_bsfwd;
+    return BMS_OK;
+  }
+  if (bsg && shared) {
+    const int rc = upload_times_bspline(c, t, n, 0, n, 0, n, &kt.d_x, &kt.d_bstab, &kt.d_bsfwd);
+    shared->d_x = kt.d_x, shared->d_bstab = kt.d_bstab, shared->d_bsfwd = kt.d_bsfwd;
+    shared->times_valid = rc == BMS_OK;
+    return rc;
+  }
+  if (bsg && kt.times_ahead) return BMS_OK;  // (on their way since the top of the call)
+  if (bsg) return upload_times_bspline(c, t, n, t_lo, t_hi, row0, row0 + rows_avail, &kt.d_x, &kt.d_bstab, &kt.d_bsfwd);
+  return upload_times(c, t, n, t_lo, t_hi, row0, row0 + rows_avail, &kt.d_x, &kt.d_tab);
+}
+
+// (a "shard" that holds every row of every column is the whole series: only its output range is restricted)
+int refuse_sharded_graded_axis(bms_ctx* c, bool regular_mesh, const bms_shard* sh, int64_t n) {
+  if (regular_mesh || !sh || (sh->data_row0 == 0 && sh->data_rows == n && sh->col_parts <= 1)) return BMS_OK;
+  return fail(c, BMS_ERR_UNSUPPORTED,
+              "the time steps vary by more than 1e3 within 48 samples: such a series is transformed with exact untiled spline "
+              "recurrences, which a time shard cannot provide");
+}
+
+// Output samples per pass of a chunk loop whose grids take bytes_per_row per sample (how_many: "" or "six ", for the message).
+// Rows the work space limit allows; a chunk shorter than a few spline halos would spend its time re-synthesising them,
+// so below that the limit is reported as too small rather than silently exceeded
+int plan_chunks(bms_ctx* c, uint64_t ws_limit, double bytes_per_row, int64_t n_new, bool regular_mesh, int64_t n, const char* how_many, int n_cols,
+                ChunkPlan& P) {
+  P.chunk = (int64_t)((double)ws_limit / bytes_per_row - 4.0 * ROW_MARGIN);
+  if (P.chunk < 4 * ROW_MARGIN && P.chunk < n_new)
+    return fail(c, BMS_ERR_NOMEM, "work space limit of %llu bytes holds fewer than %d rows of the %s%d-column grids (%.0f bytes each); raise it with bms_ctx_set_workspace_limit",
+                (unsigned long long)ws_limit, 8 * ROW_MARGIN, how_many, n_cols, bytes_per_row);
+  P.chunk = std::min<int64_t>(P.chunk, n_new);
+  if (!regular_mesh && P.chunk < n_new)
+    return fail(c, BMS_ERR_UNSUPPORTED, "irregular time axis (steps vary by more than 1e3 within 48 samples): the series does not fit the work space in one piece");
+  P.spline_tile = regular_mesh ? SPLINE_TILE : (int)std::min<int64_t>(n + 1, 0x7fffffff);  // one tile: exact recurrences
+  return BMS_OK;
+}
+
+// input rows [g0, g1) of the chunk that produces outputs [c0, c1), which the call must hold (rows [row0, row0 + rows_avail))
+int chunk_rows(bms_ctx* c, const PixelTables& T, const double* t, int64_t n, bool regular_mesh, int64_t c0, int64_t c1, int64_t row0,
+               int64_t rows_avail, int64_t& g0, int64_t& g1) {
+  // (irregular time axis: the whole series, so that the single-tile recurrences start and end at the true ends)
+  g0 = 0, g1 = n;
+  if (regular_mesh) needed_rows(T, t, n, c0, c1, g0, g1);
+  if (g0 < row0 || g1 > row0 + rows_avail)
+    return fail(c, BMS_ERR_INVALID,
+                "shard holds rows [%lld, %lld) but outputs [%lld, %lld) need rows [%lld, %lld): halo too small "
+                "(use bms_shard_plan)",
+                (long long)row0, (long long)(row0 + rows_avail), (long long)c0, (long long)c1, (long long)g0, (long long)g1);
+  return BMS_OK;
+}
+
+// sYlm(F G) = sum_m' D_{m m'}(F) sYlm'(G): device modes c16[rows][ld] as seen from the rotated frame, the frame of the separable
+// synthesis, in place (columns beyond the modes -- the constant column -- stay); nothing to do for the identity
+static bool identity_rotor(const double* q) { return q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0; }
+int rotate_into_grid_frame(bms_ctx* c, const bms_transformation* tr, double* data, int64_t rows, int64_t ld, int ell_min, int ell_max) {
+  const double* q = tr->frame_rotation;
+  if (identity_rotor(q)) return BMS_OK;
+  const double sp[4] = {q[0], q[3], q[2], q[1]};  // (w + i z, y + i x)
+  return rotate_impl(c, data, BMS_DEVICE, rows, ld, ell_min, ell_max, sp, false, false);
+}
+
+// the same for staged input: rotated in place in the staging copy (host callers), in a copy named `name` otherwise (*d_data then)
+int rotated_input_in_grid_frame(bms_ctx* c, const bms_transformation* tr, const char* name, int mem, const double** d_data, int64_t rows, int64_t ld,
+                                int ell_min, int ell_max) {
+  double* d_copy = const_cast<double*>(*d_data);
+  if (mem == BMS_DEVICE && !identity_rotor(tr->frame_rotation)) {
+    int rc;
+    if ((rc = dev_buf_t(c, name, (size_t)rows * ld * 2, &d_copy))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_copy, *d_data, (size_t)rows * ld * 16, hipMemcpyDeviceToDevice, c->stream));
+    *d_data = d_copy;
+  }
+  return rotate_into_grid_frame(c, tr, d_copy, rows, ld, ell_min, ell_max);
+}
+
+// What a launch of the evaluating product (kernels_gemm_eval.hip) over input rows [g0, g1) and columns [cA, cB) for outputs [c0, c1)
+// is told about the spline; skew_a / skew_b are the caller's.  ldg: the row stride of the call's grids, which the side buffer takes.
+int spline_eval_args(bms_ctx* c, const KnotTables& kt, const PixelTables& T, int cA, int cB, const double* t, int64_t n, int64_t g0, int64_t g1,
+                     int64_t c0, int64_t c1, double* out, long long ldo, long long ldg, SplineEval& ev) {
+  ev.table = kt.d_bstab, ev.x = kt.d_x, ev.tt = T.tt, ev.g0 = g0, ev.n_knots = n;
+  ev.i_lo = c0, ev.i_hi = c1, ev.out = out, ev.ldo = ldo;
+  ev.search_halfwidth = eval_search_halfwidth(T, cA, cB, t, g0, g1);
+  ev.inv_dx = (g1 - g0 >= 2 && t[g1 - 1] > t[g0]) ? (double)(g1 - 1 - g0) / (t[g1 - 1] - t[g0]) : 0.0;
+  ev.side = nullptr, ev.side_ld = ldg;
+  if (!c->d_eval_stats) {
+    HIP_TRY(c, hipMalloc(&c->d_eval_stats, 16));
+    HIP_TRY(c, hipMemsetAsync(c->d_eval_stats, 0, 16, c->stream));
+  }
+  ev.stats = c->d_eval_stats;
+  ev.step = c->opt.v[OPT_GEMM_EVAL_STEP] == 61 ? 61 : 64;  // (bms_ctx_set_option takes 0 -- automatic --, 61 or 64)
+  c->eval_tiles += eval_tile_count(g1 - g0, cB - cA, ev.step);
+  if (ev.step == 61) return BMS_OK;  // (overlapping tiles: no side buffer)
+  return dev_buf_t(c, "Cside", (size_t)zgemm3m_eval_side_rows(g1 - g0) * ldg, &ev.side);
 }

@@ -1,7 +1,8 @@
 """`make SAN=1` (scri_amd/csrc/Makefile): the host side of the engine -- shard plans, output windows, knot ranges, column parts,
-search bounds, rotor / harmonic / conformal tables, the frame integrator -- compiled with AddressSanitizer and
-UndefinedBehaviorSanitizer and run over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd
-grids (tools/san/host_san_driver.cpp).  No GPU sanitizer exists on this pool; this is the part that can be covered."""
+search bounds, the chunk planner of the two transforms (caps that give 1 to several hundred chunks, and what it refuses), rotor /
+harmonic / conformal tables, the frame integrator -- compiled with AddressSanitizer and UndefinedBehaviorSanitizer and run over the
+five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids (tools/san/host_san_driver.cpp).  No GPU
+sanitizer exists on this pool; this is the part that can be covered."""
 import os
 import subprocess
 

@@ -1,8 +1,9 @@
 // Host-side sanitizer run (no GPU sanitizer exists on this pool: ASan / UBSan cover what runs on the host).
 // `make -C scri_amd/csrc SAN=1` compiles this file -- which INCLUDES the host side of the engine (engine_*.hip, split by entry family
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
-// parts, chunk walks, the pieces of the pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain and of the alignment entries, the planner and the per-step math of the precessing sample waveform over the five BASELINE shapes, 1..8 shards,
-// 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
+// pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain and of the alignment entries, the planner and the per-step
+// math of the precessing sample waveform over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -59,6 +60,61 @@ void fill_transformation(bms_transformation& tr, std::vector<cplx>& st, const Sh
   tr.boost_velocity[0] = 1e-4 * s.boost_scale, tr.boost_velocity[1] = 2e-4 * s.boost_scale, tr.boost_velocity[2] = 3e-4 * s.boost_scale;
   tr.n_theta = s.n_theta, tr.n_phi = s.n_phi;
   tr.ell_max_out = s.ell_max;
+}
+
+// The chunk loops of the two transforms (plan_chunks, chunk_rows of engine_tables.hip) under work-space caps that give 1, 2, 7 and several
+// hundred chunks: the chunks tile the output window once and in order, and each reads rows inside the series that hold its outputs'
+// knots.  (No chunk is shorter than 4 * ROW_MARGIN outputs, so "several hundred" -- at least 200 chunks -- is asserted for the series of
+// 1e5 steps and more; cfg1's 2000 steps make 15 chunks of that least length, and the tiling checks hold for them all the same.)
+// Then what the planner refuses: a cap below 4 * ROW_MARGIN rows, a graded axis in more than one chunk, a shard one row short.
+void chunk_walk(const Shape& s, const bms_transformation& tr, const PixelTables& T, const double* t, int64_t i_lo, int64_t i_hi) {
+  bms_ctx dummy;
+  const int64_t n = s.n, n_new = i_hi - i_lo;
+  REQUIRE(n_new > 8 * ROW_MARGIN);
+  const double bytes_per_row = (s.abd ? 19.0 : 4.0) * (double)round_up(2LL * T.n_pix, 16) * 8.0;  // as the two implementations count them
+  const char* how_many = s.abd ? "six " : "";
+  auto cap_for = [&](int64_t rows) { return (uint64_t)(((double)rows + 4.0 * ROW_MARGIN + 0.5) * bytes_per_row); };
+  ChunkPlan P;
+  for (int want : {1, 2, 7, 300}) {
+    const int64_t rows = std::max<int64_t>((n_new + want - 1) / want, 4 * ROW_MARGIN);  // (no chunk is shorter than 4 * ROW_MARGIN)
+    REQUIRE(plan_chunks(&dummy, cap_for(rows), bytes_per_row, n_new, true, n, how_many, T.n_pix, P) == BMS_OK);
+    REQUIRE(P.chunk == rows && P.spline_tile == SPLINE_TILE);
+    int64_t covered = i_lo, count = 0;
+    for (int64_t c0 = i_lo; c0 < i_hi; c0 += P.chunk, ++count) {
+      const int64_t c1 = std::min<int64_t>(c0 + P.chunk, i_hi);
+      REQUIRE(c0 == covered && c1 > c0);
+      int64_t g0 = -1, g1 = -1, ja, jb;
+      REQUIRE(chunk_rows(&dummy, T, t, n, true, c0, c1, 0, n, g0, g1) == BMS_OK);
+      needed_knots(T, t, n, c0, c1, ja, jb);
+      REQUIRE(0 <= g0 && g0 <= ja && jb < g1 && g1 <= n);
+      covered = c1;
+    }
+    REQUIRE(covered == i_hi && count == (n_new + rows - 1) / rows);
+    REQUIRE(count == want || (want == 300 && (n < 100000 || count >= 200)));
+  }
+  char text[96];
+  std::snprintf(text, sizeof text, "fewer than %d rows of the %s%d-column grids", 8 * ROW_MARGIN, how_many, T.n_pix);
+  REQUIRE(plan_chunks(&dummy, cap_for(4 * ROW_MARGIN - 1), bytes_per_row, n_new, true, n, how_many, T.n_pix, P) == BMS_ERR_NOMEM);
+  REQUIRE(std::strstr(bms_last_error(&dummy), text) != nullptr);
+  REQUIRE(plan_chunks(&dummy, 0, bytes_per_row, n_new, true, n, how_many, T.n_pix, P) == BMS_ERR_NOMEM);
+  REQUIRE(plan_chunks(&dummy, cap_for(4 * ROW_MARGIN - 1), bytes_per_row, 100, true, n, how_many, T.n_pix, P) == BMS_OK && P.chunk == 100);  // (a window that fits)
+  // a graded axis is one chunk over the whole series, or refused
+  REQUIRE(plan_chunks(&dummy, cap_for(n_new - 1), bytes_per_row, n_new, false, n, how_many, T.n_pix, P) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(plan_chunks(&dummy, cap_for(n_new), bytes_per_row, n_new, false, n, how_many, T.n_pix, P) == BMS_OK);
+  REQUIRE(P.chunk == n_new && P.spline_tile == n + 1);
+  int64_t g0 = -1, g1 = -1;
+  REQUIRE(chunk_rows(&dummy, T, t, n, false, i_lo, i_hi, 0, n, g0, g1) == BMS_OK && g0 == 0 && g1 == n);
+  bms_shard whole = {0, n, i_lo, i_hi, 0, 0}, part = {1, n - 1, i_lo, i_hi, 0, 0};
+  REQUIRE(refuse_sharded_graded_axis(&dummy, false, nullptr, n) == BMS_OK && refuse_sharded_graded_axis(&dummy, false, &whole, n) == BMS_OK);
+  REQUIRE(refuse_sharded_graded_axis(&dummy, true, &part, n) == BMS_OK && refuse_sharded_graded_axis(&dummy, false, &part, n) == BMS_ERR_UNSUPPORTED);
+  // a mid-series shard: the rows bms_shard_plan names are enough, one row less at either end is not
+  const int64_t o0 = i_lo + n_new / 3, o1 = i_lo + 2 * n_new / 3;
+  int64_t need[2], win[2];
+  REQUIRE(bms_shard_plan(nullptr, t, n, &tr, o0, o1, need, win) == BMS_OK && 0 < need[0] && need[1] < n);
+  REQUIRE(chunk_rows(&dummy, T, t, n, true, o0, o1, need[0], need[1] - need[0], g0, g1) == BMS_OK && g0 == need[0] && g1 == need[1]);
+  REQUIRE(chunk_rows(&dummy, T, t, n, true, o0, o1, need[0] + 1, need[1] - need[0] - 1, g0, g1) == BMS_ERR_INVALID);
+  REQUIRE(std::strstr(bms_last_error(&dummy), "halo too small (use bms_shard_plan)") != nullptr);
+  REQUIRE(chunk_rows(&dummy, T, t, n, true, o0, o1, need[0], need[1] - need[0] - 1, g0, g1) == BMS_ERR_INVALID);
 }
 
 void run_shape(const Shape& s) {
@@ -138,6 +194,7 @@ void run_shape(const Shape& s) {
     }
     REQUIRE(P.max_rows == max_rows && P.max_out == max_out);
   }
+  chunk_walk(s, tr, T, t.data(), i_lo, i_hi);
   // rotor grid, harmonics, conformal factors of the (boosted, rotated) grid through the ctx = NULL building blocks
   std::vector<double> rot((size_t)4 * T.n_pix);
   REQUIRE(bms_rotor_grid(nullptr, tr.frame_rotation, tr.boost_velocity, s.n_theta, s.n_phi, rot.data()) == BMS_OK);
