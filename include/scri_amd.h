@@ -82,6 +82,10 @@ int bms_ctx_reserve(bms_ctx* ctx, uint64_t bytes);
  * reset, out[1] = tiles whose samples left the window of output times staged in LDS (non-uniform time axes, strong boosts: same
  * results through global memory, slower), out[2] = per-column marches continued from global memory.  No reference counterpart. */
 int bms_ctx_get_eval_stats(bms_ctx* ctx, int64_t* out /* [3] */, int reset);
+/* Which kernel served the rotations (bms_rotate_const / bms_rotate_series and the transforms' rotation of the modes): out[0], out[1],
+ * out[2] = launches of the LDS-resident, the staged matrix-core and the VALU kernel since the last reset, out[3] = waves per
+ * workgroup (4, 3, 2 or 1, by ell_max) of the most recent VALU launch, 0 if there was none.  Host counters; no reference counterpart. */
+int bms_ctx_get_rotate_stats(bms_ctx* ctx, int64_t* out /* [4] */, int reset);
 /* block until all work queued by this context has finished */
 int bms_ctx_synchronize(bms_ctx* ctx);
 

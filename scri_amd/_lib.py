@@ -84,6 +84,7 @@ SIGNATURES = {
     "bms_ctx_set_workspace_limit": (c_int, [c_vp, ctypes.c_uint64]),
     "bms_ctx_reserve": (c_int, [c_vp, ctypes.c_uint64]),
     "bms_ctx_get_eval_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
+    "bms_ctx_get_rotate_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
     "bms_ctx_synchronize": (c_int, [c_vp]),
     "bms_ctx_enable_timing": (c_int, [c_vp, c_int]),
     "bms_ctx_get_timing": (c_int, [c_vp, c_dp, ctypes.POINTER(c_i64), c_int]),
@@ -479,6 +480,13 @@ class Context:
         """(tiles launched, tiles off the LDS path, marches continued from global memory) of the evaluating product since the last reset"""
         out = (c_i64 * 3)()
         self.check(load().bms_ctx_get_eval_stats(self._h, out, 1 if reset else 0), "bms_ctx_get_eval_stats")
+        return tuple(int(v) for v in out)
+
+    def rotate_stats(self, reset=True):
+        """(launches of the LDS-resident kernel, of the staged MFMA kernel, of the VALU kernel, waves per workgroup of the most recent
+        VALU launch) of the rotations since the last reset"""
+        out = (c_i64 * 4)()
+        self.check(load().bms_ctx_get_rotate_stats(self._h, out, 1 if reset else 0), "bms_ctx_get_rotate_stats")
         return tuple(int(v) for v in out)
 
     def reserve(self, nbytes=0):

@@ -184,6 +184,10 @@ struct bms_ctx {
   std::vector<Slab> slabs;             // reserved by bms_ctx_reserve; the newest one with room serves the named buffers
   int delta_lmax = -1;                 // Delta tables cached up to this l
   int delta_mfma_lmax = -1;            // ... in the MFMA B-image packing
+  // which rotation kernel served the calls since the last reset (bms_ctx_get_rotate_stats): launches of the resident, staged and VALU
+  // kernels, and the waves per workgroup of the most recent VALU launch as its launcher reported them
+  uint64_t rot_launches[3] = {0, 0, 0};
+  int rot_valu_waves = 0;
   hipStream_t pipe_up = nullptr, pipe_down = nullptr;  // run_host_pipeline: uploads and downloads beside the kernels
   // set by SharedPieceTables around the per-piece calls of a pipelined call: the pieces share one transformation, so the
   // per-direction tables are computed (and read back) once, and a piece returns without waiting for its kernels

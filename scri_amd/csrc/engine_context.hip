@@ -342,6 +342,20 @@ extern "C" int bms_ctx_get_eval_stats(bms_ctx* c, int64_t* out /*[3]*/, int rese
   return BMS_OK;
 } BMS_CATCH(c)
 
+// Which rotation kernel served the calls (engine_rotate.hip, launch_segments): out[0..2] = launches of the LDS-resident, the staged
+// MFMA and the VALU kernel since the last reset, out[3] = waves per workgroup of the most recent VALU launch (0: none yet).  Host
+// counters only: nothing is read from the device and nothing waits.
+extern "C" int bms_ctx_get_rotate_stats(bms_ctx* c, int64_t* out /*[4]*/, int reset) try {
+  if (!c || !out) return BMS_ERR_INVALID;
+  for (int k = 0; k < 3; ++k) out[k] = (int64_t)c->rot_launches[k];
+  out[3] = c->rot_valu_waves;
+  if (reset) {
+    for (int k = 0; k < 3; ++k) c->rot_launches[k] = 0;
+    c->rot_valu_waves = 0;
+  }
+  return BMS_OK;
+} BMS_CATCH(c)
+
 extern "C" int bms_ctx_enable_timing(bms_ctx* c, int on) try {
   if (!c) return BMS_ERR_INVALID;
   c->timing = on != 0;

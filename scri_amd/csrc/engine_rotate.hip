@@ -87,7 +87,8 @@ int rotate_impl(bms_ctx* c, void* data, int mem, int64_t n_times, int64_t ld, in
       else if (sg.kind == 1)
         TIMED(c, BMS_TAG_ROTATE, launch_rotate_modes_mfma(c->stream, seg_data, rows, pitch, sg.lo, sg.hi, rot, series ? 4 : 0, d_delta, d_off));
       else
-        TIMED(c, BMS_TAG_ROTATE, launch_rotate_modes(c->stream, seg_data, rows, pitch, sg.lo, sg.hi, rot, series ? 4 : 0, d_delta, d_off));
+        TIMED(c, BMS_TAG_ROTATE, launch_rotate_modes(c->stream, seg_data, rows, pitch, sg.lo, sg.hi, rot, series ? 4 : 0, d_delta, d_off, &c->rot_valu_waves));
+      if (rows > 0) ++c->rot_launches[sg.kind];  // (bms_ctx_get_rotate_stats; a launcher handed no rows launches nothing)
     }
     return BMS_OK;
   };

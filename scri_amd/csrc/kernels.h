@@ -52,9 +52,9 @@ constexpr int ROT_MB = 4;  // mu-block of the packed Delta tables (see kernels_r
 int rotate_waves_per_block(int ell_max);
 hipError_t launch_rotate_modes(hipStream_t stream, double* data, long long n_times, long long ld, int ell_min, int ell_max,
                                const double* RaRb, long long rotor_stride, const double* delta,
-                               const long long* delta_off);
+                               const long long* delta_off, int* waves_used = nullptr /* out: waves per workgroup of the launch */);
 
-// MFMA formulation (kernels_rotate_mfma.hip), ell_max <= ~32: btab = per-l packed B images, boff = offsets (doubles)
+// MFMA formulation (kernels_rotate_mfma.hip), ell_max <= 33: btab = per-l packed B images, boff = offsets (doubles)
 struct RotGeom;
 void rotate_mfma_table_shape(int ell, int* kpad, int* pd);
 int rotate_mfma_supported(int ell_max);

@@ -201,10 +201,11 @@ int rotate_waves_per_block(int ell_max) {
 
 hipError_t launch_rotate_modes(hipStream_t stream, double* data, long long n_times, long long ld, int ell_min, int ell_max,
                                const double* RaRb, long long rotor_stride, const double* delta,
-                               const long long* delta_off) {
+                               const long long* delta_off, int* waves_used) {
   if (n_times <= 0) return hipSuccess;
   const int waves = rotate_waves_per_block(ell_max);
   if (waves < 1) return hipErrorInvalidValue;
+  if (waves_used) *waves_used = waves;
   const int pitch = (2 * ell_max + 1) | 1;
   const size_t lds = (size_t)waves * 2 * 64 * pitch * sizeof(double);
   hipError_t e = allow_dynamic_lds((const void*)rotate_modes_kernel);

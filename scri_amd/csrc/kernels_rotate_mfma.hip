@@ -24,8 +24,8 @@ namespace bms {
 typedef double v4dr __attribute__((ext_vector_type(4)));
 
 constexpr int RM_TB = 64;       // time steps per workgroup
-constexpr int RM_MAX_NT = 5;    // column tiles of 16: 2l+1 <= 80 (l <= 32 supported by the launcher)
-constexpr int RM_LD = 9;        // elements a thread loads per batch in the staging pass ((2l+1)/4 <= 9 for l <= 16)
+constexpr int RM_MAX_NT = 5;    // column tiles of 16: 2l+1 <= 80; the LDS image fits 160 KB up to l = 33, which is what the launcher takes
+constexpr int RM_LD = 9;        // elements a thread loads per batch in the staging pass of the <5> build (a quarter row there is 13..17: two batches)
 
 struct RotGeom {
   int pa;       // LDS pitch of an A row (doubles), 2 x odd

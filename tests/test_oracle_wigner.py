@@ -30,6 +30,27 @@ def test_C1_C2_unitary_and_representation():
         assert np.abs(D12 - D2 @ D1).max() > 0.1  # the other order is NOT the convention
 
 
+@pytest.mark.parametrize("ell", [36, 79])
+def test_unitary_and_representation_at_the_ell_of_the_rotation_fallbacks(ell):
+    """tests/test_gpu_rotation_routes.py leans on the oracle's D up to l = 79 (the last l of the VALU rotation kernel); the pins above stop
+    at l = 16.  Unitarity and D(q1 q2) = D(q1) D(q2) for one random pair and one near-pole rotor.  2e-13 is the 2e-14 above times 10:
+    a product of two matrices of order 159 accumulates more rounding than one of order 33.  (The fast D against the 60-digit sum is
+    1.9e-15 at l = 79 and <= 5.9e-15 at l = 36; at l = 79 that sum takes minutes, which is why it is not the routine check.)"""
+    rng = np.random.default_rng(79)
+    q1, q2 = _rand_rotor(rng), _rand_rotor(rng)
+    pole = np.array([1.0, 3e-10, -4e-10, 0.3])
+    pole /= np.linalg.norm(pole)
+    q = np.stack([q1, q2, quat.qmul(q1, q2), pole, quat.qmul(pole, q1)])
+    sp = quat.as_spinor_array(q)
+    n = 2 * ell + 1
+    D1, D2, D12, Dp, Dp1 = wigner.wigner_D_matrices(sp[:, 0], sp[:, 1], ell, ell).reshape(5, n, n)  # (one call: its cost hardly depends on the rotor count)
+    for D in (D1, D2, Dp):
+        assert np.abs(D @ D.conj().T - np.eye(n)).max() < 2e-13
+    assert np.abs(D12 - D1 @ D2).max() < 2e-13
+    assert np.abs(Dp1 - Dp @ D1).max() < 2e-13
+    assert np.abs(D12 - D2 @ D1).max() > 0.1 * n**-0.5  # the other order is NOT the convention
+
+
 def test_fast_D_matches_exact_sum():
     rng = np.random.default_rng(1)
     rotors = [_rand_rotor(rng) for _ in range(3)] + [np.array([1.0, 0, 0, 1e-9]), np.array([1e-9, 1.0, 0, 0]), np.array([1.0, 1, 0, 0]) / math.sqrt(2)]
