@@ -345,7 +345,10 @@ int bms_grid_multiply(bms_ctx* ctx, const void* a, int spin_a, int ell_max_a, co
 /* ---- what feeds the rotation path -------------------------------------------------------- */
 /* <Ldt> (f8[n][3]), <LL> (f8[n][3][3]) and the angular velocity omega = -<LL>^-1 <Ldt> (f8[n][3]) of a waveform from its
  * modes data c16[n][ld] (l = ell_min..ell_max) and their cubic-spline time derivative: LdtVector / LLMatrix /
- * angular_velocity of scri/mode_calculations.py:46-57, 298-313, 403-432.  Outputs are host arrays; any may be NULL. */
+ * angular_velocity of scri/mode_calculations.py:46-57, 298-313, 403-432.  Outputs are host arrays; any may be NULL.
+ * A time step's modes and their derivatives are held in the LDS of one workgroup: a range of more modes than fit
+ * (5120 with 160 KB: l = 0..70 is the largest range from 0) is BMS_ERR_UNSUPPORTED, here and in bms_corotating_frame /
+ * bms_coprecessing_frame, before anything is launched. */
 int bms_angular_velocity(bms_ctx* ctx, const double* t, int64_t n_times, const void* data, int64_t ld, int ell_min, int ell_max,
                          int mem, double* ldt_out, double* ll_out, double* omega_out);
 

@@ -233,6 +233,9 @@ extern "C" int bms_angular_velocity(bms_ctx* c, const double* t, int64_t n, cons
   if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
   const int n_modes = LM_total_size(ell_min, ell_max);
   if (ld < n_modes) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
+  if (!angular_velocity_supported(n_modes))
+    return fail(c, BMS_ERR_UNSUPPORTED, "%d modes (ell = %d .. %d): the angular-velocity kernel holds a time step's modes and their derivatives in LDS and takes at most %d modes",
+                n_modes, ell_min, ell_max, angular_velocity_max_modes());
   for (int64_t i = 1; i < n; ++i)
     if (!(t[i] > t[i - 1])) return fail(c, BMS_ERR_INVALID, "time array must be strictly increasing (index %lld)", (long long)i);
   int rc;

@@ -119,6 +119,9 @@ int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, int* n_modes)
   if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
   *n_modes = LM_total_size(ell_min, ell_max);
   if (ld < *n_modes) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
+  if (!angular_velocity_supported(*n_modes))
+    return fail(c, BMS_ERR_UNSUPPORTED, "%d modes (ell = %d .. %d): the angular-velocity kernel holds a time step's modes and their derivatives in LDS and takes at most %d modes",
+                *n_modes, ell_min, ell_max, angular_velocity_max_modes());
   return BMS_OK;
 }
 

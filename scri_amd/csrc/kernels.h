@@ -16,13 +16,23 @@ namespace bms {
 // y extent of a launch grid (HIP: 65 535); launchers whose y counts time tiles cut longer launches into slices or refuse them
 constexpr long long GRID_Y_MAX = 65535;
 
+// LDS one workgroup can have on device `dev`: asked of the device (the opt-in limit where the runtime reports one, else the per-block
+// limit; this library only runs on gfx950, whose 160 KB is the floor assumed when neither query answers with more than the 64 KB
+// default).
+inline int lds_per_workgroup(int dev) {
+  int lds = 0, v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess) lds = std::max(lds, v);
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess) lds = std::max(lds, v);
+  (void)hipGetLastError();
+  if (lds <= 64 * 1024) lds = 160 * 1024;
+  return lds;
+}
+
 // Dynamic LDS beyond 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize on the kernel.  It is set ONCE per (kernel, device), to
-// everything the CU has beyond the kernel's static LDS: a per-launch value is a race between host threads that launch the same kernel
-// with different sizes (thread A sets 124 KB, thread B sets 60 KB, A's launch is refused) -- contexts are meant to be driven from
-// several threads (include/scri_amd.h).
-// The per-CU LDS size is asked of the device (the opt-in limit where the runtime reports one, else the per-block limit; this library
-// only runs on gfx950, whose 160 KB is the floor assumed when neither query answers with more than the 64 KB default).  Only a SUCCESS
-// is remembered: a transient failure is tried again by the next launch instead of failing that kernel for the life of the process.
+// everything the CU has beyond the kernel's static LDS (lds_per_workgroup): a per-launch value is a race between host threads that
+// launch the same kernel with different sizes (thread A sets 124 KB, thread B sets 60 KB, A's launch is refused) -- contexts are meant
+// to be driven from several threads (include/scri_amd.h).  Only a SUCCESS is remembered: a transient failure is tried again by the
+// next launch instead of failing that kernel for the life of the process.
 inline hipError_t allow_dynamic_lds(const void* fn) {
   static std::mutex mu;
   static std::map<std::pair<const void*, int>, bool> done;
@@ -31,11 +41,7 @@ inline hipError_t allow_dynamic_lds(const void* fn) {
   std::lock_guard<std::mutex> guard(mu);
   const auto key = std::make_pair(fn, dev);
   if (done.count(key)) return hipSuccess;
-  int lds = 0, v = 0;
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess) lds = std::max(lds, v);
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess) lds = std::max(lds, v);
-  (void)hipGetLastError();
-  if (lds <= 64 * 1024) lds = 160 * 1024;
+  const int lds = lds_per_workgroup(dev);
   hipFuncAttributes attr;
   hipError_t e = hipFuncGetAttributes(&attr, fn);
   if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds - (int)attr.sharedSizeBytes);
@@ -324,6 +330,11 @@ hipError_t launch_cmul(hipStream_t stream, const double* a, const double* b, dou
 // derivative Fdot, both c16[n][ld/2] (scri/mode_calculations.py:14-57, 209-313, 403-432)
 hipError_t launch_angular_velocity(hipStream_t stream, const double* F, const double* Fdot, long long ld, long long n_times,
                                    int ell_min, int n_modes, double* ldt_out, double* ll_out, double* omega_out);
+// The kernel keeps the two rows of a time step in LDS, one wave per step: the launcher takes 4, 2 or 1 waves per workgroup, the most
+// whose rows fit.  angular_velocity_max_modes: the most modes one wave's rows can hold on the current device (5120 with 160 KB);
+// angular_velocity_supported: whether n_modes is within that.  The entries ask before they launch anything.
+int angular_velocity_max_modes();
+bool angular_velocity_supported(int n_modes);
 
 // ---- frame construction (kernels_frames.hip): rotors f8[n][4] = (w, x, y, z)
 struct Vec4 {

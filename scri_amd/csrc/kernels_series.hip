@@ -13,7 +13,7 @@
 namespace bms {
 
 // ------------------------------------------------------------------------------------------------ slopes at the knots
-// Thread (column, tile): s_j = r'_j - C_j s_{j+1}, started `halo` knots above the tile (0.268^halo decay), written for
+// Thread (column, tile): s_j = r'_j - C_j s_{j+1}, started `halo` knots above the tile (0.268^halo decay on uniform steps: kernels_spline.hip), written for
 // the knots of the tile.  R and S must be different buffers (a tile's start-up reads r' of its neighbour).
 __global__ __launch_bounds__(64) void spline_slopes_kernel(const double* __restrict__ R, double* __restrict__ S, long long ld,
                                                            int n_cols, long long n, const SplineTable* __restrict__ table,
@@ -459,11 +459,27 @@ __global__ __launch_bounds__(256) void angular_velocity_kernel(const double* __r
   }
 }
 
+// bytes of LDS per wave: its row of modes and its row of time derivatives
+static size_t angular_velocity_wave_bytes(int n_modes) { return (size_t)2 * n_modes * sizeof(double2); }
+
+int angular_velocity_max_modes() {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  return (int)((size_t)lds_per_workgroup(dev) / angular_velocity_wave_bytes(1));
+}
+bool angular_velocity_supported(int n_modes) { return n_modes >= 0 && n_modes <= angular_velocity_max_modes(); }
+
 hipError_t launch_angular_velocity(hipStream_t stream, const double* F, const double* Fdot, long long ld, long long n_times,
                                    int ell_min, int n_modes, double* ldt_out, double* ll_out, double* omega_out) {
   if (n_times <= 0) return hipSuccess;
-  const int waves = 4;
-  const size_t lds = (size_t)waves * 2 * n_modes * sizeof(double2);
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const size_t room = (size_t)lds_per_workgroup(dev);
+  // the kernel takes its wave count from blockDim: 4 waves per workgroup while their rows fit, then 2, then 1
+  int waves = 4;
+  while (waves > 1 && (size_t)waves * angular_velocity_wave_bytes(n_modes) > room) waves >>= 1;
+  const size_t lds = (size_t)waves * angular_velocity_wave_bytes(n_modes);
+  if (lds > room) return hipErrorInvalidValue;  // (the entries refuse such a range by angular_velocity_supported, with a message)
   if (lds > 64 * 1024) {
     hipError_t e = allow_dynamic_lds((const void*)angular_velocity_kernel);
     if (e != hipSuccess) return e;

@@ -8,9 +8,15 @@
 // right-hand sides differ) and is evaluated at u_eval = u'/k_p + alpha_p.  The Thomas factors of the shared
 // matrix are computed once (SplineTable); per column the fit costs 3 FMA per knot forward and 1 backward.
 //
-// The inverse of the (strictly diagonally dominant, ratio 1/2) spline matrix decays like (2 - sqrt 3)^n
-// = 0.268^n, for any knot spacing, so the time axis is cut into tiles whose recurrences start `halo` knots
-// outside the tile (0.268^32 = 5e-19: below fp64 rounding of the global solve).  That gives
+// On uniform steps the inverse of the spline matrix decays like (2 - sqrt 3)^n = 0.268^n, so the time axis is cut
+// into tiles whose recurrences start `halo` knots outside the tile (0.268^32 = 5e-19: below fp64 rounding of the
+// global solve).  For arbitrary steps the matrix (strictly diagonally dominant, ratio 1/2) only promises 1/2 per
+// knot -- 0.5^32 = 2e-10 -- and steps that keep shrinking by a large factor come close to it: a recurrence factor
+// C_j = h_{j-1} / (2 (h_{j-1} + h_j) - h_j C_{j-1}) tends to 1/2 as h_{j-1} / h_j grows.  What keeps 32 knots of
+// run-in sufficient is the mesh guard (spline_tile_for, walk_time_axis): an axis whose steps differ by more than
+// 1e3 within 48 knots is not tiled at all (a sustained ratio of 1e3^(1/48) = 1.15 per knot gives C = 0.29,
+// 0.29^32 = 6e-18).  tests/test_gpu_spline_edges.py holds axes on both sides of that guard to the
+// extended-precision reference.  The tiles give
 // n_pix x n_tiles independent threads, lanes across adjacent pixels (16 B coalesced complex accesses),
 // marching in time.  Both kernels are HBM-bound streaming passes.
 #include <cstdlib>
@@ -257,7 +263,7 @@ __global__ __launch_bounds__(64) void spline_backward_eval_kernel(
 
   long long jE = jI + halo;
   if (jE > jend - 1) jE = jend - 1;
-  // s at jE: exact at the true last knot, otherwise the truncated start (decays as 0.268^halo)
+  // s at jE: exact at the true last knot, otherwise the truncated start (decays as 0.268^halo on uniform steps; see the header)
   double2 s1 = ld2(rp, jE);
   {
     long long j = jE - 1;
