@@ -434,6 +434,29 @@ int bms_multishuffle(bms_ctx* ctx, const void* in, void* out, int mem, int64_t n
 /* fletcher32(data): 16-bit words, modulus 65535; returns c1 << 16 | c0 */
 int bms_fletcher32(bms_ctx* ctx, const void* data, int mem, int64_t n_bytes, uint32_t* checksum);
 
+/* ---- the corotating paired-XOR storage form (scri/SpEC/file_io/corotating_paired_xor.py: the in-memory core of save, :70-90, and
+ * of load, :240,255), one fused kernel each way.  The files themselves (HDF5, JSON) are the caller's business.
+ * pack: data c16[n_times][ld] (ld >= n_modes), modes l = ell_min .. ell_max of a waveform ALREADY in the corotating frame ->
+ * words_out u64[n_times][2 n_modes].  Per time step: conjugate pairs s = (f[l,m] + conj f[l,-m]) / sqrt2 in column +m,
+ * d = (f[l,m] - conj f[l,-m]) / sqrt2 in column -m (waveform_modes.py:659-685); every real and imaginary part rounded to a multiple
+ * of 2^-e, e = floor(-log2(norm tolerance / sqrt(n_modes))) with the norm of that time step (:458-476); -0.0 replaced by +0.0; XOR with
+ * the packed words of the previous time step (utilities.py:195-217).  The arithmetic is the reference's operation for operation, so
+ * the words equal its own wherever the norm's exponent does not hinge on the order of the norm's sum.
+ * A time step that cannot be packed -- a non-finite value, zero norm (the reference stores NaN there), 2^e outside the doubles -- fails
+ * the call with BMS_ERR_INVALID; *first_bad_row (optional) is the first such row, -1 if there is none, and words_out is then not to be used.
+ * BMS_ERR_INVALID also for tolerance <= 0, ld < n_modes and words_out overlapping data.  `mem` as everywhere: host arrays are staged
+ * (in pieces under the work-space cap, each with the row before it; the words do not depend on the pieces), device arrays (16-byte
+ * aligned) are used in place. */
+int bms_pack_paired_xor(bms_ctx* ctx, const void* data, int64_t ld, int64_t n_times, int ell_min, int ell_max, int mem,
+                        double tolerance, void* words_out, int64_t* first_bad_row);
+/* unpack: words u64[n_times][2 n_modes] -> data_out c16[n_times][ld_out]: the running XOR down the time steps (utilities.py:220-232)
+ * with f[l,m] = (s + d) / sqrt2, f[l,-m] = conj(s - d) / sqrt2 (waveform_modes.py:688-703) on the way out.  Pieces of a host array
+ * pass the running XOR on.  data_out must not overlap words. */
+int bms_unpack_paired_xor(bms_ctx* ctx, const void* words, int64_t n_times, int ell_min, int ell_max, int mem, void* data_out,
+                          int64_t ld_out);
+/* rows one tile of the pack kernel owns (tests place series lengths around it); a size, not a status */
+int64_t bms_paired_xor_tile_rows(void);
+
 /* ---- extrapolation of finite-radius waveforms to null infinity (scri/extrapolation.py:1270-1474, _Extrapolate) ------------
  * For every time step t and order N = orders[o]: the constant term of the least-squares polynomial of degree N in x = 1/r through
  * the n_radii points (1 / radii[i][t], series[i][t][m]), for each mode m -- numpy.polynomial.polynomial.polyfit(x, y, N)[0] of

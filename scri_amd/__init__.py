@@ -113,3 +113,7 @@ for _name, _module in (("map_to_superrest_frame", _superrest), ("map_to_abd_fram
     _sys.modules[f"{__name__}.asymptotic_bondi_data.{_name}"] = _module  # (`from scri_amd.asymptotic_bondi_data.bms_charges import ...`)
 _sys.modules[__name__ + ".SpEC"] = SpEC
 _sys.modules[__name__ + ".SpEC.file_io"] = file_io
+# the storage format lives under the readers' package there (scri/SpEC/file_io/corotating_paired_xor.py)
+from . import corotating_paired_xor  # noqa: E402,F401
+file_io.corotating_paired_xor = corotating_paired_xor
+_sys.modules[__name__ + ".SpEC.file_io.corotating_paired_xor"] = corotating_paired_xor

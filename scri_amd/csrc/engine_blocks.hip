@@ -719,3 +719,141 @@ extern "C" int bms_fletcher32(bms_ctx* c, const void* data, int mem, int64_t n_b
   *checksum = (uint32_t)((acc[1] % 65535) << 16 | (acc[0] % 65535));
   return BMS_OK;
 } BMS_CATCH(c)
+
+// ---------------------------------------------------------------------------------------------- corotating paired-XOR storage form
+// scri/SpEC/file_io/corotating_paired_xor.py:70-90 (pack) and :240,255 (unpack) on the modes of a corotating-frame waveform
+// (kernels_bits.hip).  The plan is host work only: the argument checks, the column tables and the pieces a host array goes through.
+struct PairedPlan {
+  int n_modes = 0, n_own = 0;
+  std::vector<int> partner, own;  // column of (l, -m) per column; the columns with m >= 0
+  int64_t piece_rows = 0;         // rows of one piece (the whole series for device memory)
+};
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// modes c16[n_times][ld_modes] on one side, words u64[n_times][2 n_modes] on the other; per row of a piece the device holds both
+BMS_INTERNAL int plan_paired_xor(bms_ctx* c, const char* who, const void* modes, int64_t ld_modes, const void* words, int64_t n_times,
+                                 int ell_min, int ell_max, int mem, PairedPlan& P) {
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "%s: mem is BMS_HOST or BMS_DEVICE, got %d", who, mem);
+  if (n_times < 0) return fail(c, BMS_ERR_INVALID, "%s: negative n_times", who);
+  if (ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "%s: need 0 <= ell_min <= ell_max, got [%d, %d]", who, ell_min, ell_max);
+  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "%s: ell_max = %d beyond %d", who, ell_max, MAX_ELL);
+  const long long n_modes = (long long)(ell_max + 1) * (ell_max + 1) - (long long)ell_min * ell_min;
+  if (paired_pack_lds_bytes((int)n_modes) > PAIRED_PACK_MAX_LDS)
+    return fail(c, BMS_ERR_UNSUPPORTED, "%s: a row of %lld modes does not fit the %zu bytes of LDS the pack kernel stages it in", who, n_modes,
+                PAIRED_PACK_MAX_LDS);
+  if (ld_modes < n_modes) return fail(c, BMS_ERR_INVALID, "%s: row stride %lld is less than the %lld modes of l = %d .. %d", who, (long long)ld_modes, n_modes, ell_min, ell_max);
+  if (n_times > 0 && (!modes || !words)) return fail(c, BMS_ERR_INVALID, "%s: null array", who);
+  if (n_times > 0) {
+    const size_t modes_bytes = ((size_t)(n_times - 1) * (size_t)ld_modes + (size_t)n_modes) * 16, words_bytes = (size_t)n_times * (size_t)n_modes * 16;
+    if (ranges_overlap(modes, modes_bytes, words, words_bytes)) return fail(c, BMS_ERR_INVALID, "%s: the modes and the words must not overlap", who);
+    if (mem == BMS_DEVICE && (((uintptr_t)modes | (uintptr_t)words) & 15)) return fail(c, BMS_ERR_INVALID, "%s: device arrays must be 16-byte aligned", who);
+  }
+  P.n_modes = (int)n_modes;
+  P.partner.resize((size_t)n_modes);
+  P.own.clear();
+  for (int l = ell_min; l <= ell_max; ++l)
+    for (int m = -l; m <= l; ++m) {
+      const int j = l * (l + 1) - ell_min * ell_min + m;
+      P.partner[(size_t)j] = l * (l + 1) - ell_min * ell_min - m;
+      if (m >= 0) P.own.push_back(j);
+    }
+  P.n_own = (int)P.own.size();
+  // a host array beyond the work-space cap goes through in pieces: 32 n_modes bytes per row (modes and words)
+  P.piece_rows = n_times;
+  if (mem == BMS_HOST && n_times > 0) {
+    const uint64_t per_row = 32ull * (uint64_t)n_modes;
+    P.piece_rows = (int64_t)std::min<uint64_t>((uint64_t)n_times, std::max<uint64_t>(1, c->ws_limit / per_row));
+  }
+  return BMS_OK;
+}
+
+// (a size, not a status: entries that return `int` return a status, negative on failure)
+extern "C" int64_t bms_paired_xor_tile_rows(void) { return PAIRED_PACK_TILE; }
+
+extern "C" int bms_pack_paired_xor(bms_ctx* c, const void* data, int64_t ld, int64_t n_times, int ell_min, int ell_max, int mem,
+                                   double tolerance, void* words_out, int64_t* first_bad_row) try {
+  if (!c) return BMS_ERR_INVALID;
+  if (first_bad_row) *first_bad_row = -1;
+  if (!(tolerance > 0.0) || !std::isfinite(tolerance)) return fail(c, BMS_ERR_INVALID, "bms_pack_paired_xor: the tolerance must be positive and finite, got %g", tolerance);
+  PairedPlan P;
+  int rc;
+  if ((rc = plan_paired_xor(c, "bms_pack_paired_xor", data, ld, words_out, n_times, ell_min, ell_max, mem, P))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t S = c->stream;
+  const int n = P.n_modes;
+  const double tol_per_mode = tolerance / std::sqrt((double)n);  // waveform_modes.py:470
+  void* vp;
+  if ((rc = upload(c, "paired_partner", P.partner.data(), 4 * (size_t)n, &vp))) return rc;
+  const int* d_partner = (const int*)vp;
+  unsigned long long* d_bad;
+  if ((rc = dev_buf_t(c, "paired_bad", 1, &d_bad))) return rc;
+  HIP_TRY(c, hipMemsetAsync(d_bad, 0xff, 8, S));
+  if (mem == BMS_DEVICE) {
+    TIMED(c, BMS_TAG_POINTWISE, launch_paired_pack(S, data, ld, n_times, 0, d_partner, n, tol_per_mode, 0, words_out, d_bad));
+  } else {
+    double* d_in;
+    uint64_t* d_out;
+    if ((rc = dev_buf_t(c, "bits_in", (size_t)(P.piece_rows + 1) * n * 2, &d_in))) return rc;
+    if ((rc = dev_buf_t(c, "bits_out", (size_t)P.piece_rows * n * 2, &d_out))) return rc;
+    for (int64_t p0 = 0; p0 < n_times; p0 += P.piece_rows) {
+      const int64_t rows = std::min<int64_t>(P.piece_rows, n_times - p0);
+      const int halo = p0 > 0;  // the piece brings the row before it: its packed form is recomputed, as a tile inside a piece does
+      HIP_TRY(c, hipMemcpy2DAsync(d_in, (size_t)n * 16, (const char*)data + (size_t)(p0 - halo) * (size_t)ld * 16, (size_t)ld * 16, (size_t)n * 16,
+                                  (size_t)(rows + halo), hipMemcpyHostToDevice, S));
+      TIMED(c, BMS_TAG_POINTWISE, launch_paired_pack(S, d_in, n, rows, halo, d_partner, n, tol_per_mode, p0, d_out, d_bad));
+      HIP_TRY(c, hipMemcpyAsync((char*)words_out + (size_t)p0 * n * 16, d_out, (size_t)rows * n * 16, hipMemcpyDeviceToHost, S));
+    }
+  }
+  unsigned long long bad = ~0ull;
+  HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, S));
+  HIP_TRY(c, hipStreamSynchronize(S));
+  if (bad != ~0ull) {
+    if (first_bad_row) *first_bad_row = (int64_t)bad;
+    return fail(c, BMS_ERR_INVALID, "bms_pack_paired_xor: row %lld cannot be packed (a non-finite value, zero norm, or a scale beyond the range of ldexp)",
+                (long long)bad);
+  }
+  return BMS_OK;
+} BMS_CATCH(c)
+
+extern "C" int bms_unpack_paired_xor(bms_ctx* c, const void* words, int64_t n_times, int ell_min, int ell_max, int mem, void* data_out,
+                                     int64_t ld_out) try {
+  if (!c) return BMS_ERR_INVALID;
+  PairedPlan P;
+  int rc;
+  if ((rc = plan_paired_xor(c, "bms_unpack_paired_xor", data_out, ld_out, words, n_times, ell_min, ell_max, mem, P))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t S = c->stream;
+  const int n = P.n_modes;
+  void* vp;
+  if ((rc = upload(c, "paired_partner", P.partner.data(), 4 * (size_t)n, &vp))) return rc;
+  const int* d_partner = (const int*)vp;
+  if ((rc = upload(c, "paired_own", P.own.data(), 4 * (size_t)P.n_own, &vp))) return rc;
+  const int* d_own = (const int*)vp;
+  uint64_t *d_carry, *d_seed;
+  if ((rc = dev_buf_t(c, "bits_carry", (size_t)paired_unpack_carry_words(P.piece_rows, n), &d_carry))) return rc;
+  if ((rc = dev_buf_t(c, "paired_seed", (size_t)2 * n, &d_seed))) return rc;
+  HIP_TRY(c, hipMemsetAsync(d_seed, 0, (size_t)n * 16, S));
+  if (mem == BMS_DEVICE) {
+    TIMED(c, BMS_TAG_POINTWISE, launch_paired_unpack(S, words, n_times, d_own, P.n_own, d_partner, n, d_carry, d_seed, data_out, ld_out));
+  } else {
+    uint64_t* d_in;
+    double* d_out;
+    if ((rc = dev_buf_t(c, "bits_in", (size_t)P.piece_rows * n * 2, &d_in))) return rc;
+    if ((rc = dev_buf_t(c, "bits_out", (size_t)P.piece_rows * n * 2, &d_out))) return rc;
+    for (int64_t p0 = 0; p0 < n_times; p0 += P.piece_rows) {  // the running XOR passes from piece to piece in d_seed
+      const int64_t rows = std::min<int64_t>(P.piece_rows, n_times - p0);
+      HIP_TRY(c, hipMemcpyAsync(d_in, (const char*)words + (size_t)p0 * n * 16, (size_t)rows * n * 16, hipMemcpyHostToDevice, S));
+      TIMED(c, BMS_TAG_POINTWISE, launch_paired_unpack(S, d_in, rows, d_own, P.n_own, d_partner, n, d_carry, d_seed, d_out, n));
+      HIP_TRY(c, hipMemcpy2DAsync((char*)data_out + (size_t)p0 * (size_t)ld_out * 16, (size_t)ld_out * 16, d_out, (size_t)n * 16, (size_t)n * 16, (size_t)rows,
+                                  hipMemcpyDeviceToHost, S));
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(S));
+  return BMS_OK;
+} BMS_CATCH(c)

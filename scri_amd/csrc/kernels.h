@@ -415,6 +415,21 @@ hipError_t launch_multishuffle(hipStream_t stream, const void* in, void* out, lo
 // acc[0] += sum d_j mod 65535-ish, acc[1] += sum (N-j) d_j (both to be reduced mod 65535 by the caller); acc zeroed before
 hipError_t launch_fletcher32(hipStream_t stream, const void* data, long long n_words, unsigned long long* acc);
 
+// the corotating paired-XOR storage form (scri/SpEC/file_io/corotating_paired_xor.py:70-90, :240,255), one kernel each way.
+// partner[n_modes]: column of (l, -m) for column (l, m); own[n_own]: the columns with m >= 0.  Pointers 16-byte aligned.
+constexpr int PAIRED_PACK_TILE = 32;               // rows one wave packs in sequence (plus the halo row before them)
+constexpr int PAIRED_UNPACK_TILE = 64;             // rows per tile of the running XOR
+constexpr size_t PAIRED_PACK_MAX_LDS = 160 * 1024;  // the pack kernel stages 36 bytes per mode
+size_t paired_pack_lds_bytes(int n_modes);
+// in c16[n_out + halo][ld] -> out u64[n_out][2 n_modes]; halo = 1: row 0 of `in` is only the row before output row 0 (a piece of a
+// longer series).  bad: min over the rows that could not be packed of row_base + output row (preset to all ones).
+hipError_t launch_paired_pack(hipStream_t stream, const void* in, long long ld, long long n_out, int halo, const int* partner, int n_modes,
+                              double tol_per_mode, long long row_base, void* out, unsigned long long* bad);
+long long paired_unpack_carry_words(long long n_rows, int n_modes);
+// words u64[n_rows][2 n_modes] -> out c16[n_rows][ld_out]; seed u64[2 n_modes]: running XOR before row 0 on entry, after the last row on exit
+hipError_t launch_paired_unpack(hipStream_t stream, const void* words, long long n_rows, const int* own, int n_own, const int* partner,
+                                int n_modes, void* carry, void* seed, void* out, long long ld_out);
+
 // ---- pointwise helpers
 // Y[t][p] += coeff * Yaux[t][p] * X[t][p]^power,  X = (x_t - alpha_p) * xa_p - xb_p   (waveform_grid.py:516-550)
 hipError_t launch_psi_mix(hipStream_t stream, double* Y, const double* Yaux, long long ld, int n_pix, long long n_rows,

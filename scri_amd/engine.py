@@ -1194,3 +1194,60 @@ def salm2map(modes, spin, ell_max, n_theta, n_phi, ctx=None):
     rc = _lib.load().bms_salm2map(ctx.handle, vptr(a2), BMS_HOST, a2.shape[0], int(spin), int(ell_max), int(n_theta), int(n_phi), vptr(out))
     ctx.check(rc, "bms_salm2map")
     return out.reshape(lead + (n_theta, n_phi))
+
+
+# ---------------------------------------------------------------------------------- corotating paired-XOR storage form
+
+
+def paired_xor_tile_rows():
+    """rows one tile of the pack kernel owns (bms_paired_xor_tile_rows)"""
+    return int(_lib.load().bms_paired_xor_tile_rows())
+
+
+def pack_paired_xor(data, ell_min, ell_max, tolerance, ctx=None):
+    """bms_pack_paired_xor: modes [n, n_modes] of a corotating-frame waveform -> packed words [n, 2 n_modes] (conjugate pairs,
+    truncation at `tolerance`, -0.0 -> +0.0, XOR of successive time steps).  A numpy array gives a numpy uint64 array; a device tensor
+    (torch complex128, unit column stride) gives a torch int64 tensor that stays in HBM.  ValueError names the first time step that
+    cannot be packed (a non-finite value, zero norm)."""
+    ctx = _ctx(ctx)
+    n = int(data.shape[0])
+    ptr, ld, mem, keep = _modes_arg(data, n, ell_min, ell_max)
+    n_modes = LM_total_size(ell_min, ell_max)
+    if mem == BMS_DEVICE:
+        import torch
+
+        words = torch.empty((n, 2 * n_modes), dtype=torch.int64, device=data.device)
+        out_ptr = c_vp(words.data_ptr())
+    else:
+        words = np.empty((n, 2 * n_modes), dtype=np.uint64)
+        out_ptr = vptr(words)
+    bad = c_i64(-1)
+    rc = _lib.load().bms_pack_paired_xor(ctx.handle, ptr, ld, n, int(ell_min), int(ell_max), mem, float(tolerance), out_ptr, ctypes.byref(bad))
+    if rc == _lib.BMS_ERR_INVALID and bad.value >= 0:
+        raise ValueError(f"time step {bad.value} cannot be packed: it holds a non-finite value, has zero norm, or its truncation scale is "
+                         "beyond the range of the doubles")
+    ctx.check(rc, "bms_pack_paired_xor")
+    del keep
+    return words
+
+
+def unpack_paired_xor(words, ell_min, ell_max, ctx=None):
+    """bms_unpack_paired_xor: packed words [n, 2 n_modes] (numpy uint64, or a torch int64 tensor on the device) -> modes [n, n_modes]
+    (numpy complex128, or a torch complex128 tensor that stays in HBM)."""
+    ctx = _ctx(ctx)
+    n_modes = LM_total_size(ell_min, ell_max)
+    n = int(words.shape[0])
+    if tuple(words.shape) != (n, 2 * n_modes):
+        raise ValueError(f"words of shape {tuple(words.shape)} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
+    if hasattr(words, "data_ptr"):
+        import torch
+
+        words = words.contiguous()
+        out = torch.empty((n, n_modes), dtype=torch.complex128, device=words.device)
+        rc = _lib.load().bms_unpack_paired_xor(ctx.handle, c_vp(words.data_ptr()), n, int(ell_min), int(ell_max), BMS_DEVICE, c_vp(out.data_ptr()), n_modes)
+    else:
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        out = np.empty((n, n_modes), dtype=np.complex128)
+        rc = _lib.load().bms_unpack_paired_xor(ctx.handle, vptr(words), n, int(ell_min), int(ell_max), BMS_HOST, vptr(out), n_modes)
+    ctx.check(rc, "bms_unpack_paired_xor")
+    return out

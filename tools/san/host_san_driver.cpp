@@ -3,7 +3,7 @@
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
 // pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain and of the alignment entries, the planner and the per-step
-// math of the precessing sample waveform over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -451,6 +451,70 @@ void slab_allocator() {
   }
 }
 
+// The corotating paired-XOR entries (engine_blocks.hip): what they refuse before a device is touched, the column tables and the pieces a
+// host array goes through under work-space caps that give 1, 2 and several hundred pieces -- the pieces tile the series once, in order.
+void paired_xor_arguments() {
+  bms_ctx dummy;
+  std::vector<cplx> modes(40 * 12);
+  std::vector<uint64_t> words(40 * 24);
+  int64_t bad = 5;
+  REQUIRE(bms_pack_paired_xor(nullptr, modes.data(), 12, 40, 2, 3, BMS_HOST, 1e-10, words.data(), &bad) == BMS_ERR_INVALID);
+  for (double tol : {0.0, -1e-10, std::nan(""), HUGE_VAL}) {
+    REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, 40, 2, 3, BMS_HOST, tol, words.data(), &bad) == BMS_ERR_INVALID && bad == -1);
+    REQUIRE(std::strstr(bms_last_error(&dummy), "tolerance") != nullptr);
+  }
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 11, 40, 2, 3, BMS_HOST, 1e-10, words.data(), &bad) == BMS_ERR_INVALID);
+  REQUIRE(std::strstr(bms_last_error(&dummy), "row stride 11") != nullptr);
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, 40, 3, 2, BMS_HOST, 1e-10, words.data(), nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, 40, 2, 3, 9, 1e-10, words.data(), nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, -1, 2, 3, BMS_HOST, 1e-10, words.data(), nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_pack_paired_xor(&dummy, nullptr, 12, 40, 2, 3, BMS_HOST, 1e-10, words.data(), nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, 40, 2, 3, BMS_HOST, 1e-10, &modes[39 * 12 + 11], nullptr) == BMS_ERR_INVALID);  // the last input value
+  REQUIRE(std::strstr(bms_last_error(&dummy), "overlap") != nullptr);
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, 40, 2, 3, BMS_DEVICE, 1e-10, (char*)words.data() + 8, nullptr) == BMS_ERR_INVALID);  // alignment
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 12, 40, 2, MAX_ELL + 1, BMS_HOST, 1e-10, words.data(), nullptr) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(bms_pack_paired_xor(&dummy, modes.data(), 1 << 20, 40, 0, 100, BMS_HOST, 1e-10, words.data(), nullptr) == BMS_ERR_UNSUPPORTED);  // beyond the LDS
+  REQUIRE(bms_pack_paired_xor(&dummy, nullptr, 12, 0, 2, 3, BMS_HOST, 1e-10, nullptr, &bad) == BMS_OK && bad == -1);  // an empty series
+  REQUIRE(bms_unpack_paired_xor(nullptr, words.data(), 40, 2, 3, BMS_HOST, modes.data(), 12) == BMS_ERR_INVALID);
+  REQUIRE(bms_unpack_paired_xor(&dummy, words.data(), 40, 2, 3, BMS_HOST, modes.data(), 11) == BMS_ERR_INVALID);
+  REQUIRE(bms_unpack_paired_xor(&dummy, words.data(), 40, 2, 3, BMS_HOST, words.data() + 24, 12) == BMS_ERR_INVALID);
+  REQUIRE(bms_unpack_paired_xor(&dummy, words.data(), 0, 2, 3, BMS_HOST, modes.data(), 12) == BMS_OK);
+  REQUIRE(bms_paired_xor_tile_rows() == PAIRED_PACK_TILE);
+  const int ranges[][2] = {{2, 2}, {2, 8}, {0, 16}, {0, 24}, {3, 40}};
+  for (const auto& lr : ranges) {
+    const int ell_min = lr[0], ell_max = lr[1];
+    const int n_modes = (ell_max + 1) * (ell_max + 1) - ell_min * ell_min;
+    const int64_t n = 100000;
+    for (int want : {1, 2, 300}) {
+      const int64_t rows = (n + want - 1) / want;
+      dummy.ws_limit = (uint64_t)rows * 32ull * (uint64_t)n_modes + 7;
+      PairedPlan P;
+      // (nothing is read through the pointers: any two ranges apart do)
+      REQUIRE(plan_paired_xor(&dummy, "test", (const void*)0x1000, n_modes + 2, (const void*)((uintptr_t)1 << 40), n, ell_min, ell_max, BMS_HOST, P) == BMS_OK);
+      REQUIRE(P.n_modes == n_modes && (int)P.partner.size() == n_modes && P.piece_rows == rows);
+      int64_t covered = 0, count = 0;
+      for (int64_t p0 = 0; p0 < n; p0 += P.piece_rows, ++count) {
+        REQUIRE(p0 == covered);
+        covered = std::min<int64_t>(p0 + P.piece_rows, n);
+      }
+      REQUIRE(covered == n && count == (n + rows - 1) / rows && (count == want || want == 300));
+      REQUIRE(plan_paired_xor(&dummy, "test", (const void*)0x1000, n_modes, (const void*)((uintptr_t)1 << 40), n, ell_min, ell_max, BMS_DEVICE, P) == BMS_OK && P.piece_rows == n);
+      // the tables: the partner of the partner is the column itself, own columns are those not below their partner, each pair once
+      int pairs = 0;
+      for (int j = 0; j < n_modes; ++j) REQUIRE(P.partner[(size_t)j] >= 0 && P.partner[(size_t)j] < n_modes && P.partner[(size_t)P.partner[(size_t)j]] == j);
+      for (int k = 0; k < P.n_own; ++k) {
+        const int j = P.own[(size_t)k];
+        REQUIRE(j >= P.partner[(size_t)j] && (k == 0 || P.own[(size_t)k - 1] < j));
+        pairs += j == P.partner[(size_t)j] ? 1 : 2;
+      }
+      REQUIRE(pairs == n_modes && P.n_own == (n_modes + (ell_max - ell_min + 1)) / 2);
+    }
+    dummy.ws_limit = 1;  // a cap below one row: one row per piece, never none
+    PairedPlan P;
+    REQUIRE(plan_paired_xor(&dummy, "test", (const void*)0x1000, n_modes, (const void*)((uintptr_t)1 << 40), 10, ell_min, ell_max, BMS_HOST, P) == BMS_OK && P.piece_rows == 1);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -470,6 +534,7 @@ int main() {
   frame_chain_arguments();
   alignment_arguments();
   sample_waveform_plan();
+  paired_xor_arguments();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
