@@ -501,6 +501,33 @@ int bms_precessing_waveform(bms_ctx* ctx, const double* t, int64_t n, int ell_ma
 int bms_radius_terms(bms_ctx* ctx, const double* t, int64_t n, const void* h0, int64_t ld_h0, int64_t n_cols, int n_terms, double amp,
                      double radius, void* out, int64_t ld_out, int mem);
 
+/* ---- centre-of-mass drift of the horizon (or star) trajectories (scri/SpEC/com_motion.py) ---------------------------------------
+ * bms_com_motion: the track (:59-60, :112-118).  x_a, x_b f8[n][3], masses f8[n_m_a], f8[n_m_b] of length n or 1:
+ * com_out[n][3] = (m_A x_A + m_B x_B) / (m_A + m_B); with matter != 0 also t_out[n] = t / (m_A + m_B) and com_out / (m_A + m_B)
+ * (t and t_out may be NULL otherwise).  numpy's rounding steps in numpy's order: the result equals the numpy expression bit for bit.
+ * Every array lives in `mem`. */
+int bms_com_motion(bms_ctx* ctx, const double* t, const double* x_a, const double* x_b, const double* m_a, int64_t n_m_a, const double* m_b,
+                   int64_t n_m_b, int64_t n, int matter, int mem, double* t_out, double* com_out);
+/* bms_com_fit: estimate_avg_com_motion's arithmetic (:206-241) on t f8[n], com f8[n][3] in `mem`.  t_i = t[0] + (t[n-1] - t[0])
+ * skip_beginning_fraction, t_f = t[n-1] - (t[n-1] - t[0]) skip_ending_fraction; i_i, i_f the first index of the minimum of |t - t_i|,
+ * |t - t_f| (found on the device); C_k = scipy.integrate.simpson(y_k[i_i .. i_f], t[i_i .. i_f]) for y_0 = com, y_1 = fl(t com) and, with
+ * fit_acceleration, y_2 = fl(fl(t t) com) -- the irregular composite rule, the correction of the last interval for an even number of
+ * samples, the trapezoid for two, a zero divisor giving a zero quotient; then the position, velocity (and acceleration) that bring the
+ * track closest to the origin over [t_i, t_f].  Weights, sums and the closed form are carried in double-double and rounded to fp64 once:
+ * the result is the correctly rounded value of the rule on the fp64 inputs, and depends on nothing but them (fixed tiles, fixed order).
+ * BMS_ERR_INVALID for n < 2, a window of fewer than two samples (i_f <= i_i) and t_f == t_i; `result` then still names the window.
+ * NaN in the input propagates. */
+typedef struct {
+  double x_i[3], v_i[3], a_i[3]; /* a_i zero without fit_acceleration */
+  double t_i, t_f;
+  int64_t i_i, i_f;
+  double moments[3][3];          /* C_k[component] rounded to fp64; C_2 zero without fit_acceleration */
+} bms_com_fit_result;
+int bms_com_fit(bms_ctx* ctx, const double* t, const double* com, int64_t n, int mem, double skip_beginning_fraction,
+                double skip_ending_fraction, int fit_acceleration, bms_com_fit_result* result);
+/* panels (two intervals each) behind one partial sum of the moments (tests place window lengths around it); a size, not a status */
+int64_t bms_com_fit_tile_panels(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,3 +117,10 @@ _sys.modules[__name__ + ".SpEC.file_io"] = file_io
 from . import corotating_paired_xor  # noqa: E402,F401
 file_io.corotating_paired_xor = corotating_paired_xor
 _sys.modules[__name__ + ".SpEC.file_io.corotating_paired_xor"] = corotating_paired_xor
+# the centre-of-mass correction from the horizon trajectories (scri/SpEC/com_motion.py; its functions also on scri.SpEC, scri/SpEC/__init__.py:7)
+from . import com_motion as _com_motion  # noqa: E402
+SpEC.com_motion, SpEC.estimate_avg_com_motion, SpEC.remove_avg_com_motion = (
+    _com_motion.com_motion, _com_motion.estimate_avg_com_motion, _com_motion.remove_avg_com_motion)
+_sys.modules[__name__ + ".SpEC.com_motion"] = _com_motion
+# the PN model of the boosted centre-of-mass charge (scri/pn/boosted_comcharge.py)
+from . import pn  # noqa: E402,F401

@@ -69,6 +69,11 @@ class bms_precessing_params(ctypes.Structure):
                 ("derive_opening_angle_dot", c_int), ("derive_nutation_angle", c_int), ("coef", c_vp), ("power", c_dp)]
 
 
+class bms_com_fit_result(ctypes.Structure):
+    _fields_ = [("x_i", ctypes.c_double * 3), ("v_i", ctypes.c_double * 3), ("a_i", ctypes.c_double * 3), ("t_i", ctypes.c_double),
+                ("t_f", ctypes.c_double), ("i_i", c_i64), ("i_f", c_i64), ("moments", (ctypes.c_double * 3) * 3)]
+
+
 KERNEL_TAGS = ("rotate", "setup", "gemm_synthesis", "spline_forward", "spline_backward", "gemm_analysis", "pointwise", "theta_quadrature", "analysis_fused", "analysis_large")
 
 # every symbol include/scri_amd.h declares: (restype, argtypes)
@@ -182,6 +187,9 @@ SIGNATURES = {
     "bms_pack_paired_xor": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, ctypes.c_double, c_vp, ctypes.POINTER(c_i64)]),
     "bms_unpack_paired_xor": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_i64]),
     "bms_paired_xor_tile_rows": (c_i64, []),
+    "bms_com_motion": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp]),
+    "bms_com_fit": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.POINTER(bms_com_fit_result)]),
+    "bms_com_fit_tile_panels": (c_i64, []),
     "bms_salm2map": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_int, c_vp]),
     "bms_evaluate_modes": (c_int, [c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_int, c_int, c_dp, c_i64, c_vp]),
     "bms_mode_map": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, ctypes.POINTER(ctypes.c_int32), c_vp, c_int, c_vp, c_i64,

@@ -11,6 +11,7 @@
 //   engine_frames.hip    corotating / coprecessing frames built on the device                                (bms_corotating_frame ..., bms_dominant_axis ...)
 //   engine_align.hip     time-and-phase alignment from correlation moments                                   (bms_align_moments, bms_align_residual)
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
+//   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
 #pragma once
 #include <algorithm>
 #include <array>

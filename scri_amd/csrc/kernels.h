@@ -430,6 +430,17 @@ long long paired_unpack_carry_words(long long n_rows, int n_modes);
 hipError_t launch_paired_unpack(hipStream_t stream, const void* words, long long n_rows, const int* own, int n_own, const int* partner,
                                 int n_modes, void* carry, void* seed, void* out, long long ld_out);
 
+// centre-of-mass track and drift fit of the horizon trajectories (scri/SpEC/com_motion.py), kernels_com.hip
+constexpr int COM_FIT_TILE = 256;  // panels (two intervals each) per partial of the moment sums: one per thread of a workgroup
+constexpr int COM_FIT_OUT = 24;    // doubles of the fit's result block (com_fit_kernel)
+// com_out[n][3] = (m_A x_A + m_B x_B) / (m_A + m_B), masses of length n or 1; matter != 0: also t_out = t / m and com_out / m
+hipError_t launch_com_track(hipStream_t stream, const double* t, const double* xa, const double* xb, const double* ma, long long n_ma,
+                            const double* mb, long long n_mb, long long n, int matter, double* t_out, double* com_out);
+long long com_fit_work_doubles(long long n);
+// window, Simpson moments in double-double and the closed-form fit of t[n], com[n][3] (n >= 2) into out[COM_FIT_OUT]
+hipError_t launch_com_fit(hipStream_t stream, const double* t, const double* com, long long n, double skip_b, double skip_e, int accel,
+                          double* work, double* out);
+
 // ---- pointwise helpers
 // Y[t][p] += coeff * Yaux[t][p] * X[t][p]^power,  X = (x_t - alpha_p) * xa_p - xb_p   (waveform_grid.py:516-550)
 hipError_t launch_psi_mix(hipStream_t stream, double* Y, const double* Yaux, long long ld, int n_pix, long long n_rows,

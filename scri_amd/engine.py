@@ -1251,3 +1251,74 @@ def unpack_paired_xor(words, ell_min, ell_max, ctx=None):
         rc = _lib.load().bms_unpack_paired_xor(ctx.handle, vptr(words), n, int(ell_min), int(ell_max), BMS_HOST, vptr(out), n_modes)
     ctx.check(rc, "bms_unpack_paired_xor")
     return out
+
+
+# ---------------------------------------------------------------------------------- centre-of-mass track and drift fit
+
+
+def com_fit_tile_panels():
+    """panels (two intervals each) behind one partial sum of the moments (bms_com_fit_tile_panels)"""
+    return int(_lib.load().bms_com_fit_tile_panels())
+
+
+def _is_device_array(x):
+    return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
+
+
+def _com_arrays(ctx, arrays):
+    """float64 contiguous copies of `arrays` side by side: device tensors if any of them is one, numpy arrays otherwise"""
+    if any(_is_device_array(x) for x in arrays):
+        import torch
+
+        from . import device_series
+
+        _on_device_of(ctx, *[x for x in arrays if _is_device_array(x)])
+        dev = device_series.attach(ctx)  # (torch's copies and the engine's kernels on one stream)
+        arrays = [x.to(torch.float64).contiguous() if _is_device_array(x) else torch.as_tensor(np.asarray(x, dtype=float), device=dev).contiguous()
+                  for x in arrays]
+        return arrays, BMS_DEVICE, [c_vp(x.data_ptr()) for x in arrays]
+    arrays = [np.ascontiguousarray(x.numpy() if hasattr(x, "data_ptr") else x, dtype=float) for x in arrays]
+    return arrays, BMS_HOST, [vptr(x) for x in arrays]
+
+
+def com_track(t, x_a, x_b, m_a, m_b, matter=False, ctx=None):
+    """bms_com_motion: (t, CoM[n, 3]) with CoM = (m_A x_A + m_B x_B) / (m_A + m_B) of trajectories x_A, x_B [n, 3] and masses of length
+    n or 1, bit for bit the numpy expression; matter=True also divides t and CoM by m_A + m_B.  numpy arrays give numpy arrays; if any
+    trajectory is a device tensor everything stays (or is put) on the device and the results are device tensors."""
+    ctx = _ctx(ctx)
+    (t, x_a, x_b, m_a, m_b), mem, ptrs = _com_arrays(ctx, [t, x_a, x_b, m_a, m_b])
+    n = int(x_a.shape[0])
+    if tuple(x_a.shape) != (n, 3) or tuple(x_b.shape) != (n, 3) or tuple(t.shape) != (n,) or m_a.ndim != 1 or m_b.ndim != 1:
+        raise ValueError(f"trajectories of shapes {tuple(x_a.shape)}, {tuple(x_b.shape)} and times of shape {tuple(t.shape)} do not describe "
+                         f"{n} samples of two positions")
+    if mem == BMS_DEVICE:
+        import torch
+
+        com = torch.empty((n, 3), dtype=torch.float64, device=x_a.device)
+        t_out = torch.empty((n,), dtype=torch.float64, device=x_a.device) if matter else t
+        out_ptrs = (c_vp(t_out.data_ptr()), c_vp(com.data_ptr()))
+    else:
+        com = np.empty((n, 3))
+        t_out = np.empty(n) if matter else t
+        out_ptrs = (vptr(t_out), vptr(com))
+    rc = _lib.load().bms_com_motion(ctx.handle, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(m_a.shape[0]), ptrs[4], int(m_b.shape[0]), n, int(bool(matter)),
+                                    mem, out_ptrs[0] if matter else None, out_ptrs[1])
+    ctx.check(rc, "bms_com_motion")
+    return t_out, com
+
+
+def com_fit(t, com, skip_beginning_fraction=0.01, skip_ending_fraction=0.10, fit_acceleration=False, ctx=None):
+    """bms_com_fit on t [n], com [n, 3] (numpy arrays, or device tensors that stay where they are): a dict with x_i, v_i, a_i [3], t_i,
+    t_f, i_i, i_f and moments [3, 3] -- the window of the skip fractions, the Simpson moments of the track over it and the position,
+    velocity (and acceleration) that bring the track closest to the origin, correctly rounded."""
+    ctx = _ctx(ctx)
+    (t, com), mem, ptrs = _com_arrays(ctx, [t, com])
+    n = int(t.shape[0])
+    if t.ndim != 1 or tuple(com.shape) != (n, 3):
+        raise ValueError(f"times of shape {tuple(t.shape)} and a track of shape {tuple(com.shape)}: expected ({n},) and ({n}, 3)")
+    res = _lib.bms_com_fit_result()
+    rc = _lib.load().bms_com_fit(ctx.handle, ptrs[0], ptrs[1], n, mem, float(skip_beginning_fraction), float(skip_ending_fraction),
+                                 int(bool(fit_acceleration)), ctypes.byref(res))
+    ctx.check(rc, "bms_com_fit")
+    return dict(x_i=np.array(res.x_i), v_i=np.array(res.v_i), a_i=np.array(res.a_i), t_i=np.float64(res.t_i), t_f=np.float64(res.t_f),
+                i_i=int(res.i_i), i_f=int(res.i_f), moments=np.array([list(row) for row in res.moments]))

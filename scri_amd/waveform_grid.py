@@ -226,7 +226,12 @@ def transform(w_modes, **kwargs):
     # ... and `devices` = the GPUs of THIS process a long host-memory series is dealt over (engine.transform_modes; default SCRI_AMD_DEVICES)
     devices = kwargs.pop("devices", None)
     original_kwargs = kwargs.copy()
-    supertranslation, frame_rotation, boost_velocity, n_theta, n_phi, type_term, aux = _prepare(w_modes, kwargs, companion_objects=group is not None)
+    # weights in HBM (WaveformModes.to_device, always [n_times, n_modes]): the transformation reads and writes them there, companions included
+    resident = bool(getattr(w_modes, "is_device_resident", False))
+    if resident:  # (the history names the companions instead of printing them: printing one reads its weights back to the host)
+        original_kwargs = {k: (str(v) if isinstance(v, WaveformModes) else v) for k, v in original_kwargs.items()}
+    supertranslation, frame_rotation, boost_velocity, n_theta, n_phi, type_term, aux = _prepare(
+        w_modes, kwargs, companion_objects=group is not None or resident)
     s = w_modes.spin_weight
 
     # to_modes argument checks (waveform_grid.py:291-297)
@@ -281,16 +286,22 @@ def transform(w_modes, **kwargs):
         t_new, d = engine.transform_modes_series(w_modes.t, flat, w_modes.ell_min, w_modes.ell_max, s, w_modes.conformal_weight, type_term, tr,
                                                  aux=aux_flat, ctx=w_modes._ctx)
         data_new = d.reshape(d.shape[:2] + trailing)
-    elif getattr(w_modes, "is_device_resident", False) and not aux:
-        # weights in HBM (WaveformModes.to_device): the transformation reads and writes them there
+    elif resident:
         from . import device_series
         from .mode_algebra import LM_total_size
 
+        aux_dev = []  # a companion already in HBM is read where it is, a host one is uploaded for the call
+        for a in aux:
+            c = a[0]
+            if tuple(c._data_shape()[2:]):
+                raise ValueError("auxiliary waveforms must carry the same trailing data dimensions")
+            rows_c = c._dev if c.is_device_resident else device_series.to_device(w_modes._ctx, c.data)
+            aux_dev.append((rows_c,) + tuple(a[1:6]) + (int(rows_c.stride(0)) if rows_c.shape[0] > 1 else int(rows_c.shape[1]),))
         n_out = LM_total_size(ell_min_out, int(ell_max_out))
         out = device_series.empty(w_modes._ctx, (w_modes.n_times, n_out))
         t_new, n_new = engine.transform_modes(
             w_modes.t, w_modes._dev.data_ptr(), w_modes.ell_min, w_modes.ell_max, s, w_modes.conformal_weight, type_term, tr,
-            ctx=w_modes._ctx, device=True, ld=w_modes.n_modes, out_ptr=out.data_ptr(),
+            aux=[(a[0].data_ptr(),) + a[1:] for a in aux_dev], ctx=w_modes._ctx, device=True, ld=w_modes.n_modes, out_ptr=out.data_ptr(),
         )
         dev_out, data_new = out[:n_new], np.empty((0, 0))
     else:

@@ -3,7 +3,7 @@
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
 // pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain and of the alignment entries, the planner and the per-step
-// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -13,6 +13,7 @@
 #include "../../scri_amd/csrc/engine_frames.hip"
 #include "../../scri_amd/csrc/engine_align.hip"
 #include "../../scri_amd/csrc/engine_sample.hip"
+#include "../../scri_amd/csrc/engine_com.hip"
 
 #include <cstdio>
 #include <random>
@@ -515,6 +516,35 @@ void paired_xor_arguments() {
   }
 }
 
+// The centre-of-mass entries (engine_com.hip): what they refuse before a device is touched.
+void com_motion_arguments() {
+  bms_ctx dummy;
+  std::vector<double> t(9, 1.0), x(27, 2.0), m(9, 0.5), out(27);
+  bms_com_fit_result res;
+  REQUIRE(bms_com_fit(nullptr, t.data(), x.data(), 9, BMS_HOST, 0.01, 0.1, 0, &res) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_fit(&dummy, nullptr, x.data(), 9, BMS_HOST, 0.01, 0.1, 0, &res) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_fit(&dummy, t.data(), nullptr, 9, BMS_HOST, 0.01, 0.1, 0, &res) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_fit(&dummy, t.data(), x.data(), 9, BMS_HOST, 0.01, 0.1, 0, nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_fit(&dummy, t.data(), x.data(), 9, 5, 0.01, 0.1, 0, &res) == BMS_ERR_INVALID);
+  for (int64_t n : {(int64_t)1, (int64_t)0, (int64_t)-3}) REQUIRE(bms_com_fit(&dummy, t.data(), x.data(), n, BMS_HOST, 0.01, 0.1, 1, &res) == BMS_ERR_INVALID);
+  for (double f : {(double)std::nan(""), (double)HUGE_VAL}) {
+    REQUIRE(bms_com_fit(&dummy, t.data(), x.data(), 9, BMS_HOST, f, 0.1, 0, &res) == BMS_ERR_INVALID);
+    REQUIRE(bms_com_fit(&dummy, t.data(), x.data(), 9, BMS_HOST, 0.01, f, 0, &res) == BMS_ERR_INVALID);
+  }
+  REQUIRE(bms_com_motion(nullptr, t.data(), x.data(), x.data(), m.data(), 9, m.data(), 1, 9, 0, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_motion(&dummy, nullptr, nullptr, x.data(), m.data(), 9, m.data(), 1, 9, 0, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_motion(&dummy, nullptr, x.data(), x.data(), m.data(), 9, m.data(), 1, 9, 0, BMS_HOST, nullptr, nullptr) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_motion(&dummy, nullptr, x.data(), x.data(), m.data(), 9, m.data(), 1, 9, 1, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);  // matter needs t
+  REQUIRE(bms_com_motion(&dummy, t.data(), x.data(), x.data(), m.data(), 9, m.data(), 1, 9, 1, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);  // ... and t_out
+  REQUIRE(bms_com_motion(&dummy, t.data(), x.data(), x.data(), m.data(), 4, m.data(), 1, 9, 0, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_motion(&dummy, t.data(), x.data(), x.data(), m.data(), 9, m.data(), 0, 9, 0, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_motion(&dummy, t.data(), x.data(), x.data(), m.data(), 1, m.data(), 1, 0, 0, BMS_HOST, nullptr, out.data()) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_motion(&dummy, t.data(), x.data(), x.data(), m.data(), 9, m.data(), 9, 9, 0, 3, nullptr, out.data()) == BMS_ERR_INVALID);
+  REQUIRE(bms_com_fit_tile_panels() == COM_FIT_TILE);
+  REQUIRE(com_fit_work_doubles(2) == com_fit_work_doubles(3) && com_fit_work_doubles(2 * COM_FIT_TILE + 2) == com_fit_work_doubles(3));
+  REQUIRE(com_fit_work_doubles(2 * COM_FIT_TILE + 3) == com_fit_work_doubles(3) + 18);  // one more tile of double-double partials
+}
+
 }  // namespace
 
 int main() {
@@ -535,6 +565,7 @@ int main() {
   alignment_arguments();
   sample_waveform_plan();
   paired_xor_arguments();
+  com_motion_arguments();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
