@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 #include "wigner.h"
@@ -120,6 +121,59 @@ __global__ __launch_bounds__(256, NTJ <= 4 ? 3 : 2) void theta_synthesis_mfma_ke
 #undef TS_LOAD
 }
 
+// ---- what the two phi-stage kernels share.  Twiddles of a lane's B fragments: cos | sin (m phi_k), m = 4 s + fk + 1, k = 16 n + fi
+template <int KM, int NTC>
+__device__ __forceinline__ void phi_twiddles(double (&bc)[KM][NTC], double (&bs)[KM][NTC], int fi, int fk, int nk, int n_phi, int L) {
+#pragma unroll
+  for (int s = 0; s < KM; ++s)
+#pragma unroll
+    for (int n = 0; n < NTC; ++n) {
+      const int m = 4 * s + fk + 1, k = 16 * n + fi;
+      double sn = 0.0, co = 0.0;
+      if (k < nk && m <= L) sincospi(2.0 * (double)(((long long)m * k) % n_phi) / (double)n_phi, &sn, &co);
+      bc[s][n] = co, bs[s][n] = sn;
+    }
+}
+
+// A work item of mt per time step: (time step, tile of RS rings, live rings of that tile)
+struct PhiItem {
+  long long t;
+  int rt, rings;
+};
+template <int RS>
+__device__ __forceinline__ PhiItem phi_item(long long item, int mt, int n_theta) {
+  const long long t = item / mt;
+  const int rt = (int)(item - t * mt);
+  return {t, rt, n_theta - RS * rt < RS ? n_theta - RS * rt : RS};
+}
+
+// The folded products of one F tile in LDS, rows m = -L .. L of RS rings each from element `tile0` of `sm` on; this lane's operand
+// is ring `ag`, Re (part 0) or Im (part 1).  u = sum_m P_m cos, v = sum_m Q_m sin over the km k steps that carry an m <= L.
+// (`sm` and `tile0` stay apart and the index is formed here: handed `sm + tile0` as one pointer, every instance of the six-field
+// kernel took 16 to 33 registers more and <9, 4> spilled 50 instead of 18)
+template <int RS, int KM, int NTC>
+__device__ __forceinline__ void phi_folded_products(const double2* sm, int tile0, int ag, int part, int fk, int L, int km,
+                                                    const double (&bc)[KM][NTC], const double (&bs)[KM][NTC], v4d_t (&u)[NTC],
+                                                    v4d_t (&v)[NTC]) {
+#pragma unroll
+  for (int n = 0; n < NTC; ++n) u[n] = v[n] = v4d_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < KM; ++s) {
+    if (s < km) {
+      const int m = 4 * s + fk + 1;
+      const int mm = m <= L ? m : 0;  // (rows beyond L: their twiddles are zero)
+      const double2 fp = sm[tile0 + (L + mm) * RS + ag], fm = sm[tile0 + (L - mm) * RS + ag];
+      const double ap = part ? fp.y + fm.y : fp.x + fm.x;  // P_m = F_m + F_-m
+      const double aq = part ? fp.x - fm.x : fm.y - fp.y;  // Q_m = i (F_m - F_-m)
+#pragma unroll
+      for (int n = 0; n < NTC; ++n) {
+        u[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ap, bc[s][n], u[n], 0, 0, 0);
+        v[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bs[s][n], v[n], 0, 0, 0);
+      }
+    }
+  }
+}
+
 // ---- phi stage: Y[t][ring][k] = (sum_m F[t][m][ring] e^{i m phi_k} (- off[pixel] x the row's constant)) (x scale[pixel], the
 // conformal factor's power behind a boost along the grid's axis).  One wave per (time step, tile of 8 rings).
 template <int KM, int NTC>
@@ -134,17 +188,8 @@ __global__ __launch_bounds__(64) void phi_synthesis_folded_kernel(const double* 
   double2* Gt = sm + nm * 8;
   const int lane = threadIdx.x, fi = lane & 15, fk = lane >> 4;
   const int nk = n_phi / 2 + 1, mt = (n_theta + 7) / 8;
-  // twiddles of this lane's B fragments: cos / sin (m phi_k), m = 4 s + fk + 1, k = 16 n + fi
   double bc[KM][NTC], bs[KM][NTC];
-#pragma unroll
-  for (int s = 0; s < KM; ++s)
-#pragma unroll
-    for (int n = 0; n < NTC; ++n) {
-      const int m = 4 * s + fk + 1, k = 16 * n + fi;
-      double sn = 0.0, co = 0.0;
-      if (k < nk && m <= L) sincospi(2.0 * (double)(((long long)m * k) % n_phi) / (double)n_phi, &sn, &co);
-      bc[s][n] = co, bs[s][n] = sn;
-    }
+  phi_twiddles(bc, bs, fi, fk, nk, n_phi, L);
   const int km = (L + 3) / 4;  // k steps that carry an m <= L
   const long long n_items = n_rows * mt;
   // This lane's pieces of an item's F tile ((2L+1) x 8 rings, 128-byte pieces): element e = lane + 64 i is ring e & 7 of row e >> 3
@@ -152,9 +197,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_folded_kernel(const double* 
   double2 pre[NPRE];
 #define PS_LOAD(ITEM)                                                                                              \
   {                                                                                                                \
-    const long long t_ = (ITEM) / mt;                                                                              \
-    const int rt_ = (int)((ITEM)-t_ * mt);                                                                         \
-    const int rings_ = n_theta - 8 * rt_ < 8 ? n_theta - 8 * rt_ : 8;                                              \
+    const auto [t_, rt_, rings_] = phi_item<8>((ITEM), mt, n_theta);                                               \
     const double* f_ = F + ((t_ * nm) * (long long)jp + 8 * rt_) * 2;                                              \
     _Pragma("unroll") for (int i = 0; i < NPRE; ++i) {                                                             \
       const int e_ = lane + 64 * i;                                                                                \
@@ -166,9 +209,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_folded_kernel(const double* 
   // operand row fi of the products: ring (fi & 3) + 4 (fi >> 3) of the tile, Re (part 0) or Im (part 1)
   const int ag = (fi & 3) + 4 * (fi >> 3), part = (fi >> 2) & 1;
   for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const long long t = item / mt;
-    const int rt = (int)(item - t * mt);
-    const int rings = n_theta - 8 * rt < 8 ? n_theta - 8 * rt : 8;
+    const auto [t, rt, rings] = phi_item<8>(item, mt, n_theta);
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
       const int e = lane + 64 * i;
@@ -177,23 +218,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_folded_kernel(const double* 
     if (item + gridDim.x < n_items) PS_LOAD(item + gridDim.x)
     // (one wave: its LDS writes are visible to its own reads in program order)
     v4d_t u[NTC], v[NTC];
-#pragma unroll
-    for (int n = 0; n < NTC; ++n) u[n] = v[n] = v4d_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KM; ++s) {
-      if (s < km) {
-        const int m = 4 * s + fk + 1;
-        const int mm = m <= L ? m : 0;  // (rows beyond L: their twiddles are zero)
-        const double2 fp = Ft[(L + mm) * 8 + ag], fm = Ft[(L - mm) * 8 + ag];
-        const double ap = part ? fp.y + fm.y : fp.x + fm.x;  // P_m = F_m + F_-m
-        const double aq = part ? fp.x - fm.x : fm.y - fp.y;  // Q_m = i (F_m - F_-m)
-#pragma unroll
-        for (int n = 0; n < NTC; ++n) {
-          u[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ap, bc[s][n], u[n], 0, 0, 0);
-          v[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bs[s][n], v[n], 0, 0, 0);
-        }
-      }
-    }
+    phi_folded_products<8>(Ft, 0, ag, part, fk, L, km, bc, bs, u, v);
     // results: rows fk + 4 r = (Re, Im) of ring fk, (Re, Im) of ring fk + 4; column k = 16 n + fi
     const double cv = off ? cst[t * ldc] : 0.0;  // the row's eliminated-constant value (real: engine_abd.hip)
 #pragma unroll
@@ -269,15 +294,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_mix6_kernel(Mix6Args a, long
   const int lane = threadIdx.x, fi = lane & 15, fk = lane >> 4;
   const int nk = n_phi / 2 + 1, mt = (n_theta + 3) / 4;
   double bc[KM][NTC], bs[KM][NTC];
-#pragma unroll
-  for (int s = 0; s < KM; ++s)
-#pragma unroll
-    for (int n = 0; n < NTC; ++n) {
-      const int m = 4 * s + fk + 1, k = 16 * n + fi;
-      double sn = 0.0, co = 0.0;
-      if (k < nk && m <= L) sincospi(2.0 * (double)(((long long)m * k) % n_phi) / (double)n_phi, &sn, &co);
-      bc[s][n] = co, bs[s][n] = sn;
-    }
+  phi_twiddles(bc, bs, fi, fk, nk, n_phi, L);
   const int km = (L + 3) / 4;
   // This lane's pieces of a pass's two F tiles ((2L+1) x 4 rings each, 64-byte pieces): element e = lane + 64 i is ring e & 3 of
   // row (e >> 2) % nm of field e / (4 nm) of the pair
@@ -285,10 +302,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_mix6_kernel(Mix6Args a, long
   double2 pre[NPRE];
 #define M6_LOAD(ITEM, PASS)                                                                                             \
   {                                                                                                                     \
-    const long long item_ = (ITEM);                                                                                     \
-    const long long t_ = item_ / mt;                                                                                    \
-    const int rt_ = (int)(item_ - t_ * mt);                                                                             \
-    const int rings_ = n_theta - 4 * rt_ < 4 ? n_theta - 4 * rt_ : 4;                                                   \
+    const auto [t_, rt_, rings_] = phi_item<4>((ITEM), mt, n_theta);                                                    \
     const long long o_ = ((t_ * nm) * (long long)jp + 4 * rt_) * 2;                                                     \
     const double *fa_ = a.F[2 * (PASS)] + o_, *fb_ = a.F[2 * (PASS) + 1] + o_;                                          \
     _Pragma("unroll") for (int i = 0; i < NPRE; ++i) {                                                                  \
@@ -306,9 +320,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_mix6_kernel(Mix6Args a, long
   const long long n_items = n_rows * mt;
   if (blockIdx.x < n_items) M6_LOAD((long long)blockIdx.x, 0)
   for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const long long t = item / mt;
-    const int rt = (int)(item - t * mt);
-    const int rings = n_theta - 4 * rt < 4 ? n_theta - 4 * rt : 4;
+    const auto [t, rt, rings] = phi_item<4>(item, mt, n_theta);
     const long long pix0 = (long long)(4 * rt) * n_phi;
     const int n_el = rings * n_phi;
     // the per-pixel constants of the mixing are requested now and arrive under the three passes (asked for inside the mixing loop
@@ -333,24 +345,7 @@ __global__ __launch_bounds__(64) void phi_synthesis_mix6_kernel(Mix6Args a, long
       if (pass == 1) M6_LOAD(item, 2)
       if (pass == 2 && item + gridDim.x < n_items) M6_LOAD(item + gridDim.x, 0)
       v4d_t u[NTC], v[NTC];
-#pragma unroll
-      for (int n = 0; n < NTC; ++n) u[n] = v[n] = v4d_t{0.0, 0.0, 0.0, 0.0};
-      const double2* Fb = Ft + ab * 4 * nm;
-#pragma unroll
-      for (int s = 0; s < KM; ++s) {
-        if (s < km) {
-          const int m = 4 * s + fk + 1;
-          const int mm = m <= L ? m : 0;
-          const double2 fp = Fb[(L + mm) * 4 + ag], fm = Fb[(L - mm) * 4 + ag];
-          const double ap = part ? fp.y + fm.y : fp.x + fm.x;
-          const double aq = part ? fp.x - fm.x : fm.y - fp.y;
-#pragma unroll
-          for (int n = 0; n < NTC; ++n) {
-            u[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ap, bc[s][n], u[n], 0, 0, 0);
-            v[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bs[s][n], v[n], 0, 0, 0);
-          }
-        }
-      }
+      phi_folded_products<4>(Ft, ab * 4 * nm, ag, part, fk, L, km, bc, bs, u, v);
       // results: rows fk + 4 r = (Re, Im) of ring fk of the pair's first field, (Re, Im) of ring fk of its second; column k = 16 n + fi
       const double2 f0a = Ft[L * 4 + fk], f0b = Ft[4 * nm + L * 4 + fk];
       // (every read of the F tiles is done: their area now takes the results)
@@ -419,6 +414,50 @@ int large_synthesis_supported(int n_theta, int n_phi, int ell_min, int ell_max) 
   return n_theta >= 2 && n_theta <= 104 && n_phi >= 1 && nk <= 64 && ell_max >= 1 && ell_max <= 33 && ell_min >= 0 && ell_min <= ell_max;
 }
 
+// ---- which instance runs.  Both stages take their K loop in 5, 7 or 9 steps of four (l values | m pairs): go(K, N) launches
+// kernel<K, N>, its two template arguments handed over as std::integral_constant.
+template <int N, class Go>
+static hipError_t with_k_steps(int k, Go go) {
+  using std::integral_constant;
+  if (k <= 5) return go(integral_constant<int, 5>{}, integral_constant<int, N>{});
+  if (k <= 7) return go(integral_constant<int, 7>{}, integral_constant<int, N>{});
+  return go(integral_constant<int, 9>{}, integral_constant<int, N>{});
+}
+
+// phi stage, either kernel: KM by the m pairs up to L, NTC = 2, 3 or 4 column tiles of 16 over k = 0 .. n_phi / 2
+template <class Go>
+static hipError_t with_phi_instance(int n_phi, int L, Go go) {
+  const int km = (L + 3) / 4, ntc = (n_phi / 2 + 1 + 15) / 16;
+  if (ntc <= 2) return with_k_steps<2>(km, go);
+  if (ntc == 3) return with_k_steps<3>(km, go);
+  return with_k_steps<4>(km, go);
+}
+
+// theta stage alone (by itself for the six fields of the fused ABD route: one launch per field into its own F)
+hipError_t launch_theta_synthesis(hipStream_t stream, const double* A, long long lda, long long n_rows, int n_theta, int ell_min,
+                                  int ell_max, const double* Tsyn, double* F) {
+  if (n_rows <= 0) return hipSuccess;
+  const int L = ell_max, nm = 2 * L + 1, jp = large_analysis_jp(n_theta);
+  static const int rows_per_block = BMS_PROBE_ENV("SCRI_AMD_TS_ROWS") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TS_ROWS")) : 256;
+  const int kl = (L + 1 - ell_min + 3) / 4, ntj_all = (n_theta + 15) / 16;
+  // SCRI_AMD_TS_SPLIT=1 and more than four ring tiles (n_theta > 64): two workgroups per m, each with half of them
+  // (measured, round 4: 99 x 99 / l <= 24, 25 000 steps, six fields: 14.65 ms split against 13.09 ms whole -- three waves per SIMD at
+  // 153 registers do not make up for gathering every mode twice; off unless asked for)
+  static const int ts_split = BMS_PROBE_ENV("SCRI_AMD_TS_SPLIT") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TS_SPLIT")) : 0;
+  const int parts = ts_split && ntj_all > 4 ? 2 : 1;
+  const int ntj = (ntj_all + parts - 1) / parts;
+  const dim3 grid(nm, (unsigned)((n_rows + rows_per_block - 1) / rows_per_block), parts);
+  auto go = [&](auto KL, auto NTJ) {
+    hipLaunchKernelGGL((theta_synthesis_mfma_kernel<KL.value, NTJ.value>), grid, dim3(256), 0, stream, A, lda, n_rows, n_theta, L, ell_min,
+                       jp, rows_per_block, Tsyn, F);
+    return hipGetLastError();
+  };
+  if (ntj <= 3) return with_k_steps<3>(kl, go);
+  if (ntj == 4) return with_k_steps<4>(kl, go);
+  if (ntj <= 5) return with_k_steps<5>(kl, go);
+  return with_k_steps<7>(kl, go);
+}
+
 // A: [n_rows][lda] modes (complex; with `off` one more complex number per row at column n_modes: it multiplies `off`);
 // Tsyn[n_modes][n_theta]; F: n_rows x (2 ell_max + 1) x large_analysis_jp(n_theta) complex of work space; Y[n_rows][ldy];
 // scale: NULL or 2 doubles per pixel (the first is used) multiplying the result.
@@ -426,105 +465,18 @@ hipError_t launch_synthesis_large(hipStream_t stream, const double* A, long long
                                   int ell_min, int ell_max, const double* Tsyn, const double* off, double* F, double* Y,
                                   long long ldy, const double* scale) {
   if (n_rows <= 0) return hipSuccess;
+  hipError_t e = launch_theta_synthesis(stream, A, lda, n_rows, n_theta, ell_min, ell_max, Tsyn, F);
+  if (e != hipSuccess) return e;
   const int L = ell_max, nm = 2 * L + 1, jp = large_analysis_jp(n_theta);
   const int n_modes = (L + 1) * (L + 1) - ell_min * ell_min;
-  static const int rows_per_block = BMS_PROBE_ENV("SCRI_AMD_TS_ROWS") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TS_ROWS")) : 256;
-  const dim3 grid1(nm, (unsigned)((n_rows + rows_per_block - 1) / rows_per_block));
-  const int kl = (L + 1 - ell_min + 3) / 4, ntj_all = (n_theta + 15) / 16;
-  // SCRI_AMD_TS_SPLIT=1 and more than four ring tiles (n_theta > 64): two workgroups per m, each with half of them
-  // (measured, round 4: 99 x 99 / l <= 24, 25 000 steps, six fields: 14.65 ms split against 13.09 ms whole -- three waves per SIMD at
-  // 153 registers do not make up for gathering every mode twice; off unless asked for)
-  static const int ts_split = BMS_PROBE_ENV("SCRI_AMD_TS_SPLIT") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TS_SPLIT")) : 0;
-  const int parts = ts_split && ntj_all > 4 ? 2 : 1;
-  const int ntj = (ntj_all + parts - 1) / parts;
-  const dim3 grid1z(grid1.x, grid1.y, parts);
-#define TS_GO(KL, NTJ)                                                                                                      \
-  hipLaunchKernelGGL((theta_synthesis_mfma_kernel<KL, NTJ>), grid1z, dim3(256), 0, stream, A, lda, n_rows, n_theta, L, ell_min, jp, \
-                     rows_per_block, Tsyn, F)
-#define TS_KL(NTJ)  \
-  if (kl <= 5)      \
-    TS_GO(5, NTJ);  \
-  else if (kl <= 7) \
-    TS_GO(7, NTJ);  \
-  else              \
-    TS_GO(9, NTJ);
-  if (ntj <= 3) {
-    TS_KL(3)
-  } else if (ntj == 4) {
-    TS_KL(4)
-  } else if (ntj <= 5) {
-    TS_KL(5)
-  } else {
-    TS_KL(7)
-  }
-#undef TS_KL
-#undef TS_GO
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const int nk = n_phi / 2 + 1, mt = (n_theta + 7) / 8;
-  const int km = (L + 3) / 4, ntc = (nk + 15) / 16;
   const size_t lds = sizeof(double2) * ((size_t)nm * 8 + (size_t)8 * n_phi);
-  const long long items = n_rows * mt;
-  const unsigned grid2 = (unsigned)(items < 256 * 8 ? items : 256 * 8);
-#define PS_GO(KM, NTC)                                                                                                          \
-  hipLaunchKernelGGL((phi_synthesis_folded_kernel<KM, NTC>), dim3(grid2), dim3(64), lds, stream, F, n_rows, n_theta, n_phi, L, jp, off, \
-                     A + 2LL * n_modes, lda, scale, Y, ldy)
-#define PS_KM(NTC)  \
-  if (km <= 5)      \
-    PS_GO(5, NTC);  \
-  else if (km <= 7) \
-    PS_GO(7, NTC);  \
-  else              \
-    PS_GO(9, NTC);
-  if (ntc <= 2) {
-    PS_KM(2)
-  } else if (ntc == 3) {
-    PS_KM(3)
-  } else {
-    PS_KM(4)
-  }
-#undef PS_KM
-#undef PS_GO
-  return hipGetLastError();
-}
-
-// theta stage alone (the six fields of the fused ABD route: one launch per field into its own F)
-hipError_t launch_theta_synthesis(hipStream_t stream, const double* A, long long lda, long long n_rows, int n_theta, int ell_min,
-                                  int ell_max, const double* Tsyn, double* F) {
-  if (n_rows <= 0) return hipSuccess;
-  const int L = ell_max, nm = 2 * L + 1, jp = large_analysis_jp(n_theta);
-  static const int rows_per_block = BMS_PROBE_ENV("SCRI_AMD_TS_ROWS") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TS_ROWS")) : 256;
-  const dim3 grid1(nm, (unsigned)((n_rows + rows_per_block - 1) / rows_per_block));
-  const int kl = (L + 1 - ell_min + 3) / 4, ntj_all = (n_theta + 15) / 16;
-  // SCRI_AMD_TS_SPLIT=1 and more than four ring tiles (n_theta > 64): two workgroups per m, each with half of them
-  // (measured, round 4: 99 x 99 / l <= 24, 25 000 steps, six fields: 14.65 ms split against 13.09 ms whole -- three waves per SIMD at
-  // 153 registers do not make up for gathering every mode twice; off unless asked for)
-  static const int ts_split = BMS_PROBE_ENV("SCRI_AMD_TS_SPLIT") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TS_SPLIT")) : 0;
-  const int parts = ts_split && ntj_all > 4 ? 2 : 1;
-  const int ntj = (ntj_all + parts - 1) / parts;
-  const dim3 grid1z(grid1.x, grid1.y, parts);
-#define TS_GO(KL, NTJ)                                                                                                      \
-  hipLaunchKernelGGL((theta_synthesis_mfma_kernel<KL, NTJ>), grid1z, dim3(256), 0, stream, A, lda, n_rows, n_theta, L, ell_min, jp, \
-                     rows_per_block, Tsyn, F)
-#define TS_KL(NTJ)  \
-  if (kl <= 5)      \
-    TS_GO(5, NTJ);  \
-  else if (kl <= 7) \
-    TS_GO(7, NTJ);  \
-  else              \
-    TS_GO(9, NTJ);
-  if (ntj <= 3) {
-    TS_KL(3)
-  } else if (ntj == 4) {
-    TS_KL(4)
-  } else if (ntj <= 5) {
-    TS_KL(5)
-  } else {
-    TS_KL(7)
-  }
-#undef TS_KL
-#undef TS_GO
-  return hipGetLastError();
+  const long long items = n_rows * ((n_theta + 7) / 8);
+  const unsigned grid = (unsigned)(items < 256 * 8 ? items : 256 * 8);
+  return with_phi_instance(n_phi, L, [&](auto KM, auto NTC) {
+    hipLaunchKernelGGL((phi_synthesis_folded_kernel<KM.value, NTC.value>), dim3(grid), dim3(64), lds, stream, F, n_rows, n_theta, n_phi, L,
+                       jp, off, A + 2LL * n_modes, lda, scale, Y, ldy);
+    return hipGetLastError();
+  });
 }
 
 int abd_mix6_supported(int n_theta, int n_phi, int ell_max) {
@@ -541,34 +493,15 @@ hipError_t launch_phi_synthesis_mix6(hipStream_t stream, const double* const F6[
   for (int f = 0; f < 6; ++f) a.F[f] = F6[f], a.out[f] = out6[f];
   a.eth_alpha = eth_alpha, a.etheth_alpha = etheth_alpha, a.cst = cst, a.ldc = ldc, a.ldo = ldo;
   const int L = ell_max, jp = large_analysis_jp(n_theta);
-  const int nk = n_phi / 2 + 1, mt = (n_theta + 3) / 4;
-  const int km = (L + 3) / 4, ntc = (nk + 15) / 16;
   const size_t lds = sizeof(double2) * (size_t)6 * 4 * n_phi;
-  const long long items = n_rows * mt;
+  const long long items = n_rows * ((n_theta + 3) / 4);
   const unsigned grid = (unsigned)(items < 256 * 4 ? items : 256 * 4);
-#define M6_GO(KM, NTC)                                                                                                    \
-  {                                                                                                                       \
-    hipError_t e_ = allow_dynamic_lds((const void*)phi_synthesis_mix6_kernel<KM, NTC>); \
-    if (e_ != hipSuccess) return e_;                                                                                      \
-    hipLaunchKernelGGL((phi_synthesis_mix6_kernel<KM, NTC>), dim3(grid), dim3(64), lds, stream, a, n_rows, n_theta, n_phi, L, jp);  \
-  }
-#define M6_KM(NTC)  \
-  if (km <= 5)      \
-    M6_GO(5, NTC)   \
-  else if (km <= 7) \
-    M6_GO(7, NTC)   \
-  else              \
-    M6_GO(9, NTC)
-  if (ntc <= 2) {
-    M6_KM(2)
-  } else if (ntc == 3) {
-    M6_KM(3)
-  } else {
-    M6_KM(4)
-  }
-#undef M6_KM
-#undef M6_GO
-  return hipGetLastError();
+  return with_phi_instance(n_phi, L, [&](auto KM, auto NTC) {
+    hipError_t e = allow_dynamic_lds((const void*)phi_synthesis_mix6_kernel<KM.value, NTC.value>);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((phi_synthesis_mix6_kernel<KM.value, NTC.value>), dim3(grid), dim3(64), lds, stream, a, n_rows, n_theta, n_phi, L, jp);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace bms

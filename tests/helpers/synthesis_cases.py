@@ -83,6 +83,33 @@ def branch_of(n_theta, n_phi, L):
     return pick(kl), (3 if ntj <= 3 else ntj if ntj <= 5 else 7), pick(km), (2 if ntc <= 2 else 3 if ntc == 3 else 4)
 
 
+def mix6_branch_of(n_theta, n_phi, L):
+    """(KM, NTC) of the phi_synthesis_mix6_kernel<KM, NTC> that launch_phi_synthesis_mix6 picks -- the phi stage's ladder, as in
+    branch_of -- or None where abd_mix6_supported (kernels_synthesis_large.hip) declines: a shape the two-kernel route does not take,
+    F tiles that do not fit the LDS area of their results (2 L + 1 > n_phi), or six result tiles of 4 n_phi pixels beyond 53 KB"""
+    if not (2 <= n_theta <= 104 and n_phi >= 1 and n_phi // 2 + 1 <= 64 and 1 <= L <= 33):
+        return None
+    if 2 * L + 1 > n_phi or 6 * 4 * n_phi * 16 > 53 * 1024:
+        return None
+    return branch_of(n_theta, n_phi, L)[2:]
+
+
+# AsymptoticBondiData without a boost through the fused phi stage (tests/test_gpu_separable_large.py): (L, n_theta, n_phi, time steps)
+M6_CASES = [
+    (20, 41, 63, 9),    # <5,2>
+    (21, 43, 63, 9),    # <7,2>
+    (29, 59, 63, 9),    # <9,2>
+    (31, 63, 63, 9),    # <9,2>  2 L + 1 = n_phi: the F tiles fill exactly the LDS area their results overwrite
+    (20, 44, 64, 9),    # <5,3>  even n_phi; n_theta a multiple of 4
+    (28, 57, 95, 9),    # <7,3>
+    (33, 67, 95, 9),    # <9,3>
+    (20, 42, 96, 9),    # <5,4>  two live rings in the last tile
+    (28, 57, 127, 9),   # <7,4>
+    (33, 67, 127, 9),   # <9,4>  the instance with scratch
+    (20, 41, 63, 120),  # <5,2>  11 ring tiles x 120 steps > 1024 work items: the grid-stride loop and its prefetch of the next item
+]
+
+
 # ------------------------------------------------------------------------------------------------ group A: engine.salm2map
 # (n_theta, n_phi, ell_max, spin, dense rows).  One-hot rows come on top: one_hot_modes().
 A_ELL = [(9, 10, L, -2, 5) for L in (19, 20, 21, 27, 28, 29, 33)]  # every edge of KL and KM; the grid need not resolve l

@@ -8,6 +8,7 @@ import pytest
 
 from oracle import abd_ref, waveform_grid_ref as grid_ref
 from oracle.containers import WM, psi2 as o_psi2, psi3 as o_psi3, h as o_h
+from tests.helpers import synthesis_cases as sy
 from tests.test_gpu_transform_abd import real_st, smooth_abd
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,45 @@ def test_abd_boost_free_separable_equals_dense_and_oracle(ctx, monkeypatch, ell_
         expect = abd_ref.transform(o, **kw)
         assert got.n_times == expect.n_times
         assert np.abs(got._raw_data - expect.raw).max() < 1e-12 * scale
+
+
+@pytest.mark.parametrize("L,n_theta,n_phi,n", sy.M6_CASES, ids=[f"l{c[0]}-{c[1]}x{c[2]}-n{c[3]}" for c in sy.M6_CASES])
+def test_abd_fused_phi_stage_at_every_instance_equals_dense_and_repeats(ctx, monkeypatch, route, L, n_theta, n_phi, n):
+    """phi_synthesis_mix6_kernel<KM, NTC> (the phi stage of the six fields fused with their mixing) at all nine instances and the edges
+    of its tiles: synthesis_cases.M6_CASES, which test_mix6_case_table_reaches_every_template_instance holds to the launcher's
+    arithmetic.  Device-resident input under a small supertranslation and a frame rotation, against the dense route of the same
+    library (swsh_kernel + zgemm3m + abd_mix) at this module's bar for that comparison; then once more into a buffer of NaN: the
+    same bits, and every element written.  Measured on an MI355X: max|fused - dense| = 6.8e-16 .. 1.4e-15 at a scale of 1.4 .. 2.3,
+    against bars of 3.5e-13 .. 9.5e-13 (profiles/r15_a_large_synthesis_ab.txt)."""
+    import torch
+
+    from scri_amd import engine, synthetic
+
+    assert sy.mix6_branch_of(n_theta, n_phi, L) is not None
+    o = smooth_abd(n, L, 500 + L + n_phi + n)
+    tr = engine.make_transformation(synthetic.real_supertranslation(real_st(3, 5, 1e-3)), ROTOR, [0, 0, 0], n_theta, n_phi, L)
+    d_in = torch.from_numpy(o.raw).to(torch.device("cuda", ctx.device))
+
+    def run(fill):
+        d_out = torch.full_like(d_in, fill)
+        torch.cuda.synchronize()
+        u_out, n_new = engine.transform_abd(o.u, d_in.data_ptr(), L, tr, ctx=ctx, device=True, out_ptr=d_out.data_ptr())
+        ctx.synchronize()
+        return u_out[:n_new], d_out[:, :n_new].cpu().numpy()
+
+    route("SCRI_AMD_NO_FUSED_ABD_MIX", None)
+    route("SCRI_AMD_NO_SEPARABLE_SYNTHESIS", None)
+    u_got, got = run(0.0)
+    u_again, again = run(float("nan"))
+    route("SCRI_AMD_NO_SEPARABLE_SYNTHESIS", "1")
+    u_ref, ref = run(0.0)
+    assert u_ref.size > 0 and np.array_equal(u_got, u_ref) and np.array_equal(u_again, u_ref)
+    assert not np.isnan(again).any()
+    assert got.shape == again.shape and got.tobytes() == again.tobytes()
+    scale = max(1.0, np.abs(ref).max())
+    worst = np.abs(got - ref).max()
+    print(f"M6 l<={L} {n_theta}x{n_phi} n={n}: max|fused - dense| = {worst:.3e}, bar {1e-13 * scale * max(1.0, L / 8.0):.3e}, scale {scale:.3e}")
+    assert worst < 1e-13 * scale * max(1.0, L / 8.0)
 
 
 @pytest.mark.parametrize("data_type,ell_max,rotated", [("psi2", 6, True), ("psi3", 8, False), ("psi2", 18, True), ("h", 20, True), ("h", 24, False)])

@@ -111,6 +111,19 @@ def test_case_table_reaches_every_template_instance():
     assert [2 * sy.grid_multiply_working_ell_max(c[1], c[3], c[4]) + 1 for c in sy.C_CASES[:3]] == [33, 41, 43]
 
 
+def test_mix6_case_table_reaches_every_template_instance():
+    """no GPU: the table of tests/test_gpu_separable_large.py's fused-ABD test on the launcher's arithmetic -- every case is one the fused
+    kernel takes (not its fallback, the unfused phi stage), and together they reach all nine phi_synthesis_mix6_kernel<KM, NTC>"""
+    branches = [sy.mix6_branch_of(nt, nph, L) for L, nt, nph, _ in sy.M6_CASES]
+    assert None not in branches
+    assert set(branches) == {(km, ntc) for km in (5, 7, 9) for ntc in (2, 3, 4)}
+    assert branches == [(5, 2), (7, 2), (9, 2), (9, 2), (5, 3), (7, 3), (9, 3), (5, 4), (7, 4), (9, 4), (5, 2)]
+    assert all(n >= 8 for *_, n in sy.M6_CASES)  # fewer steps: no B-spline form, so no elimination on the modes and no fused mixing
+    # the restatement declines where abd_mix6_supported does
+    assert sy.mix6_branch_of(63, 63, 32) is None and sy.mix6_branch_of(63, 63, 31) == (9, 2)  # 2 L + 1 <= n_phi
+    assert sy.mix6_branch_of(105, 63, 20) is None and sy.mix6_branch_of(41, 128, 20) is None and sy.mix6_branch_of(69, 127, 34) is None
+
+
 # ------------------------------------------------------------------------------------------------------------- group A
 def _device_salm2map(ctx, a, spin, ell_max, n_theta, n_phi):
     """bms_salm2map on device memory: the modes in a tensor, the grid into a tensor that starts as NaN"""
