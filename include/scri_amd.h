@@ -398,6 +398,20 @@ int bms_corotating_frame(bms_ctx* ctx, const double* t, int64_t n_times, const v
 int bms_coprecessing_frame(bms_ctx* ctx, const double* t, int64_t n_times, const void* data, int64_t ld, int ell_min, int ell_max, int mem,
                            const double rough[3], int64_t rough_index, int iterations, double* frame_dev, double* frame_out,
                            double* axis_out);
+/* quaternion.squad (scri/waveform_base.py:957 interpolates the frame of a waveform with it), as scri_amd.quaternions.squad states it:
+ * the rotors R_in f8[n][4] at the times t_in[n] (host, finite, strictly increasing, n >= 2; the steps need not be uniform) interpolated
+ * to the arguments t_out[m] (host, finite, in ANY order, m >= 0), out f8[m][4]; R_in and out live in `mem` and must not overlap.
+ *     out = slerp( slerp(R_i, R_{i+1}, tau), slerp(A_i, B_i, tau), 2 tau (1 - tau) ),   slerp(p, q, tau) = p exp(tau log(p^-1 q)),
+ *     A_i = R_i exp( (-log(R_i^-1 R_{i+1}) + log(R_{i-1}^-1 R_i) h_i / h_{i-1}) / 4 ),
+ *     B_i = R_{i+1} exp( -(log(R_{i+1}^-1 R_{i+2}) h_i / h_{i+1} - log(R_i^-1 R_{i+1})) / 4 ),   h_i = t_{i+1} - t_i,
+ * with the end rules A_0 = R_0, A_{n-1} = R_{n-1}, B_{n-2} = R_{n-1}, B_{n-1} = R_n applied in this order (they meet at n = 2 and 3).
+ * Interval: i = clip(#{k: t_in[k] <= t} - 1, 0, n - 1), tau = (t - t_i) / (t_{i+1} - t_i); an argument below t_in[0] takes interval 0
+ * with tau < 0, and interval n - 1 runs to the mirrored knot t_n = 2 t_{n-1} - t_{n-2} with R_n = R_{n-1} R_{n-2}^-1 R_{n-1}.  The
+ * logarithm has a zero vector part where the vector norm is <= 1e-300.  Two launches: control points per knot, then one thread per
+ * argument; every operation is in the order of the numpy statement, so host and device memory give the same bits and an argument's
+ * value does not depend on the others.  A NULL pointer, a bad `mem`, n < 2, m < 0, non-finite or not strictly increasing t_in and
+ * non-finite t_out are refused (BMS_ERR_INVALID) before anything is staged; the rotors themselves are not inspected. */
+int bms_squad(bms_ctx* ctx, const double* t_in, int64_t n, const void* R_in, int mem, const double* t_out, int64_t m, void* out);
 
 /* ---- time-and-phase alignment of two waveforms from correlation moments (scri_amd/alignment.py; DESIGN: "Alignment as moments") ----
  * The moving waveform A: time axis ta[na] (host, na >= 4, strictly increasing), values ya and knot slopes sa of its not-a-knot cubic

@@ -8,7 +8,7 @@
 //   engine_modes.hip     WaveformModes transform: one call, shard, pipelined, series, grid                   (bms_transform_modes*, ...)
 //   engine_abd.hip       AsymptoticBondiData transform                                                       (bms_transform_abd*)
 //   engine_blocks.hip    building blocks, series and bit operators               (bms_rotor_grid ... bms_grid_multiply, bms_xor_timeseries ...)
-//   engine_frames.hip    corotating / coprecessing frames built on the device                                (bms_corotating_frame ..., bms_dominant_axis ...)
+//   engine_frames.hip    corotating / coprecessing frames built on the device, rotor interpolation           (bms_corotating_frame ..., bms_dominant_axis ..., bms_squad)
 //   engine_align.hip     time-and-phase alignment from correlation moments                                   (bms_align_moments, bms_align_residual)
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)

@@ -125,7 +125,44 @@ int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, int* n_modes)
   return BMS_OK;
 }
 
+// what bms_squad refuses in its two host arrays, before anything is staged
+int squad_checks(bms_ctx* c, const double* t_in, int64_t n, const double* t_out, int64_t m) {
+  if (n < 2) return fail(c, BMS_ERR_INVALID, "squad needs at least 2 rotors, got %lld", (long long)n);
+  if (m < 0) return fail(c, BMS_ERR_INVALID, "negative number of arguments (%lld)", (long long)m);
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(t_in[i])) return fail(c, BMS_ERR_INVALID, "time array must be finite (index %lld)", (long long)i);
+  for (int64_t i = 1; i < n; ++i)
+    if (!(t_in[i] > t_in[i - 1])) return fail(c, BMS_ERR_INVALID, "time array must be strictly increasing (index %lld)", (long long)i);
+  for (int64_t j = 0; j < m; ++j)
+    if (!std::isfinite(t_out[j])) return fail(c, BMS_ERR_INVALID, "arguments must be finite (index %lld)", (long long)j);
+  return BMS_OK;
+}
+
 }  // namespace
+
+extern "C" int bms_squad(bms_ctx* c, const double* t_in, int64_t n, const void* R_in, int mem, const double* t_out, int64_t m,
+                         void* out) try {
+  if (!c || !t_in || !R_in || !t_out || !out) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = squad_checks(c, t_in, n, t_out, m))) return rc;
+  if (m == 0) return BMS_OK;
+  void *d_t, *d_u;
+  const double* d_R;
+  double *d_AB, *d_out;
+  if ((rc = upload(c, "times", t_in, 8 * (size_t)n, &d_t))) return rc;
+  if ((rc = upload(c, "times_new", t_out, 8 * (size_t)m, &d_u))) return rc;
+  if ((rc = in_array(c, "fr_in", (const double*)R_in, mem, (size_t)n * 4, &d_R))) return rc;
+  if ((rc = dev_buf_t(c, "fr_squad_AB", (size_t)n * 8, &d_AB))) return rc;
+  if ((rc = out_array(c, "fr_out", (double*)out, mem, (size_t)m * 4, &d_out))) return rc;
+  hipStream_t S = c->stream;
+  TIMED(c, BMS_TAG_POINTWISE, launch_squad_control(S, d_R, (const double*)d_t, n, d_AB));
+  TIMED(c, BMS_TAG_POINTWISE, launch_squad_eval(S, d_R, (const double*)d_t, n, d_AB, (const double*)d_u, m, d_out));
+  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, S));
+  HIP_TRY(c, hipStreamSynchronize(S));
+  return BMS_OK;
+} BMS_CATCH(c)
 
 extern "C" int bms_frame_from_angular_velocity(bms_ctx* c, const double* t, int64_t n, const double* omega, int mem, const double R0[4],
                                                double tolerance, double* R_out) try {

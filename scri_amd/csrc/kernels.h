@@ -373,6 +373,11 @@ hipError_t launch_rotor_omega(hipStream_t stream, const double* R, const double*
 // (w + i z, y + i x) to spinors; log_out, spinors may be null
 hipError_t launch_frame_adjust(hipStream_t stream, double* frame, long long n, Vec4 right, int with_right, double pow2, double* log_out,
                                double* spinors);
+// quaternion.squad in two steps (n >= 2 knots t, rotors R f8[n][4]): the control points AB f8[n][8] = (A_i, B_i) with the statement's end
+// rules, B[n-1] = the mirrored rotor beyond the end; then out f8[m][4] at the arguments t_out[m], in any order
+hipError_t launch_squad_control(hipStream_t stream, const double* R, const double* t, long long n, double* AB);
+hipError_t launch_squad_eval(hipStream_t stream, const double* R, const double* t, long long n, const double* AB, const double* t_out,
+                             long long m, double* out);
 
 // ---- time-and-phase alignment from correlation moments (kernels_align.hip; scri_amd/alignment.py)
 constexpr int ALIGN_TILE_OFFSETS = 16;    // offsets x rows of a workgroup's tile; the row tiling fixes the order of every sum

@@ -329,6 +329,93 @@ __global__ __launch_bounds__(256) void frame_adjust_kernel(double* __restrict__ 
   if (spinors) spinors[4 * j] = q.w, spinors[4 * j + 1] = q.z, spinors[4 * j + 2] = q.y, spinors[4 * j + 3] = q.x;
 }
 
+// ------------------------------------------------------------------------------------------------ rotor interpolation (squad)
+// scri_amd.quaternions.squad, operation for operation (no contraction, the same order of every sum), so that the only difference from
+// the numpy statement is the device's atan2 / sin / cos / log / exp.  Two kernels: the control points A_i, B_i depend on the knots
+// alone (three logarithms and two exponentials per knot), so they are formed once per knot and not once per argument; an argument then
+// costs a binary search of the knots and three slerps.  One thread per knot / per argument, nothing shared, no order among arguments.
+__device__ __forceinline__ Quat quat_log(const Quat& q) {
+#pragma clang fp contract(off)
+  const double vn = sqrt(q.x * q.x + q.y * q.y + q.z * q.z);
+  const double qn = sqrt(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+  const double scale = vn > 1e-300 ? atan2(vn, q.w) / vn : 0.0;
+  return {log(qn > 0.0 ? qn : 1.0), q.x * scale, q.y * scale, q.z * scale};
+}
+__device__ __forceinline__ Quat quat_exp(const Quat& q) {
+#pragma clang fp contract(off)
+  const double vn = sqrt(q.x * q.x + q.y * q.y + q.z * q.z);
+  const double e = exp(q.w);
+  const double s = vn > 1e-300 ? sin(vn) / vn : 1.0;
+  const double es = e * s;
+  return {e * cos(vn), es * q.x, es * q.y, es * q.z};
+}
+__device__ __forceinline__ Quat quat_scaled(const Quat& q, double f) { return {q.w * f, q.x * f, q.y * f, q.z * f}; }
+// q1 (q1^-1 q2)^tau
+__device__ __forceinline__ Quat quat_slerp(const Quat& q1, const Quat& q2, double tau) {
+  return qmul(q1, quat_exp(quat_scaled(quat_log(qmul(qconj(q1), q2)), tau)));
+}
+
+// AB f8[n][8] = (A_i, B_i).  The end rules in the statement's order: A[0] = R[0], A[-1] = R[-1], B[-2] = R[-1], B[-1] = R_n, the later
+// one winning where they meet (n = 2, 3).  The knots the general rule reads (i - 1 .. i + 2) exist wherever an end rule does not apply.
+__global__ __launch_bounds__(256) void squad_control_kernel(const double* __restrict__ R, const double* __restrict__ t, long long n,
+                                                            double* __restrict__ AB) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Quat Ri = load_quat(R, i);
+  Quat A, B;
+  if (i == 0 || i == n - 1) {
+    A = Ri;
+  } else {
+    const Quat step = quat_log(qmul(qconj(Ri), load_quat(R, i + 1)));
+    const Quat back = quat_log(qmul(qconj(load_quat(R, i - 1)), Ri));
+    const double r_next = (t[i + 1] - t[i]) / (t[i] - t[i - 1]);
+    const Quat e = {(-step.w + back.w * r_next) * 0.25, (-step.x + back.x * r_next) * 0.25, (-step.y + back.y * r_next) * 0.25,
+                    (-step.z + back.z * r_next) * 0.25};
+    A = qmul(Ri, quat_exp(e));
+  }
+  if (i == n - 1) {
+    B = qmul(qmul(Ri, qconj(load_quat(R, i - 1))), Ri);  // R_n, the mirrored value beyond the end
+  } else if (i == n - 2) {
+    B = load_quat(R, i + 1);
+  } else {
+    const Quat Rn = load_quat(R, i + 1);
+    const Quat step = quat_log(qmul(qconj(Ri), Rn));
+    const Quat ahead = quat_log(qmul(qconj(Rn), load_quat(R, i + 2)));
+    const double r_after = (t[i + 1] - t[i]) / (t[i + 2] - t[i + 1]);
+    const Quat e = {(ahead.w * r_after - step.w) * -0.25, (ahead.x * r_after - step.x) * -0.25, (ahead.y * r_after - step.y) * -0.25,
+                    (ahead.z * r_after - step.z) * -0.25};
+    B = qmul(Rn, quat_exp(e));
+  }
+  store_quat(AB, 2 * i, A);
+  store_quat(AB, 2 * i + 1, B);
+}
+
+// out[j] = squad at t_out[j]: interval i = clip(searchsorted(t, t_out[j], "right") - 1, 0, n - 1); interval n - 1 runs to the mirrored
+// knot 2 t[n-1] - t[n-2] with the mirrored rotor R_n = B[n-1]
+__global__ __launch_bounds__(256) void squad_eval_kernel(const double* __restrict__ R, const double* __restrict__ t, long long n,
+                                                         const double* __restrict__ AB, const double* __restrict__ t_out, long long m,
+                                                         double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= m) return;
+  const double u = t_out[j];
+  long long lo = 0, hi = n;  // the number of knots <= u
+  while (lo < hi) {
+    const long long mid = lo + (hi - lo) / 2;
+    if (t[mid] <= u) lo = mid + 1; else hi = mid;
+  }
+  const long long i = lo > 0 ? lo - 1 : 0;
+  const bool last = i == n - 1;
+  const Quat Ri = load_quat(R, i);
+  const Quat Rn = last ? load_quat(AB, 2 * i + 1) : load_quat(R, i + 1);
+  const double t_next = last ? t[i] + (t[i] - t[i - 1]) : t[i + 1];
+  const double tau = (u - t[i]) / (t_next - t[i]);
+  const Quat a = quat_slerp(Ri, Rn, tau);
+  const Quat b = quat_slerp(load_quat(AB, 2 * i), load_quat(AB, 2 * i + 1), tau);
+  store_quat(out, j, quat_slerp(a, b, 2 * tau * (1 - tau)));
+}
+
 }  // namespace
 
 long long frame_scan_blocks(long long n) { return (n + SCAN_BLOCK - 1) / SCAN_BLOCK; }
@@ -382,6 +469,15 @@ hipError_t launch_rotor_omega(hipStream_t stream, const double* R, const double*
 hipError_t launch_frame_adjust(hipStream_t stream, double* frame, long long n, Vec4 right, int with_right, double pow2, double* log_out,
                                double* spinors) {
   FRAME_LAUNCH(frame_adjust_kernel, n, frame, n, right, with_right, pow2, log_out, spinors);
+}
+hipError_t launch_squad_control(hipStream_t stream, const double* R, const double* t, long long n, double* AB) {
+  if (n < 2) return hipErrorInvalidValue;
+  FRAME_LAUNCH(squad_control_kernel, n, R, t, n, AB);
+}
+hipError_t launch_squad_eval(hipStream_t stream, const double* R, const double* t, long long n, const double* AB, const double* t_out,
+                             long long m, double* out) {
+  if (n < 2) return hipErrorInvalidValue;
+  FRAME_LAUNCH(squad_eval_kernel, m, R, t, n, AB, t_out, m, out);
 }
 
 }  // namespace bms

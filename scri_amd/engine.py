@@ -682,11 +682,32 @@ def map2salm(grid, spin, ell_max, ell_min=0, ctx=None):
     return out.reshape(lead + (out.shape[1],))
 
 
+def _device_series_arg(ctx, y, n, n_new):
+    """(address, row stride, columns, a new device tensor [n_new, n_cols]) for a series y [n, n_cols] resident on the GPU"""
+    import torch
+
+    from . import device_series
+
+    device_series.attach(ctx)
+    _on_device_of(ctx, y)
+    if y.dtype != torch.complex128 or y.ndim != 2 or y.shape[0] != n or (y.shape[1] > 1 and y.stride(1) != 1):
+        raise ValueError(f"a device series must be complex128 [{n}, n_cols] with unit column stride, got {y.dtype} of shape {tuple(y.shape)}")
+    n_cols = int(y.shape[1])
+    out = torch.empty((n_new, n_cols), dtype=torch.complex128, device=y.device)
+    return c_vp(y.data_ptr()), (y.stride(0) if n > 1 else max(n_cols, 1)), n_cols, out
+
+
 def cubic_spline(x, y, x_new, ctx=None):
-    """scipy.interpolate.CubicSpline(x, y)(x_new) for complex y[N, ...] (axis 0 = time)."""
+    """scipy.interpolate.CubicSpline(x, y)(x_new) for complex y[N, ...] (axis 0 = time).  y may be a device tensor [N, n_cols]
+    (complex128, unit column stride): the same launches read it where it is and the result is a new device tensor."""
     ctx = _ctx(ctx)
     x = np.ascontiguousarray(x, dtype=float)
     xn = np.ascontiguousarray(x_new, dtype=float)
+    if hasattr(y, "data_ptr"):
+        y_ptr, ld, n_cols, out = _device_series_arg(ctx, y, x.shape[0], xn.shape[0])
+        rc = _lib.load().bms_cubic_spline(ctx.handle, dptr(x), x.shape[0], y_ptr, ld, n_cols, BMS_DEVICE, dptr(xn), xn.shape[0], c_vp(out.data_ptr()))
+        ctx.check(rc, "bms_cubic_spline")
+        return out
     y = _lib.as_c16(y)
     tail = y.shape[1:]
     y2 = y.reshape(y.shape[0], -1)
@@ -801,10 +822,17 @@ def radius_terms(t, h0, n_terms, amp, radius, out, ctx=None):
 
 def spline_derivative(x, y, x_new, order=0, ctx=None):
     """scipy CubicSpline(x, y, axis=0) differentiated (`order` 1..3) or integrated (`order` -1 .. -16; zero at x[0]) and
-    evaluated at x_new, for complex y[N, ...]."""
+    evaluated at x_new, for complex y[N, ...].  y may be a device tensor [N, n_cols] (complex128, unit column stride): the same
+    launches read it where it is and the result is a new device tensor."""
     ctx = _ctx(ctx)
     x = np.ascontiguousarray(x, dtype=float)
     xn = np.ascontiguousarray(x_new, dtype=float)
+    if hasattr(y, "data_ptr"):
+        y_ptr, ld, n_cols, out = _device_series_arg(ctx, y, x.shape[0], xn.shape[0])
+        rc = _lib.load().bms_spline_derivative(ctx.handle, dptr(x), x.shape[0], y_ptr, ld, n_cols, BMS_DEVICE, dptr(xn), xn.shape[0], int(order),
+                                               c_vp(out.data_ptr()))
+        ctx.check(rc, "bms_spline_derivative")
+        return out
     y = _lib.as_c16(y)
     tail = y.shape[1:]
     y2 = y.reshape(y.shape[0], -1)
@@ -1015,6 +1043,35 @@ def rotor_angular_velocity(t, R, ctx=None):
     out_ptr, out = _step_out(R, n, 3)
     rc = _lib.load().bms_rotor_angular_velocity(ctx.handle, dptr(t), n, R_ptr, mem, out_ptr)
     ctx.check(rc, "bms_rotor_angular_velocity")
+    return out
+
+
+def squad(R_in, t_in, t_out, ctx=None, out=None):
+    """quaternion.squad of the rotors R_in[n, 4] at the times t_in[n] evaluated at t_out[m] (any order), on the GPU (bms_squad):
+    `scri_amd.quaternions.squad` is the statement.  R_in: a numpy array, or a device tensor (float64, contiguous); the result [m, 4]
+    lives where R_in does (`out`, device input only: the device tensor it is written to).  No rotors, no arguments or one rotor
+    answer as the statement does, without a launch."""
+    ctx = _ctx(ctx)
+    _on_device_of(ctx, R_in, out)
+    t_in = np.ascontiguousarray(t_in, dtype=float)
+    t_out = np.ascontiguousarray(t_out, dtype=float).reshape(-1)
+    on_device = hasattr(R_in, "data_ptr")
+    if not on_device:
+        R_in = np.asarray(R_in, dtype=float)
+    size = R_in.numel() if on_device else R_in.size
+    n, m = (int(R_in.shape[0]) if size else 0), t_out.shape[0]
+    if n < 2 or m == 0:  # the statement's answers: nothing from nothing, one rotor repeated
+        rows = 0 if n == 0 or m == 0 else m
+        _, res = _step_out(R_in, rows, 4, out)
+        if rows:
+            res.reshape(rows, 4)[:] = R_in.reshape(-1, 4)[:1]
+        return res
+    if t_in.shape != (n,):
+        raise ValueError(f"t_in must have shape ({n},); it has shape {t_in.shape}")
+    R_ptr, mem, R = _step_arg(R_in, n, 4, "R_in")
+    out_ptr, out = _step_out(R, m, 4, out)
+    rc = _lib.load().bms_squad(ctx.handle, dptr(t_in), n, R_ptr, mem, dptr(t_out), m, out_ptr)
+    ctx.check(rc, "bms_squad")
     return out
 
 

@@ -10,7 +10,6 @@ Same names, arguments, history lines and errors as the reference, with two delib
 M Omega r (`Omegas`) and the exclusion of insignificant radii for psi0 / psi1 (`NoiseFloor`), two branches that fail in the
 reference, raise NotImplementedError.  The file readers and writers are out of scope.
 """
-import copy
 import warnings
 
 import numpy as np
@@ -40,16 +39,9 @@ def _resident(W):
     return getattr(W, "is_device_resident", False)
 
 
-def _interpolated(W, T):
-    """W.interpolate(T), leaving W where it is: a device-resident W is read through a shallow copy (the spline runs from host
-    memory), and the result is uploaded again."""
-    if not _resident(W):
-        return W.interpolate(T)
-    return copy.copy(W).interpolate(T).to_device()
-
-
 def _host_data(W):
-    """the modes of W on the host, without moving a device-resident W off the device"""
+    """the modes of W on the host for a fit whose inputs are not all device resident (the fit reads one kind of memory): a copy, which
+    leaves a device-resident W where it is"""
     return W._dev.cpu().numpy() if _resident(W) else W.data
 
 
@@ -66,7 +58,7 @@ def set_common_time(Ws, Radii, MinTimeStep=0.005, EarliestTime=-3e300, LatestTim
     for k in range(len(Radii)):
         r = np.asarray(Radii[k], dtype=float).astype(np.complex128)
         Radii[k] = engine.cubic_spline(Ws[k].t, r, T, ctx=Ws[k]._ctx).real
-        Ws[k] = _interpolated(Ws[k], T)
+        Ws[k] = Ws[k].interpolate(T)  # (a device-resident waveform is read where it is, and so is the result)
 
 
 def _check_arguments(Ws, Radii, orders, Omegas):

@@ -66,8 +66,9 @@ class WaveformModes(ModeOperators):
             )
 
     # ---- where the mode weights live.  `data` is the host array of the reference's interface; an object moved to the GPU with
-    # to_device() keeps its weights in HBM, and transform / rotate_decomposition_basis / copy work on them there (results
-    # stay there too).  Reading `data` brings them back and makes the host array authoritative again (the caller may write to it).
+    # to_device() keeps its weights in HBM, and transform / rotate_decomposition_basis / copy / interpolate / slicing work on them
+    # there (results stay there too); data_dot ... data_iint read them there and return the reference's host array.  Reading `data`
+    # brings them back and makes the host array authoritative again (the caller may write to it).
     @property
     def data(self):
         if self._host is None and self._dev is not None:
@@ -284,12 +285,20 @@ class WaveformModes(ModeOperators):
             raise ValueError("Could not understand input `{}` (of type `{}`) ".format(key, type(key)))
         if isinstance(tkey, (int, np.integer)):
             tkey = slice(tkey, tkey + 1 if tkey != -1 else None)
+        # weights resident on the GPU are sliced there: a copy, as the host slice is, so neither object sees the other's later changes
+        dev = None
+        if self.is_device_resident:
+            import torch
+
+            dev = self._dev[tkey, cols].clone(memory_format=torch.contiguous_format)
         W = type(self)(
-            t=self.t[tkey], data=self.data[tkey, cols], ell_min=new_ells[0], ell_max=new_ells[1],
+            t=self.t[tkey], data=np.empty((0, dev.shape[1])) if dev is not None else self.data[tkey, cols], ell_min=new_ells[0], ell_max=new_ells[1],
             frame=self.frame[tkey] if self.frame.shape[0] == self.n_times else self.frame, frameType=self.frameType,
             dataType=self.dataType, r_is_scaled_out=self.r_is_scaled_out, m_is_scaled_out=self.m_is_scaled_out,
             history=list(self.history), ctx=self._ctx,
         )
+        if dev is not None:
+            W._host, W._dev = None, dev
         W.history.pop()  # the constructor's line, replaced by the slicing statement
         W._append_history(f"{W} = {self}[{key}]")
         return W
@@ -302,35 +311,49 @@ class WaveformModes(ModeOperators):
         )
         return W
 
-    # ---- interpolation in time (waveform_base.py:950-967): not-a-knot cubic spline on the GPU
+    # ---- interpolation in time (waveform_base.py:950-967): not-a-knot cubic spline on the GPU.  Weights resident there are read where
+    # they are (the same entry and launches as from host memory) and the result stays there; a time-dependent frame -- a host array in
+    # either case -- then goes through the GPU squad (bms_squad), and through the numpy statement for a host-resident object.
     def interpolate(self, tprime):
         tprime = np.asarray(tprime, dtype=float)
         W = self.copy_without_data()
         W.t = np.copy(tprime)
         if self.frame.shape[0] > 1:  # waveform_base.py:957
-            W.frame = quaternions.squad(self.frame, self.t, tprime)
+            if self.is_device_resident:
+                W.frame = engine.squad(self.frame, self.t, tprime, ctx=self._ctx)
+            else:
+                W.frame = quaternions.squad(self.frame, self.t, tprime)
         else:
             W.frame = np.array(self.frame, copy=True)
-        W.data = engine.cubic_spline(self.t, self.data, tprime, ctx=self._ctx)
+        if self.is_device_resident:
+            W._host, W._dev = None, engine.cubic_spline(self.t, self._dev, tprime, ctx=self._ctx)
+        else:
+            W.data = engine.cubic_spline(self.t, self.data, tprime, ctx=self._ctx)
         W._append_history(f"{W} = {self}.interpolate({tprime})")
         return W
 
-    # time calculus of the mode data (scri/waveform_base.py:689-703): cubic-spline derivatives / antiderivatives on the GPU
+    # time calculus of the mode data (scri/waveform_base.py:689-703): cubic-spline derivatives / antiderivatives on the GPU.  The result
+    # is the host array of the reference's properties; weights resident on the GPU stay there, and only the result comes back.
+    def _data_derivative(self, order):
+        if self.is_device_resident:
+            return engine.spline_derivative(self.t, self._dev, self.t, order, ctx=self._ctx).cpu().numpy()
+        return engine.spline_derivative(self.t, self.data, self.t, order, ctx=self._ctx)
+
     @property
     def data_dot(self):
-        return engine.spline_derivative(self.t, self.data, self.t, 1, ctx=self._ctx)
+        return self._data_derivative(1)
 
     @property
     def data_ddot(self):
-        return engine.spline_derivative(self.t, self.data, self.t, 2, ctx=self._ctx)
+        return self._data_derivative(2)
 
     @property
     def data_int(self):
-        return engine.spline_derivative(self.t, self.data, self.t, -1, ctx=self._ctx)
+        return self._data_derivative(-1)
 
     @property
     def data_iint(self):
-        return engine.spline_derivative(self.t, self.data, self.t, -2, ctx=self._ctx)
+        return self._data_derivative(-2)
 
     def LdtVector(self):
         from . import mode_calculations

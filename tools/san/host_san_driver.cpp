@@ -2,7 +2,7 @@
 // `make -C scri_amd/csrc SAN=1` compiles this file -- which INCLUDES the host side of the engine (engine_*.hip, split by entry family
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
-// pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain and of the alignment entries, the planner and the per-step
+// pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain, of the rotor interpolation and of the alignment entries, the planner and the per-step
 // math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
@@ -296,6 +296,22 @@ void frame_chain_arguments() {
   REQUIRE(modes_checks(&dummy, 2, 8, 77, &nm) == BMS_OK && nm == 77);
   REQUIRE(modes_checks(&dummy, 2, 8, 76, &nm) == BMS_ERR_INVALID);
   REQUIRE(modes_checks(&dummy, 2, MAX_ELL + 1, 1 << 30, &nm) == BMS_ERR_UNSUPPORTED);
+  // rotor interpolation: no context, then what squad_checks reads in the two host arrays (any order of the arguments is fine)
+  double ts[4] = {0.0, 0.1, 0.25, 0.3}, u[3] = {0.27, -0.5, 0.1};
+  REQUIRE(bms_squad(nullptr, ts, 4, v, BMS_HOST, u, 3, out) == BMS_ERR_INVALID);
+  REQUIRE(squad_checks(&dummy, ts, 4, u, 3) == BMS_OK);
+  REQUIRE(squad_checks(&dummy, ts, 2, u, 0) == BMS_OK);
+  REQUIRE(squad_checks(&dummy, ts, 1, u, 3) == BMS_ERR_INVALID);
+  REQUIRE(squad_checks(&dummy, ts, 0, u, 3) == BMS_ERR_INVALID);
+  REQUIRE(squad_checks(&dummy, ts, 4, u, -1) == BMS_ERR_INVALID);
+  u[1] = std::numeric_limits<double>::infinity();
+  REQUIRE(squad_checks(&dummy, ts, 4, u, 3) == BMS_ERR_INVALID);
+  REQUIRE(squad_checks(&dummy, ts, 4, u, 1) == BMS_OK);
+  u[1] = -0.5, ts[3] = std::nan("");
+  REQUIRE(squad_checks(&dummy, ts, 4, u, 3) == BMS_ERR_INVALID);
+  ts[3] = ts[2];
+  REQUIRE(squad_checks(&dummy, ts, 4, u, 3) == BMS_ERR_INVALID);
+  REQUIRE(squad_checks(&dummy, ts, 3, u, 3) == BMS_OK);
 }
 
 // The alignment entries (engine_align.hip) do the same, and their checks of the host arrays run before anything is staged.
