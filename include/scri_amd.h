@@ -334,6 +334,25 @@ int bms_mode_map(bms_ctx* ctx, void* out, int64_t ld_out, int64_t n_rows, int n_
  * the reference's loop, so the sums agree with it to the bit (and with them the parity-violation measures,
  * scri/waveform_modes.py:769-778 ...).  data c16[n_rows][ld] and out f8[n_rows] live in `mem`. */
 int bms_row_norm(bms_ctx* ctx, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int take_sqrt, double* out);
+/* Polar form of a series, WaveformBase.abs / arg / arg_unwrapped (scri/waveform_base.py:520-533): data c16[n_rows][ld] (the first n_cols
+ * columns of a row) -> abs_out = hypot(re, im) and arg_out = atan2(im, re), f8[n_rows][ld_out] each, in `mem` like the data; either
+ * (not both) may be NULL.  IEEE special cases: |inf + nan i| = inf, arg(+0 + 0i) = 0, arg(-1 + 0i) = pi, arg(-1 - 0i) = -pi, a NaN part
+ * gives a NaN angle.  unwrap != 0: arg_out is the angle unwrapped down the rows, numpy.unwrap(numpy.angle(data), axis=0) stated as an
+ * integer scan: with p the angle above and d = p[i][j] - p[i-1][j], k[i][j] = -1 if d > pi, +1 if d < -pi, else 0 (pi the double,
+ * k[0][j] = 0), K = the running sum of k down column j, arg_out[i][j] = p[i][j] + 2 pi K[i][j] rounded once; row 0 is p[0].  From the
+ * first NaN angle of a column on, that column is NaN (as numpy's cumsum leaves it); infinite parts give finite angles.  Where |d| is
+ * within a rounding of pi numpy's rounded `mod` may decide the other way.  Host and device memory give the same
+ * bits.  BMS_ERR_INVALID: NULL data, both outputs NULL, a bad mem, negative sizes, ld < n_cols, ld_out < n_cols; n_rows == 0 or
+ * n_cols == 0 writes nothing. */
+int bms_polar(bms_ctx* ctx, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int unwrap, double* abs_out,
+              double* arg_out, int64_t ld_out);
+/* rows per tile of the wrap-count scan behind bms_polar (series lengths around its multiples cross a tile edge) */
+int64_t bms_polar_tile_rows(void);
+/* *count = the elements of data c16[n_rows][ld] (first n_cols columns, in `mem`) with a non-finite real or imaginary part, *first_row =
+ * the first row that holds one, -1 if none (both host integers): the "data must be finite" check of WaveformBase.ensure_validity
+ * (scri/waveform_base.py:299-367).  n_rows == 0 or n_cols == 0 writes nothing. */
+int bms_count_nonfinite(bms_ctx* ctx, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int64_t* count,
+                        int64_t* first_row);
 /* ModesTimeSeries.grid_multiply (scri/modes_time_series.py:142-202): modes a (spin_a, l = 0..ell_max_a,
  * c16[n_times][(ell_max_a+1)^2]) and b likewise are evaluated on the (2 working_ell_max + 1)^2 equiangular grid
  * (spinsfast.salm2map), multiplied there, and the product is analysed (map2salm, spin spin_a + spin_b) into

@@ -527,6 +527,71 @@ extern "C" int bms_row_norm(bms_ctx* c, const void* data, int64_t ld, int64_t n_
   return BMS_OK;
 } BMS_CATCH(c)
 
+// WaveformBase.abs / arg / arg_unwrapped (scri/waveform_base.py:520-533) of a series in host or device memory (kernels_polar.hip).  A host
+// array is uploaded whole and goes through the same launches, so both kinds of memory give the same bits.
+extern "C" int64_t bms_polar_tile_rows(void) { return POLAR_TILE_ROWS; }
+
+extern "C" int bms_polar(bms_ctx* c, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int unwrap, double* abs_out,
+                         double* arg_out, int64_t ld_out) try {
+  if (!c || !data || (!abs_out && !arg_out)) return BMS_ERR_INVALID;
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n_rows < 0 || n_cols < 0 || ld < n_cols || ld_out < n_cols) return fail(c, BMS_ERR_INVALID, "bad sizes");
+  if (n_rows == 0 || n_cols == 0) return BMS_OK;
+  if (n_rows > (int64_t)0x7fffffff * POLAR_TILE_ROWS || n_cols > 65535 * 64) return fail(c, BMS_ERR_UNSUPPORTED, "the series is too long or too wide");
+  if (mem == BMS_DEVICE && (((uintptr_t)data & 15) || (((uintptr_t)abs_out | (uintptr_t)arg_out) & 7)))
+    return fail(c, BMS_ERR_INVALID, "device arrays must be aligned to their elements");
+  hipStream_t S = c->stream;
+  int rc;
+  const double* d_in;
+  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
+  double *d_abs = abs_out, *d_arg = arg_out;
+  long long ldo = ld_out;
+  if (mem == BMS_HOST) {
+    ldo = n_cols;
+    if (abs_out && (rc = dev_buf_t(c, "polar_abs", (size_t)n_rows * n_cols, &d_abs))) return rc;
+    if (arg_out && (rc = dev_buf_t(c, "polar_arg", (size_t)n_rows * n_cols, &d_arg))) return rc;
+  }
+  long long* d_carry = nullptr;
+  if (unwrap && arg_out)
+    if ((rc = dev_buf_t(c, "polar_carry", (size_t)polar_carry_words(n_rows, n_cols), &d_carry))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_polar(S, d_in, ld, n_rows, n_cols, unwrap, d_abs, d_arg, ldo, d_carry));
+  if (mem == BMS_HOST) {
+    if (abs_out)
+      HIP_TRY(c, hipMemcpy2DAsync(abs_out, (size_t)ld_out * 8, d_abs, (size_t)n_cols * 8, (size_t)n_cols * 8, (size_t)n_rows, hipMemcpyDeviceToHost, S));
+    if (arg_out)
+      HIP_TRY(c, hipMemcpy2DAsync(arg_out, (size_t)ld_out * 8, d_arg, (size_t)n_cols * 8, (size_t)n_cols * 8, (size_t)n_rows, hipMemcpyDeviceToHost, S));
+  }
+  HIP_TRY(c, hipStreamSynchronize(S));
+  return BMS_OK;
+} BMS_CATCH(c)
+
+// the "data must be finite" check of WaveformBase.ensure_validity (scri/waveform_base.py:299-367) where the data are
+extern "C" int bms_count_nonfinite(bms_ctx* c, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int64_t* count,
+                                   int64_t* first_row) try {
+  if (!c || !data || !count || !first_row) return BMS_ERR_INVALID;
+  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n_rows < 0 || n_cols < 0 || ld < n_cols) return fail(c, BMS_ERR_INVALID, "bad sizes");
+  if (n_rows == 0 || n_cols == 0) return BMS_OK;
+  if (mem == BMS_DEVICE && ((uintptr_t)data & 15)) return fail(c, BMS_ERR_INVALID, "device arrays must be aligned to their elements");
+  hipStream_t S = c->stream;
+  int rc;
+  const double* d_in;
+  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
+  unsigned long long* d_acc;
+  if ((rc = dev_buf_t(c, "polar_acc", 2, &d_acc))) return rc;
+  HIP_TRY(c, hipMemsetAsync(d_acc, 0, 8, S));
+  HIP_TRY(c, hipMemsetAsync(d_acc + 1, 0xff, 8, S));
+  TIMED(c, BMS_TAG_POINTWISE, launch_count_nonfinite(S, d_in, ld, n_rows, n_cols, d_acc));
+  unsigned long long acc[2];
+  HIP_TRY(c, hipMemcpyAsync(acc, d_acc, 16, hipMemcpyDeviceToHost, S));
+  HIP_TRY(c, hipStreamSynchronize(S));
+  *count = (int64_t)acc[0];
+  *first_row = acc[0] ? (int64_t)acc[1] : -1;
+  return BMS_OK;
+} BMS_CATCH(c)
+
 // ModesTimeSeries.grid_multiply (scri/modes_time_series.py:142-202): both mode sets (l_min = 0) are synthesised on the
 // (2W+1) x (2W+1) equiangular grid, multiplied there, and the product (spin s_a + s_b) is analysed up to output_ell_max.
 extern "C" int bms_grid_multiply(bms_ctx* c, const void* a, int spin_a, int ell_max_a, const void* b, int spin_b, int ell_max_b,

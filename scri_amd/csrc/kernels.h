@@ -435,6 +435,16 @@ long long paired_unpack_carry_words(long long n_rows, int n_modes);
 hipError_t launch_paired_unpack(hipStream_t stream, const void* words, long long n_rows, const int* own, int n_own, const int* partner,
                                 int n_modes, void* carry, void* seed, void* out, long long ld_out);
 
+// ---- polar form of a series (kernels_polar.hip; scri/waveform_base.py:520-533): abs = hypot(re, im), arg = atan2(im, re), and the angle
+// unwrapped down the rows by an integer wrap count (p + 2 pi K, NaN from the first NaN angle of a column on)
+constexpr int POLAR_TILE_ROWS = 64;  // rows per tile of the wrap-count scan
+long long polar_carry_words(long long n_rows, int n_cols);  // 64-bit words of `carry`
+// in c16[n_rows][ld] -> abs_out, arg_out f8[n_rows][ld_out] (one may be null); unwrap != 0: arg_out is the unwrapped angle (carry needed)
+hipError_t launch_polar(hipStream_t stream, const void* in, long long ld, long long n_rows, int n_cols, int unwrap, double* abs_out,
+                        double* arg_out, long long ld_out, void* carry);
+// acc[0] += elements with a non-finite part, acc[1] = min(acc[1], first row holding one); acc preset to (0, all ones)
+hipError_t launch_count_nonfinite(hipStream_t stream, const void* in, long long ld, long long n_rows, int n_cols, unsigned long long* acc);
+
 // centre-of-mass track and drift fit of the horizon trajectories (scri/SpEC/com_motion.py), kernels_com.hip
 constexpr int COM_FIT_TILE = 256;  // panels (two intervals each) per partial of the moment sums: one per thread of a workgroup
 constexpr int COM_FIT_OUT = 24;    // doubles of the fit's result block (com_fit_kernel)

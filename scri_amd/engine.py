@@ -922,6 +922,73 @@ def row_norm(data, take_sqrt=False, ctx=None, device_tensor=None):
     return out
 
 
+def polar_tile_rows():
+    """rows per tile of the wrap-count scan behind abs_arg(unwrap=True) (bms_polar_tile_rows)"""
+    return int(_lib.load().bms_polar_tile_rows())
+
+
+POLAR_TILE_ROWS = polar_tile_rows()  # the kernel's constant: series lengths around its multiples cross a tile edge
+
+def _polar_series_arg(ctx, data):
+    """(address, row stride, rows, columns, memory kind, trailing shape, the array) of a series [N, ...]: a numpy array, or a device
+    tensor [N, n_cols] (complex128, unit column stride, any row stride)"""
+    if hasattr(data, "data_ptr"):
+        import torch
+
+        from . import device_series
+
+        device_series.attach(ctx)
+        _on_device_of(ctx, data)
+        if data.dtype != torch.complex128 or data.ndim != 2 or (data.shape[1] > 1 and data.stride(1) != 1):
+            raise ValueError(f"a device series must be complex128 [N, n_cols] with unit column stride, got {data.dtype} of shape {tuple(data.shape)}")
+        n_rows, n_cols = int(data.shape[0]), int(data.shape[1])
+        return c_vp(data.data_ptr()), (data.stride(0) if n_rows > 1 else max(n_cols, 1)), n_rows, n_cols, BMS_DEVICE, (n_cols,), data
+    data = _lib.as_c16(data)
+    if data.ndim < 1:
+        raise ValueError("a series has a time axis")
+    d2 = data.reshape(data.shape[0], int(np.prod(data.shape[1:])))
+    return vptr(d2), max(d2.shape[1], 1), d2.shape[0], d2.shape[1], BMS_HOST, data.shape[1:], d2
+
+
+def abs_arg(data, unwrap=False, want=("abs", "arg"), ctx=None):
+    """bms_polar: |data| and the angle atan2(im, re) of a complex series data[N, ...] (axis 0 = time), the statements numpy.abs and
+    numpy.angle; with unwrap=True the angle is unwrapped along the time axis, the statement numpy.unwrap(numpy.angle(data), axis=0).
+    A numpy array in gives numpy arrays out; a device tensor in ([N, n_cols] complex128, unit column stride, any row stride) gives
+    float64 device tensors out, so amplitude and phase stay in HBM.  want: the results to compute, in the order they are returned
+    (a tuple); one name as a string returns that array alone."""
+    ctx = _ctx(ctx)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or len(set(names)) != len(names) or not set(names) <= {"abs", "arg"}:
+        raise ValueError(f"want names 'abs' and / or 'arg', got {want!r}")
+    ptr, ld, n_rows, n_cols, mem, tail, _keep = _polar_series_arg(ctx, data)
+    if mem == BMS_DEVICE:
+        import torch
+
+        out = {k: torch.empty((n_rows, n_cols), dtype=torch.float64, device=data.device) for k in names}
+        address = lambda x: c_vp(x.data_ptr())  # noqa: E731
+    else:
+        out = {k: np.empty((n_rows, n_cols)) for k in names}
+        address = vptr
+    if n_rows and n_cols:
+        rc = _lib.load().bms_polar(ctx.handle, ptr, ld, n_rows, n_cols, mem, int(bool(unwrap)), address(out["abs"]) if "abs" in out else None,
+                                   address(out["arg"]) if "arg" in out else None, n_cols)
+        ctx.check(rc, "bms_polar")
+    res = tuple(out[k] if mem == BMS_DEVICE else out[k].reshape((n_rows,) + tuple(tail)) for k in names)
+    return res[0] if isinstance(want, str) else res
+
+
+def count_nonfinite(data, ctx=None):
+    """bms_count_nonfinite: (the number of elements of the complex series data[N, ...] with a non-finite real or imaginary part, the
+    first row that holds one or -1).  data: a numpy array, or a device tensor as abs_arg takes it (it stays where it is)."""
+    ctx = _ctx(ctx)
+    ptr, ld, n_rows, n_cols, mem, _tail, _keep = _polar_series_arg(ctx, data)
+    count, first = c_i64(0), c_i64(-1)
+    if n_rows and n_cols:
+        rc = _lib.load().bms_count_nonfinite(ctx.handle, ptr, ld, n_rows, n_cols, mem, ctypes.byref(count), ctypes.byref(first))
+        ctx.check(rc, "bms_count_nonfinite")
+    return int(count.value), int(first.value)
+
+
 def _modes_arg(data, n, ell_min, ell_max):
     """(address, row stride, memory kind, object to keep alive) of modes [n, n_modes]: a numpy array on the host, or a torch tensor
     (complex128, unit column stride) for modes resident on the GPU"""

@@ -406,9 +406,28 @@ class ModeOperators:
         times = time_intersection(self.t, w_a.t)
         # A's modes may come in another order: column of (l, m) in this object for every column of A
         order = np.array([self.index(ell, m) for ell, m in w_a.LM], dtype=int)
-        data = engine.cubic_spline(w_a.t, w_a.data, times, ctx=self._ctx) - engine.cubic_spline(self.t, self.data[:, order], times, ctx=self._ctx)
+        # With either waveform resident on the GPU the difference is formed and left there: both series go through the same spline
+        # launches on device tensors (a host-resident partner is uploaded as a copy; neither object changes residency), the subtraction
+        # with A's column order is one mode-map launch (1 a + (-1) b[order]: exact products, the one rounding of a - b), and the frames
+        # go through the GPU squad.  Two host-resident waveforms take the host statements below.
+        dev = None
+        if getattr(self, "is_device_resident", False) or getattr(w_a, "is_device_resident", False):
+            from . import _lib, device_series
+
+            ctx = next((c for c in (self._ctx, w_a._ctx) if c is not None), None) or _lib.default_context()
+            on_device = lambda w: w._dev if w.is_device_resident else device_series.to_device(ctx, w.data)  # noqa: E731
+            series = lambda w, y: device_series.DeviceModesTimeSeries(y, times, 0, w.ell_min, w.ell_max, ctx=ctx)  # noqa: E731
+            a = series(w_a, engine.cubic_spline(w_a.t, on_device(w_a), times, ctx=ctx))
+            b = series(self, engine.cubic_spline(self.t, on_device(self), times, ctx=ctx))
+            n = a.buf.shape[1]
+            dev = a._map(n, np.arange(n, dtype=np.int32), np.ones(n, dtype=complex), other=b, idx_b=order, coef_b=np.full(n, -1.0 + 0.0j))
+            squad = lambda f, t: engine.squad(f, t, times, ctx=ctx)  # noqa: E731
+        else:
+            ctx = self._ctx
+            data = engine.cubic_spline(w_a.t, w_a.data, times, ctx=ctx) - engine.cubic_spline(self.t, self.data[:, order], times, ctx=ctx)
+            squad = lambda f, t: quaternions.squad(f, t, times)  # noqa: E731
         fa, fb = np.asarray(w_a.frame, dtype=float).reshape(-1, 4), np.asarray(self.frame, dtype=float).reshape(-1, 4)
-        at = lambda f, t: quaternions.squad(f, t, times) if f.shape[0] > 1 else f  # noqa: E731
+        at = lambda f, t: squad(f, t) if f.shape[0] > 1 else f  # noqa: E731
         if fa.shape[0] >= 1 and fb.shape[0] >= 1:
             frame = quaternions.multiply(at(fa, w_a.t), quaternions.conjugate(at(fb, self.t)) / np.sum(at(fb, self.t) ** 2, axis=-1, keepdims=True))
         elif fb.shape[0] >= 1:
@@ -421,14 +440,16 @@ class ModeOperators:
         frame = np.atleast_2d(frame)
         if frame.shape[0] == times.shape[0] and frame.shape[0] > 1:
             # mean rotor in the chordal metric: the normalised time integral of the rotor series
-            mean = engine.spline_derivative(times, frame.astype(complex), times[-1:], order=-1, ctx=self._ctx).real[0]
+            mean = engine.spline_derivative(times, frame.astype(complex), times[-1:], order=-1, ctx=ctx).real[0]
             if mean[0] < 0:  # nearer to -1 than to +1: |R + 1| < |R - 1|
                 frame = -frame
         elif frame.shape[0] == 1 and frame[0, 0] < 0:
             frame = -frame
-        W = WaveformModes(t=times, data=data, history=[], frame=frame, frameType=self.frameType, dataType=self.dataType,
-                          r_is_scaled_out=self.r_is_scaled_out, m_is_scaled_out=self.m_is_scaled_out, ell_min=w_a.ell_min, ell_max=w_a.ell_max,
-                          ctx=self._ctx)
+        W = WaveformModes(t=times, data=np.empty((0, dev.shape[1])) if dev is not None else data, history=[], frame=frame, frameType=self.frameType,
+                          dataType=self.dataType, r_is_scaled_out=self.r_is_scaled_out, m_is_scaled_out=self.m_is_scaled_out, ell_min=w_a.ell_min,
+                          ell_max=w_a.ell_max, ctx=ctx)
+        if dev is not None:
+            W._host, W._dev = None, dev
         W.history += ["B.compare(A)\n", "### A.history.str():\n" + "".join(w_a.history), "### B.history.str():\n" + "".join(self.history),
                       "### End of old histories from `compare`"]
         return W

@@ -151,13 +151,19 @@ class WaveformModes(ModeOperators):
             errors.append("frame must have 0, 1 or n_times elements")
         if not np.all(np.isfinite(self.frame)):
             errors.append("frame must be finite")
-        if self.data.shape[0] != self.n_times:
+        if self.is_device_resident:  # weights in HBM are checked there (bms_count_nonfinite) and stay there
+            shape, is_complex = self._data_shape(), str(self._dev.dtype) == "torch.complex128"
+            finite = not is_complex or engine.count_nonfinite(self._dev, ctx=self._ctx)[0] == 0
+        else:
+            shape, is_complex = self.data.shape, self.data.dtype == np.dtype(complex)
+            finite = np.all(np.isfinite(self.data.view(float)))
+        if shape[0] != self.n_times:
             errors.append("data.shape[0] != n_times")
-        if not np.all(np.isfinite(self.data.view(float))):
+        if not finite:
             errors.append("data must be finite")
-        if self.data.dtype != np.dtype(complex):
+        if not is_complex:
             errors.append("data must be complex")
-        if self.data.shape[1] != LM_total_size(self.ell_min, self.ell_max):
+        if shape[1] != LM_total_size(self.ell_min, self.ell_max):
             errors.append("data.shape[1] inconsistent with ell range")
         if errors:
             if assertions:
@@ -207,16 +213,27 @@ class WaveformModes(ModeOperators):
     def data_2d(self):
         return self.data.reshape((self.n_times, self.n_data_sets))
 
+    # amplitude and phase (waveform_base.py:520-533).  Weights resident on the GPU are read there (bms_polar) and stay there; the result
+    # is the host array of the reference's properties.  `engine.abs_arg(w._dev, ...)` keeps the results in HBM as well.
+    def _polar(self, what, unwrap=False):
+        return engine.abs_arg(self._dev, unwrap=unwrap, want=what, ctx=self._ctx).cpu().numpy()
+
     @property
     def abs(self):
+        if self.is_device_resident:
+            return self._polar("abs")
         return np.abs(self.data)
 
     @property
     def arg(self):
+        if self.is_device_resident:
+            return self._polar("arg")
         return np.angle(self.data)
 
     @property
     def arg_unwrapped(self):
+        if self.is_device_resident:
+            return self._polar("arg", unwrap=True)
         return np.unwrap(np.angle(self.data), axis=0)
 
     def norm(self, take_sqrt=False, indices=slice(None, None, None)):
@@ -225,8 +242,17 @@ class WaveformModes(ModeOperators):
         # the reference adds re^2 + im^2 column by column (complex_array_norm / complex_array_abs, waveform_base.py:19-35); the same
         # order here, so the sums agree to the bit.  Weights resident on the GPU are reduced there (bms_row_norm); a host array is
         # reduced where it is -- one pass over it, against an upload of the whole series.
-        if self.is_device_resident and indices == slice(None, None, None) and len(self._data_shape()) == 2:
-            return engine.row_norm(None, take_sqrt=take_sqrt, ctx=self._ctx, device_tensor=self._dev)
+        # A slice of the times is reduced there as a strided view (the kernel takes the row stride; every row's sum has its own order,
+        # so the bits are the host loop's); a negative step, which a device view cannot have, gathers its rows into a copy first.
+        if self.is_device_resident and isinstance(indices, slice) and len(self._data_shape()) == 2:
+            start, stop, step = indices.indices(self._data_shape()[0])
+            if step > 0:
+                view = self._dev[start:stop:step]
+            else:
+                import torch
+
+                view = self._dev.index_select(0, torch.arange(start, stop, step, device=self._dev.device))
+            return engine.row_norm(None, take_sqrt=take_sqrt, ctx=self._ctx, device_tensor=view)
         d = self.data_2d[indices]
         n = np.zeros(d.shape[0], dtype=float)
         for j in range(d.shape[1]):
