@@ -86,7 +86,22 @@ int bms_ctx_get_eval_stats(bms_ctx* ctx, int64_t* out /* [3] */, int reset);
  * out[2] = launches of the LDS-resident, the staged matrix-core and the VALU kernel since the last reset, out[3] = waves per
  * workgroup (4, 3, 2 or 1, by ell_max) of the most recent VALU launch, 0 if there was none.  Host counters; no reference counterpart. */
 int bms_ctx_get_rotate_stats(bms_ctx* ctx, int64_t* out /* [4] */, int reset);
-/* block until all work queued by this context has finished */
+/* STREAM-ORDERED RETURN.  bms_transform_modes and bms_transform_modes_shard return WITHOUT waiting for the device when all of this
+ * holds: the data is device-resident (mem == BMS_DEVICE, the result goes to a device pointer); the context runs on a stream the caller
+ * named (bms_ctx_set_stream with a handle, or bms_ctx_use_default_stream -- with the context's own stream the caller has nothing to
+ * order on, so those calls wait); the call is warm, i.e. every table it needs was kept by the context and nothing was copied out of
+ * host memory for it (a first call, a call on a new time axis or transformation, a call that runs in several chunks or again after
+ * a failed allocation all wait as before); and the context option ASYNC_RETURN is on (the default; bms_ctx_set_option(ctx,
+ * "ASYNC_RETURN", 0) or the environment variable SCRI_AMD_NO_ASYNC_RETURN when the context is created switch it off).  The contract
+ * of such a call: the result, and the moment the input may be overwritten or freed, are ORDERED ON THE CONTEXT'S STREAM -- work the
+ * caller queues there afterwards sees the result, and further calls of the context follow in order; the host must not read the
+ * result or reuse the input from another stream before bms_ctx_synchronize (the host-side wait) or a wait on that stream of its own.
+ * t_out, *n_times_out and *first_index_out are host values and complete at the return.  Errors in the arguments still fail at the
+ * call; an error of a kernel surfaces at the next wait.  Host-memory calls, grids sent to the host and every other entry point wait
+ * as they always did.  out[0] = calls that returned without waiting since the last reset, out[1] = 1 while one may still be running.
+ * Host counters; no reference counterpart. */
+int bms_ctx_get_async_stats(bms_ctx* ctx, int64_t* out /* [2] */, int reset);
+/* block until all work queued by this context has finished: the host-side wait of a stream-ordered return */
 int bms_ctx_synchronize(bms_ctx* ctx);
 
 /* Optional per-kernel timing: when enabled every kernel launch is bracketed by two HIP events on the

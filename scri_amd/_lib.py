@@ -90,6 +90,7 @@ SIGNATURES = {
     "bms_ctx_reserve": (c_int, [c_vp, ctypes.c_uint64]),
     "bms_ctx_get_eval_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
     "bms_ctx_get_rotate_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
+    "bms_ctx_get_async_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
     "bms_ctx_synchronize": (c_int, [c_vp]),
     "bms_ctx_enable_timing": (c_int, [c_vp, c_int]),
     "bms_ctx_get_timing": (c_int, [c_vp, c_dp, ctypes.POINTER(c_i64), c_int]),
@@ -503,6 +504,13 @@ class Context:
         out = (c_i64 * 4)()
         self.check(load().bms_ctx_get_rotate_stats(self._h, out, 1 if reset else 0), "bms_ctx_get_rotate_stats")
         return tuple(int(v) for v in out)
+
+    def async_stats(self, reset=True):
+        """(transformations that returned stream-ordered, i.e. without a host-side wait, since the last reset; whether one may still be
+        running).  Such a call's result is ordered on the context's stream: `synchronize()` is the host-side wait (include/scri_amd.h)."""
+        out = (c_i64 * 2)()
+        self.check(load().bms_ctx_get_async_stats(self._h, out, 1 if reset else 0), "bms_ctx_get_async_stats")
+        return int(out[0]), bool(out[1])
 
     def reserve(self, nbytes=0):
         """One device allocation of `nbytes` (0: one and a half times the work-space cap) that the context's work-space buffers are carved from

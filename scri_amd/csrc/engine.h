@@ -193,6 +193,15 @@ struct bms_ctx {
   // set by SharedPieceTables around the per-piece calls of a pipelined call: the pieces share one transformation, so the
   // per-direction tables are computed (and read back) once, and a piece returns without waiting for its kernels
   bool async_pieces = false;
+  // Stream-ordered return (option ASYNC_RETURN): a transformation of device-resident data on a stream the caller gave
+  // leaves without waiting for it unless the call queued a copy out of host memory that does not outlive it (upload() and the other
+  // staging copies raise host_copy_queued; the entry point lowers it).  async_pending: such a call may still be running -- whatever is
+  // about to write the context's buffers from ANOTHER stream, or moves the context to another stream, drains c->stream first
+  // (drain_async_return).
+  bool host_copy_queued = false;
+  bool async_pending = false;
+  bool chunk_retry = false;  // with_smaller_chunks runs the call again after a failed allocation
+  uint64_t async_returns = 0;  // calls that returned without waiting since the last reset (bms_ctx_get_async_stats)
   bool piece_tables_valid = false;
   void* piece_tables = nullptr;  // PieceTables*
   // constant rotors of internal rotations travel through a page-locked ring (a truly asynchronous copy: no stream
@@ -326,6 +335,15 @@ BMS_INTERNAL int exception_status(bms_ctx* c) noexcept;
     }                                                                                                        \
   } while (0)
 
+// Before work goes to a stream other than c->stream (the auxiliary stream's set-up kernels, the pipelines' transfers): a call that
+// returned stream-ordered may still read the buffers that work writes.
+inline int drain_async_return(bms_ctx* c) {
+  if (!c->async_pending) return BMS_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->async_pending = false;
+  return BMS_OK;
+}
+
 inline bool valid_mem(int mem) { return mem == BMS_HOST || mem == BMS_DEVICE; }
 constexpr int MAX_ELL = 8192;  // 2 (l + 1)^2 fits an int with room; tables of such an l are far beyond any device's memory anyway
 
@@ -372,7 +390,9 @@ inline int with_smaller_chunks(bms_ctx* c, F call) {
     c->ws_limit /= 2;
     c->alloc_failed = false;
     c->eval_tiles = tiles0;  // (diagnostic counter: the failed attempt's launches, if any, are not counted twice)
+    c->chunk_retry = true;   // (an attempt after a failed allocation ends with the host-side wait)
     rc = call();
+    c->chunk_retry = false;
   }
   if (rc == BMS_OK) c->sticky_limit = c->ws_limit, c->sticky_left = 16;
   c->ws_limit = full;
@@ -450,6 +470,7 @@ inline int run_dealt_over_contexts(bms_ctx* const* ctxs, int n_ctx, int pieces, 
 template <class Up, class Compute, class Down>
 int run_host_pipeline(bms_ctx* c, int k0, int k1, bool in_place, bool host_waits, const char* err_first, const char* err, Up up,
                       Compute compute, Down down) {
+  if (int rc0 = drain_async_return(c)) return rc0;
   if (!c->pipe_up) {
     HIP_TRY(c, hipStreamCreateWithFlags(&c->pipe_up, hipStreamNonBlocking));
     HIP_TRY(c, create_download_stream(c));

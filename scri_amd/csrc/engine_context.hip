@@ -258,10 +258,11 @@ extern "C" int bms_host_unregister(void* p) try {
 // old one is drained, so that no slot still waits for its copy on a stream nobody will synchronise any more.
 static int switch_stream(bms_ctx* c, hipStream_t s) {
   if (s == c->stream) return BMS_OK;
-  if (c->rot_ring_next) {
+  if (c->rot_ring_next || c->async_pending) {  // (a call that returned stream-ordered may still run on the old stream)
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->rot_ring_next = 0;
+    c->async_pending = false;
   }
   c->stream = s;
   return BMS_OK;
@@ -356,6 +357,16 @@ extern "C" int bms_ctx_get_rotate_stats(bms_ctx* c, int64_t* out /*[4]*/, int re
   return BMS_OK;
 } BMS_CATCH(c)
 
+// Stream-ordered return (option ASYNC_RETURN): out[0] = transformations that returned without a host-side wait since the last reset,
+// out[1] = 1 while such a call may still be running (nothing has waited for the context's stream since).  Host counters only.
+extern "C" int bms_ctx_get_async_stats(bms_ctx* c, int64_t* out /*[2]*/, int reset) try {
+  if (!c || !out) return BMS_ERR_INVALID;
+  out[0] = (int64_t)c->async_returns;
+  out[1] = c->async_pending ? 1 : 0;
+  if (reset) c->async_returns = 0;
+  return BMS_OK;
+} BMS_CATCH(c)
+
 extern "C" int bms_ctx_enable_timing(bms_ctx* c, int on) try {
   if (!c) return BMS_ERR_INVALID;
   c->timing = on != 0;
@@ -392,5 +403,6 @@ extern "C" int bms_ctx_synchronize(bms_ctx* c) try {
   if (!c) return BMS_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->async_pending = false;
   return BMS_OK;
 } BMS_CATCH(c)

@@ -58,6 +58,7 @@ extern "C" int bms_transform_modes_shard(bms_ctx* c, const bms_wm_input* in, con
                                          int64_t* first_index_out) try {
   if (!c) return BMS_ERR_INVALID;
   if (!data_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
+  c->host_copy_queued = false;  // (raised by every copy this call queues out of host memory: it then ends with the host-side wait)
   return with_smaller_chunks(c, [&] { return transform_modes_impl(c, in, tr, sh, t_out, data_out, n_times_out, first_index_out, nullptr); });
 } BMS_CATCH(c)
 
@@ -798,8 +799,21 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   for (int64_t i = 0; i < n_new; ++i) t_out[i] = (1 / T.gamma) * (in->t[i_lo + i] - T.tt);
   // (the walk of this call covered the kept axis entry's range exactly when the entry was asked for ahead of it)
   time_axis_commit(c, kt.times_ahead, regular_mesh);
-  // host tables above are stack/vector memory: wait for the uploads (and results) before returning
-  if (!c->async_pieces) HIP_TRY(c, hipStreamSynchronize(S));
+  // Stream-ordered return (include/scri_amd.h): device-resident data in and out on a stream the CALLER gave, one
+  // chunk, and nothing queued here reads host memory of this call (a warm call: every table was found in the context) -- the result
+  // and the reuse of the input are ordered on that stream, and the work buffers are written by the next call on the same stream only
+  // (what goes to another stream drains first: drain_async_return).  Everything else waits: host tables above are stack / vector
+  // memory, and a caller of the context's own stream has no handle to order on.
+  const bool ordered_return = !c->async_pieces && c->opt.on(OPT_ASYNC_RETURN) && S != c->own_stream && in->mem == BMS_DEVICE && !grid_out &&
+                              !c->host_copy_queued && !c->chunk_retry && !walk_first && plan.chunk >= n_new;
+  if (ordered_return) {
+    drain.skip = true;
+    c->async_pending = true;
+    ++c->async_returns;
+  } else if (!c->async_pieces) {
+    HIP_TRY(c, hipStreamSynchronize(S));
+    c->async_pending = false;
+  }
   trace.mark("final synchronize");
   return BMS_OK;
 }

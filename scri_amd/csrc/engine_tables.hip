@@ -453,6 +453,7 @@ int run_analysis(bms_ctx* c, const AnalysisPlan& A, const double* d_G, long long
 int upload(bms_ctx* c, const char* name, const void* host, size_t bytes, void** dev) {
   int rc = dev_buf(c, name, bytes, dev);
   if (rc) return rc;
+  c->host_copy_queued = true;  // (`host` may not outlive the call: it ends with a host-side wait)
   HIP_TRY(c, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, c->stream));
   return BMS_OK;
 }
@@ -918,6 +919,9 @@ int device_pixel_tables(bms_ctx* c, const bms_transformation* tr, PixelTables& T
   cplx* d_coefs;
   int rc = dev_buf_t(c, keep ? "pc_coefs" : "pix_coefs", (size_t)3 * nst, &d_coefs);
   if (rc) return rc;
+  // (the blocks below are rewritten on PS: an earlier call that returned stream-ordered may still read them on the main stream)
+  if (PS != c->stream && (rc = drain_async_return(c))) return rc;
+  c->host_copy_queued = true;
   HIP_TRY(c, hipMemcpyAsync(d_coefs, coefs.data(), sizeof(cplx) * 3 * nst, hipMemcpyHostToDevice, PS));
   P.st = d_coefs;
   P.c0 = coef0 ? d_coefs + nst : nullptr;

@@ -45,47 +45,59 @@ namespace bms {
   X(NO_FUSED_ABD_MIX, "NO_FUSED_ABD_MIX")                      \
   X(NO_ROTATE_PIPELINE, "NO_ROTATE_PIPELINE")
 
+// One more option follows the route flags in the same array; it is not a choice between routes and it defaults to ON:
+//   ASYNC_RETURN  1 (default) / 0: a device-resident transformation on a stream the caller gave returns without a host-side wait
+//                 (include/scri_amd.h); it changes WHEN a call returns, never what it computes.  The environment
+//                 switches it OFF: SCRI_AMD_NO_ASYNC_RETURN.
 enum RouteOpt : int {
 #define X(e, n) OPT_##e,
   BMS_ROUTE_OPTIONS(X)
 #undef X
-      OPT_COUNT
+      OPT_COUNT,  // (the route flags end here)
+  OPT_ASYNC_RETURN = OPT_COUNT,
+  OPT_TOTAL
 };
 
 inline const char* route_option_name(int i) {
-  static const char* const names[OPT_COUNT] = {
+  static const char* const names[OPT_TOTAL] = {
 #define X(e, n) n,
       BMS_ROUTE_OPTIONS(X)
 #undef X
+      "ASYNC_RETURN",
   };
-  return (i >= 0 && i < OPT_COUNT) ? names[i] : nullptr;
+  return (i >= 0 && i < OPT_TOTAL) ? names[i] : nullptr;
 }
 
 // "NO_GEMM_EVAL" or "SCRI_AMD_NO_GEMM_EVAL" -> index, -1 if there is no such option
 inline int route_option_index(const char* name) {
   if (!name) return -1;
   if (std::strncmp(name, "SCRI_AMD_", 9) == 0) name += 9;
-  for (int i = 0; i < OPT_COUNT; ++i)
+  for (int i = 0; i < OPT_TOTAL; ++i)
     if (std::strcmp(name, route_option_name(i)) == 0) return i;
   return -1;
 }
 
 struct RouteOptions {
-  long long v[OPT_COUNT] = {0};
-  RouteOptions() { v[OPT_AXIS_BOOST_MIN_WORK] = -1; }
+  long long v[OPT_TOTAL] = {0};
+  RouteOptions() {
+    v[OPT_AXIS_BOOST_MIN_WORK] = -1;
+    v[OPT_ASYNC_RETURN] = 1;
+  }
   bool on(RouteOpt o) const { return v[o] != 0; }
   // The context's defaults, read from the environment ONCE (bms_ctx_create is the only caller): a flag is on when its variable is set to
   // anything but "0" or the empty string; the numeric options take the number.
   void read_environment() {
-    for (int i = 0; i < OPT_COUNT; ++i) {
+    for (int i = 0; i < OPT_TOTAL; ++i) {
       char full[64] = "SCRI_AMD_";
-      std::strncat(full, route_option_name(i), sizeof full - 10);
+      std::strncat(full, i == OPT_ASYNC_RETURN ? "NO_ASYNC_RETURN" : route_option_name(i), sizeof full - 10);
       const char* e = std::getenv(full);
       if (!e) continue;
       if (i == OPT_AXIS_BOOST_MIN_WORK) {
         v[i] = std::atoll(e) > 0 ? std::atoll(e) : 0;
       } else if (i == OPT_GEMM_EVAL_STEP) {
         v[i] = std::atoll(e);
+      } else if (i == OPT_ASYNC_RETURN) {  // (the variable switches the default OFF)
+        v[i] = (e[0] == 0 || std::strcmp(e, "0") == 0) ? 1 : 0;
       } else {
         v[i] = (e[0] == 0 || std::strcmp(e, "0") == 0) ? 0 : 1;
       }

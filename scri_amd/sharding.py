@@ -370,6 +370,7 @@ class ShardedTransform:
         t_out, n_new, first = engine.transform_modes(
             self.t_global, ext.data_ptr(), self.ell_min, self.ell_max, self.spin_weight, self.conformal_weight, self.type_term, self.tr,
             aux=aux, ctx=self.ctx, device=True, ld=ext.stride(0), out_ptr=out.data_ptr(), shard=shard)
+        self._sync_after_engine(ext)  # (a warm call returns stream-ordered: torch reads `out` on ITS stream)
         return t_out, out[:n_new], first
 
     def _split_columns(self, block):
@@ -414,6 +415,15 @@ class ShardedTransform:
         same = getattr(self.ctx, "stream_handle", None) == torch.cuda.current_stream(tensor.device).cuda_stream
         if not same:
             torch.cuda.synchronize(tensor.device)
+
+    def _sync_after_engine(self, tensor):
+        """The other direction: a warm device-resident transformation returns without a host-side wait, its result ordered on the
+        context's stream (include/scri_amd.h).  When that is torch's current stream, what torch does with the result follows in
+        order; otherwise the host waits for the context here."""
+        import torch
+
+        if getattr(self.ctx, "stream_handle", None) != torch.cuda.current_stream(tensor.device).cuda_stream:
+            self.ctx.synchronize()
 
     def own_rows_view(self, like=None):
         """"rows", WaveformModes: the place of this rank's own rows inside the exchange buffer.  A caller that keeps its
