@@ -86,6 +86,11 @@ int bms_ctx_get_eval_stats(bms_ctx* ctx, int64_t* out /* [3] */, int reset);
  * out[2] = launches of the LDS-resident, the staged matrix-core and the VALU kernel since the last reset, out[3] = waves per
  * workgroup (4, 3, 2 or 1, by ell_max) of the most recent VALU launch, 0 if there was none.  Host counters; no reference counterpart. */
 int bms_ctx_get_rotate_stats(bms_ctx* ctx, int64_t* out /* [4] */, int reset);
+/* Which instance of the back substitution + evaluation on the grid served the transformations: out[0] = kernel launches that read the
+ * output times from the window staged in LDS (the lanes of a wave within a few samples of each other), out[1] = launches of the
+ * instance that gathers them (large supertranslations, strong boosts at large |t|), since the last reset.  One call of a
+ * transformation makes one launch per run of time tiles of the same kind.  Host counters; no reference counterpart. */
+int bms_ctx_get_backward_stats(bms_ctx* ctx, int64_t* out /* [2] */, int reset);
 /* STREAM-ORDERED RETURN.  bms_transform_modes and bms_transform_modes_shard return WITHOUT waiting for the device when all of this
  * holds: the data is device-resident (mem == BMS_DEVICE, the result goes to a device pointer); the context runs on a stream the caller
  * named (bms_ctx_set_stream with a handle, or bms_ctx_use_default_stream -- with the context's own stream the caller has nothing to

@@ -90,6 +90,7 @@ SIGNATURES = {
     "bms_ctx_reserve": (c_int, [c_vp, ctypes.c_uint64]),
     "bms_ctx_get_eval_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
     "bms_ctx_get_rotate_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
+    "bms_ctx_get_backward_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
     "bms_ctx_get_async_stats": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int]),
     "bms_ctx_synchronize": (c_int, [c_vp]),
     "bms_ctx_enable_timing": (c_int, [c_vp, c_int]),
@@ -503,6 +504,13 @@ class Context:
         VALU launch) of the rotations since the last reset"""
         out = (c_i64 * 4)()
         self.check(load().bms_ctx_get_rotate_stats(self._h, out, 1 if reset else 0), "bms_ctx_get_rotate_stats")
+        return tuple(int(v) for v in out)
+
+    def backward_stats(self, reset=True):
+        """(kernel launches of the back substitution + evaluation on the grid that read their output times from the staged window, launches
+        of the instance that gathers them) since the last reset"""
+        out = (c_i64 * 2)()
+        self.check(load().bms_ctx_get_backward_stats(self._h, out, 1 if reset else 0), "bms_ctx_get_backward_stats")
         return tuple(int(v) for v in out)
 
     def async_stats(self, reset=True):

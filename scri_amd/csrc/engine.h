@@ -188,6 +188,9 @@ struct bms_ctx {
   // which rotation kernel served the calls since the last reset (bms_ctx_get_rotate_stats): launches of the resident, staged and VALU
   // kernels, and the waves per workgroup of the most recent VALU launch as its launcher reported them
   uint64_t rot_launches[3] = {0, 0, 0};
+  // kernel launches of the back substitution + evaluation on the grid since the last reset (bms_ctx_get_backward_stats): of the
+  // instance that reads its abscissae from the staged window, and of the one that gathers them (launch_bspline_backward_eval)
+  unsigned long long bwd_launches[2] = {0, 0};
   int rot_valu_waves = 0;
   hipStream_t pipe_up = nullptr, pipe_down = nullptr;  // run_host_pipeline: uploads and downloads beside the kernels
   // set by SharedPieceTables around the per-piece calls of a pipelined call: the pieces share one transformation, so the

@@ -220,7 +220,8 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
   }
 
   // ---- chunk loop: 6 fields x (Y, R, G)
-  const BsplineSpread spread = skew_spread(T, cA, cB, u);
+  BsplineSpread spread = skew_spread(T, cA, cB, u);
+  spread.launches = c->bwd_launches;
   const double bytes_per_row = 19.0 * ldg * 8.0;  // 6 x (Y, R, G) + F
   ChunkPlan plan;
   if ((rc = plan_chunks(c, c->ws_limit, bytes_per_row, n_new, regular_mesh, n, "six ", n_cols, plan))) return rc;

@@ -357,6 +357,16 @@ extern "C" int bms_ctx_get_rotate_stats(bms_ctx* c, int64_t* out /*[4]*/, int re
   return BMS_OK;
 } BMS_CATCH(c)
 
+// Which instance of bspline_backward_eval_kernel served the transformations (launch_bspline_backward_eval decides tile by tile and
+// launches once per run of tiles with the same answer): out[0] = kernel launches that read the output abscissae from the window staged
+// with the table words, out[1] = launches of the instance that gathers them, since the last reset.  Host counters only.
+extern "C" int bms_ctx_get_backward_stats(bms_ctx* c, int64_t* out /*[2]*/, int reset) try {
+  if (!c || !out) return BMS_ERR_INVALID;
+  for (int k = 0; k < 2; ++k) out[k] = (int64_t)c->bwd_launches[k];
+  if (reset) c->bwd_launches[0] = c->bwd_launches[1] = 0;
+  return BMS_OK;
+} BMS_CATCH(c)
+
 // Stream-ordered return (option ASYNC_RETURN): out[0] = transformations that returned without a host-side wait since the last reset,
 // out[1] = 1 while such a call may still be running (nothing has waited for the context's stream since).  Host counters only.
 extern "C" int bms_ctx_get_async_stats(bms_ctx* c, int64_t* out /*[2]*/, int reset) try {

@@ -698,7 +698,8 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
   }
 
   // ---------------------------------------------------------------- chunk loop over output samples
-  const BsplineSpread spread = skew_spread(T, cA, cB, in->t);
+  BsplineSpread spread = skew_spread(T, cA, cB, in->t);
+  spread.launches = c->bwd_launches;
   // bytes per output row ~ (Y + R + G [+ Yaux]) * ldg * 8
   const double bytes_per_row = (4.0 + (psi ? 1.0 : 0.0)) * ldg * 8.0;  // Y, R, G, F (+ Yaux)
   ChunkPlan plan;

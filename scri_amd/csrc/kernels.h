@@ -299,6 +299,7 @@ hipError_t launch_negated_row(hipStream_t stream, const double* off, double* row
 struct BsplineSpread {
   double skew_rate_range, skew_offset_range;
   const double* x;
+  unsigned long long* launches = nullptr;  // optional host counters: kernel launches [0] with the abscissa window, [1] of the gather instance
 };
 hipError_t launch_bspline_backward_eval(hipStream_t stream, const double* C, long long ld, int n_cols, long long g0,
                                         long long n_rows, long long n_knots, const double* x, const BsplineTable* table,

@@ -808,6 +808,7 @@ hipError_t launch_bspline_backward_eval(hipStream_t stream, const double* C, lon
     long long y1 = y0 + 1;
     while (y1 < n_tiles && y1 - y0 < GRID_Y_MAX && fits(y1) == w) ++y1;
     dim3 grid((n_cols + 63) / 64, (unsigned)(y1 - y0));
+    if (spread && spread->launches) ++spread->launches[w && xp != 1 && xp != 4 ? 0 : 1];
     if (xp == 1) {  // (ring rows, knots per group, deferred stores, register sets, non-temporal rows, abscissa window)
       BS_GO(8, 3, 0, 2, false, false);
     } else if (xp == 4) {

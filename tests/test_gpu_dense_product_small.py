@@ -19,7 +19,9 @@ NO_GEMM_EVAL route of the same context (back substitution on the grid) at the ba
   late tiles of n = 331 and of the shard reject their window (the steps there are several times shorter than where the skew was
   earned); at n = 70 on the graded axis with 64-row steps a search cannot tell at the edge of its staged window (with 61-row steps,
   which have no boundary blocks, every search can) and the march goes on from global memory.  A change of synthetic.time_axis, of the window's margins or of these boosts that loses one of
-  the exits fails the test instead of passing on the staged path alone."""
+  the exits fails the test instead of passing on the staged path alone.
+The comparison here stays one between two routes of the library; where the evaluating product meets a reference -- the oracle's
+from_modes restated in extended precision -- is tests/test_gpu_time_spline_edges.py (routes A3, A3', A3'')."""
 import numpy as np
 import pytest
 

@@ -265,9 +265,13 @@ def test_output_window_matches_the_transforms(ctx):
 @pytest.mark.parametrize("n", [8, 9, 10, 13, 40, 320, 321, 353, 700, 1500])
 @pytest.mark.parametrize("mesh", ["uniform", "ratio30", "alternating"])
 def test_bspline_path_on_short_and_irregular_time_axes(ctx, n, mesh):
-    """The B-spline form of the spline (elimination on the modes) against the oracle's scipy splines: series as short as
-    the form allows (8 samples: below that the slope form runs), lengths around the 320-knot tile and its 32-knot halo,
-    and irregular meshes, where the end rows of the collocation system and the decay of the tiled recurrences matter."""
+    """The B-spline form of the spline against the oracle's scipy splines: series as short as the form allows (8 samples:
+    below that the slope form runs) and irregular meshes, where the end rows of the collocation system and the decay of
+    the tiled recurrences matter.  The transformation carries a boost, so the dense route runs: the whole solve on the
+    modes by bspline_solve_modes_kernel (tiles of 48 knots, run-in 32) and the evaluation in the epilogue of
+    zgemm3m_eval_kernel with spline_straddle_eval_kernel -- not bspline_forward_modes_kernel (the 320-knot tile and its
+    32-knot halo the lengths 320, 321 and 353 were chosen for) and not bspline_backward_eval_kernel.  Those, and every
+    seam of the kernels that do run, are held to an exact reference in tests/test_gpu_time_spline_edges.py."""
     import scri_amd
     from oracle import waveform_grid_ref as grid_ref
     from oracle.containers import WM, h
