@@ -373,6 +373,28 @@ int64_t bms_polar_tile_rows(void);
  * (scri/waveform_base.py:299-367).  n_rows == 0 or n_cols == 0 writes nothing. */
 int bms_count_nonfinite(bms_ctx* ctx, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int64_t* count,
                         int64_t* first_row);
+/* The library's dense products on operands of the caller: what every boosted synthesis, the dense and phi-DFT analysis, the psi fields of
+ * AsymptoticBondiData and bms_rotate_const_D run through, callable by itself (and so testable against a reference).
+ *   form BMS_PRODUCT_COMPLEX     A, B, C complex128 interleaved, three real matrix products per complex one ("3M")
+ *        BMS_PRODUCT_COMPLEX_4M  the same operands, the plain four-product form (componentwise-accurate imaginary parts)
+ *        BMS_PRODUCT_REAL        A, B, C fp64
+ * Row-major, pitches lda / ldb / ldc in DOUBLES whatever the form.  With P = 64 complex columns and R = 8 rows (real form: P = 128
+ * columns, R = 16 rows):
+ *   read     of A: the K entries of rows 0 .. M-1 and nothing else -- not the rest of a pitch, not a row >= M;
+ *            of B: R ceil(K / R) rows x P ceil(N / P) columns.  Rows >= K and columns >= N have to EXIST and be FINITE; their values
+ *            reach no result (pad rows are multiplied by zeros, pad columns feed results nobody stores), so they need not be zero;
+ *            of col_off / col_scale (either may be NULL: no offset / scale 1): 2N doubles, per real and imaginary column (real form: N).
+ *   written  the 2N (real form: N) leading doubles of rows 0 .. M-1 of C, nothing else.
+ *   refused  BMS_ERR_INVALID: a NULL ctx, A, B or C; form outside 0 .. 2; M < 0 or N < 0; K < 1; lda < 2K, ldc < 2N, ldb < 2 P ceil(N / P)
+ *            (real form: K, N, P ceil(N / P)); A or B not 16-byte aligned, lda or ldb odd; complex forms: C not 16-byte aligned or ldc
+ *            odd (real form: C not 8-byte aligned); col_off or col_scale not 8-byte aligned; real form: an odd K.  M == 0 or N == 0
+ *            (with arguments that pass the above) is BMS_OK with nothing written.  BMS_ERR_UNSUPPORTED: N or K of 2^31, more than 2^30 tiles.
+ * Nothing is launched by a refused call. */
+enum { BMS_PRODUCT_COMPLEX = 0, BMS_PRODUCT_REAL = 1, BMS_PRODUCT_COMPLEX_4M = 2 };
+/* C[M x N] = (A[M x K] . B[K x N] - col_off) * col_scale on the library's matrix-core kernels; all operands device memory of the
+ * caller, pitches in doubles, stream-ordered on the context's stream (no host wait). */
+int bms_dense_product(bms_ctx* ctx, int form, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                      int64_t M, int64_t N, int64_t K, const void* col_off, const void* col_scale);
 /* ModesTimeSeries.grid_multiply (scri/modes_time_series.py:142-202): modes a (spin_a, l = 0..ell_max_a,
  * c16[n_times][(ell_max_a+1)^2]) and b likewise are evaluated on the (2 working_ell_max + 1)^2 equiangular grid
  * (spinsfast.salm2map), multiplied there, and the product is analysed (map2salm, spin spin_a + spin_b) into

@@ -199,6 +199,7 @@ SIGNATURES = {
                               ctypes.POINTER(ctypes.c_int32), c_vp, c_int, c_vp, c_int]),
     "bms_row_norm": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp]),
     "bms_grid_multiply": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_i64, c_int, c_int, c_vp]),
+    "bms_dense_product": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "bms_polar": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_i64]),
     "bms_polar_tile_rows": (c_i64, []),
     "bms_count_nonfinite": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),

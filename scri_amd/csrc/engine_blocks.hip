@@ -527,6 +527,40 @@ extern "C" int bms_row_norm(bms_ctx* c, const void* data, int64_t ld, int64_t n_
   return BMS_OK;
 } BMS_CATCH(c)
 
+// The plain dense products on operands of the caller (include/scri_amd.h states the contract): a thin wrapper of launch_zgemm3m /
+// launch_dgemm.  The launchers refuse misaligned operands and an odd K of the real form themselves (hipErrorInvalidValue: every internal
+// caller is covered); the entry states the same conditions first, so that the caller gets BMS_ERR_INVALID and a message, and adds what
+// only it knows -- that the pitches cover the rows.  Nothing of the context but its stream is used: the call returns stream-ordered.
+extern "C" int bms_dense_product(bms_ctx* c, int form, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                                 int64_t M, int64_t N, int64_t K, const void* col_off, const void* col_scale) try {
+  if (!c || !A || !B || !C) return BMS_ERR_INVALID;
+  if (form != BMS_PRODUCT_COMPLEX && form != BMS_PRODUCT_REAL && form != BMS_PRODUCT_COMPLEX_4M)
+    return fail(c, BMS_ERR_INVALID, "form is BMS_PRODUCT_COMPLEX, BMS_PRODUCT_REAL or BMS_PRODUCT_COMPLEX_4M, got %d", form);
+  const bool real = form == BMS_PRODUCT_REAL;
+  const int64_t per = real ? 1 : 2, panel = real ? 128 : 64, tile_rows = real ? 128 : 64;
+  if (M < 0 || N < 0 || K < 1) return fail(c, BMS_ERR_INVALID, "bad sizes (need M, N >= 0 and K >= 1)");
+  if (N > 0x7fffffff - 127 || K > 0x7fffffff - 15) return fail(c, BMS_ERR_UNSUPPORTED, "N or K beyond 2^31");
+  if (real && (K & 1)) return fail(c, BMS_ERR_INVALID, "the real product takes an even K (it loads A two k at a time), got %lld", (long long)K);
+  const int64_t n_pad = (N + panel - 1) / panel * panel;
+  if (lda < per * K || ldc < per * N || ldb < per * n_pad)
+    return fail(c, BMS_ERR_INVALID, "a pitch is shorter than its row (lda >= %lld, ldb >= %lld, ldc >= %lld doubles)", (long long)(per * K),
+                (long long)(per * n_pad), (long long)(per * N));
+  if ((((uintptr_t)A | (uintptr_t)B) & 15) || ((lda | ldb) & 1) || ((uintptr_t)C & (real ? 7 : 15)) || (!real && (ldc & 1)) ||
+      (((uintptr_t)col_off | (uintptr_t)col_scale) & 7))
+    return fail(c, BMS_ERR_INVALID, "A, B%s must be 16-byte aligned with even pitches (the kernels' 16-byte accesses)", real ? "" : ", C");
+  if (M == 0 || N == 0) return BMS_OK;
+  if ((M + tile_rows - 1) / tile_rows > (int64_t)(1 << 30) / (n_pad / panel)) return fail(c, BMS_ERR_UNSUPPORTED, "more than 2^30 tiles");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t S = c->stream;
+  if (real)
+    TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_dgemm(S, (const double*)A, lda, (const double*)B, ldb, (double*)C, ldc, M, (int)N, (int)K,
+                                                  (const double*)col_off, (const double*)col_scale));
+  else
+    TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m(S, (const double*)A, lda, (const double*)B, ldb, (double*)C, ldc, M, (int)N, (int)K,
+                                                    (const double*)col_off, (const double*)col_scale, form == BMS_PRODUCT_COMPLEX_4M));
+  return BMS_OK;
+} BMS_CATCH(c)
+
 // WaveformBase.abs / arg / arg_unwrapped (scri/waveform_base.py:520-533) of a series in host or device memory (kernels_polar.hip).  A host
 // array is uploaded whole and goes through the same launches, so both kinds of memory give the same bits.
 extern "C" int64_t bms_polar_tile_rows(void) { return POLAR_TILE_ROWS; }

@@ -198,17 +198,28 @@ hipError_t launch_phi_synthesis_mix6(hipStream_t stream, const double* const F6[
                                      double* const out6[6], long long ldo);
 
 // ---- dense fp64 GEMM on MFMA: C[M x N] = (A[M x K] * B[K x N] - col_off[N]) * col_scale[N]
-// A row-major (lda), B row-major (ldb, zero padded to a multiple of 128 columns and 16 rows), C row-major (ldc).
+// A row-major (lda), B row-major (ldb), C row-major (ldc); col_off/col_scale N entries or null.
+// Read: of A the K entries of rows 0 .. M-1 and nothing else (the kernel puts zeros for k >= K and rows >= M); of B
+// 16 ceil(K / 16) rows x 128 ceil(N / 128) columns -- rows >= K and columns >= N have to exist and be finite, they need not be zero
+// (pad rows meet the zeros of A, pad columns feed results nobody stores).  Written: the N leading doubles of rows 0 .. M-1 of C.
+// Preconditions (hipErrorInvalidValue otherwise): K >= 2 and even (A is loaded two k at a time: with an odd K the load that holds
+// A[row][K-1] would take A[row][K] along and multiply it by B's pad row); A and B 16-byte aligned with even lda and ldb, C 8-byte.
 hipError_t launch_dgemm(hipStream_t stream, const double* A, long long lda, const double* B, long long ldb, double* C,
                         long long ldc, long long M, int N, int K, const double* col_off, const double* col_scale);
 
 // ---- complex128 GEMM on MFMA with 3 real products per complex one: C = (A . B - col_off) * col_scale
-// A[M x K], B[K x N], C[M x N] complex interleaved, row-major, pitches lda/ldb/ldc in DOUBLES; B zero padded to a multiple
-// of 64 complex columns and 8 rows; col_off/col_scale per real column (2N entries) or null.  The last K chunk reads up to 7 rows of B
-// past row K - 1: the kernel zero-guards A for k >= K, so those rows need not be zero (AsymptoticBondiData keeps sigma's offset row
-// right behind the rows psi0 multiplies) -- they only have to exist.
+// A[M x K], B[K x N], C[M x N] complex interleaved, row-major, pitches lda/ldb/ldc in DOUBLES; col_off/col_scale per real column
+// (2N entries) or null.
+// Read: of A the K entries of rows 0 .. M-1 and nothing else (not the rest of a pitch, not a row >= M: the kernel puts zeros there);
+// of B 8 ceil(K / 8) rows x 64 ceil(N / 64) complex columns -- rows >= K and columns >= N have to exist and be FINITE, they need not
+// be zero: pad rows meet the zeros of A (AsymptoticBondiData keeps sigma's offset row right behind the rows psi0 multiplies, the
+// rotation hands over rows whose K entries are followed by the next l block), pad columns feed results nobody stores.
+// Written: the 2N leading doubles of rows 0 .. M-1 of C.
+// Preconditions (hipErrorInvalidValue otherwise): K >= 1; A, B and C 16-byte aligned with even lda, ldb and ldc (16-byte loads and
+// stores).  four: the 4-product form (zgemm3m_mfma_kernel<true>, the accuracy yardstick) instead of the 3-product one; the probe
+// switch SCRI_AMD_ZGEMM_4M asks for it on every call.
 hipError_t launch_zgemm3m(hipStream_t stream, const double* A, long long lda, const double* B, long long ldb, double* C,
-                          long long ldc, long long M, int N, int K, const double* col_off, const double* col_scale);
+                          long long ldc, long long M, int N, int K, const double* col_off, const double* col_scale, bool four = false);
 
 // ---- the same product with the spline evaluation in its epilogue (kernels_gemm_eval.hip): A holds B-spline coefficients of the
 // modes (both sweeps of the collocation solve done on the modes), the product is the coefficient grid, and each 64-knot tile

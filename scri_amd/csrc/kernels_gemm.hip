@@ -13,6 +13,7 @@
 // operands are staged global -> registers -> LDS with a two-deep LDS ring (one barrier per K-step); the LDS
 // pitches (A rows 18 doubles, B rows 144 doubles) make every ds_read_b64 fragment read conflict free.
 // Blocks are dealt in 8 x 8 super-tiles per XCD so that A slabs and B panels are re-used out of that XCD's L2.
+#include <cstdint>
 #include <cstdlib>
 #include "kernels.h"
 
@@ -321,8 +322,10 @@ __global__ __launch_bounds__(256, FOUR ? 2 : 3) void zgemm3m_mfma_kernel(const d
 #undef Z_STORE_LDS
 
 hipError_t launch_zgemm3m(hipStream_t stream, const double* A, long long lda, const double* B, long long ldb, double* C,
-                          long long ldc, long long M, int N, int K, const double* col_off, const double* col_scale) {
+                          long long ldc, long long M, int N, int K, const double* col_off, const double* col_scale, bool four) {
   if (M <= 0 || N <= 0) return hipSuccess;
+  // the kernel's 16-byte loads of A and B and its 16-byte stores of C (kernels.h)
+  if (K < 1 || !A || !B || !C || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) || ((lda | ldb | ldc) & 1)) return hipErrorInvalidValue;
   const int nbm = (int)((M + Z_BM - 1) / Z_BM);
   const int nbn = (N + Z_BN - 1) / Z_BN;
   // Super-tile of 64 workgroup tiles per XCD turn: 64 row tiles x 1 column tile for tall launches (every workgroup of the
@@ -334,8 +337,8 @@ hipError_t launch_zgemm3m(hipStream_t stream, const double* A, long long lda, co
   const int sr = 1 << st_rows_log2, sc = 64 >> st_rows_log2;
   const long long n_super = (long long)((nbm + sr - 1) / sr) * ((nbn + sc - 1) / sc);
   const long long grid = ((n_super + 7) / 8) * 8 * 64;
-  static const bool four = BMS_PROBE_ENV("SCRI_AMD_ZGEMM_4M") && atoi(BMS_PROBE_ENV("SCRI_AMD_ZGEMM_4M")) != 0;
-  if (four)
+  static const bool four_env = BMS_PROBE_ENV("SCRI_AMD_ZGEMM_4M") && atoi(BMS_PROBE_ENV("SCRI_AMD_ZGEMM_4M")) != 0;
+  if (four || four_env)
     hipLaunchKernelGGL(zgemm3m_mfma_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, A, lda, B, ldb, C, ldc, M, N,
                        K, nbm, nbn, st_rows_log2, col_off, col_scale);
   else
@@ -347,6 +350,8 @@ hipError_t launch_zgemm3m(hipStream_t stream, const double* A, long long lda, co
 hipError_t launch_dgemm(hipStream_t stream, const double* A, long long lda, const double* B, long long ldb, double* C,
                         long long ldc, long long M, int N, int K, const double* col_off, const double* col_scale) {
   if (M <= 0 || N <= 0) return hipSuccess;
+  // the kernel's 16-byte loads: A two k at a time (an odd K would take A[row][K] along), B two columns at a time (kernels.h)
+  if (K < 2 || (K & 1) || !A || !B || !C || (((uintptr_t)A | (uintptr_t)B) & 15) || ((uintptr_t)C & 7) || ((lda | ldb) & 1)) return hipErrorInvalidValue;
   const int nbm = (int)((M + G_BM - 1) / G_BM);
   const int nbn = (N + G_BN - 1) / G_BN;
   static const int st_rows_log2 = BMS_PROBE_ENV("SCRI_AMD_GEMM_ST_ROWS_LOG2") ? atoi(BMS_PROBE_ENV("SCRI_AMD_GEMM_ST_ROWS_LOG2")) : 5;

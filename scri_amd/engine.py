@@ -989,6 +989,19 @@ def count_nonfinite(data, ctx=None):
     return int(count.value), int(first.value)
 
 
+PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
+
+
+def dense_product(form, a_ptr, lda, b_ptr, ldb, c_ptr, ldc, M, N, K, col_off_ptr=None, col_scale_ptr=None, ctx=None):
+    """bms_dense_product: C[M x N] = (A[M x K] . B[K x N] - col_off) * col_scale on the matrix-core kernels.  Every operand is a device
+    ADDRESS (int) of the caller's, pitches in doubles; include/scri_amd.h says what is read, written and refused.  Stream-ordered on
+    the context's stream: ctx.synchronize() is the host-side wait."""
+    ctx = _ctx(ctx)
+    rc = _lib.load().bms_dense_product(ctx.handle, int(form), c_vp(a_ptr), int(lda), c_vp(b_ptr), int(ldb), c_vp(c_ptr), int(ldc), int(M),
+                                       int(N), int(K), c_vp(col_off_ptr), c_vp(col_scale_ptr))
+    ctx.check(rc, "bms_dense_product")
+
+
 def _modes_arg(data, n, ell_min, ell_max):
     """(address, row stride, memory kind, object to keep alive) of modes [n, n_modes]: a numpy array on the host, or a torch tensor
     (complex128, unit column stride) for modes resident on the GPU"""

@@ -10,7 +10,9 @@ NO_GEMM_EVAL route of the same context (back substitution on the grid) at the ba
   read of the input past the shard's first or last row (the solve's run-in, the staging of the product's A operand) meets a NaN.
   The product itself reads A from the engine's own buffer of solved coefficients, so these tests see a descriptor that ends too
   EARLY (rows or k-steps read as zero: wrong values) or a wrong turn offset, not one that reaches a few rows too far -- that its
-  bounds are exactly the rows and k-steps of the tile is established by reading the kernel, not here;
+  bounds are exactly the rows and k-steps of the tile is established by reading the kernel, not here.  (That holds for the EVALUATING
+  product only.  The plain products, zgemm3m_mfma_kernel and dgemm_mfma_kernel, are held to exactly that -- A between NaNs, garbage in
+  B's padding, sentinels around C, a reference on operands the test owns -- by tests/test_gpu_dense_product_edges.py);
 * the uniform, the jittered and the graded time axis (synthetic.time_axis) at a mild boost and at 40 times that boost (two samples in
   some intervals, none in others): the search's first guess accepted, one off, the nine steps, and tiles whose samples leave the
   window of output times staged in LDS.  ctx.eval_stats() = (tiles and boundary blocks launched, of those: the ones whose samples do

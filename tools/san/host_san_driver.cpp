@@ -3,7 +3,7 @@
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
 // pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain, of the rotor interpolation and of the alignment entries, the planner and the per-step
-// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -561,6 +561,64 @@ void com_motion_arguments() {
   REQUIRE(com_fit_work_doubles(2 * COM_FIT_TILE + 3) == com_fit_work_doubles(3) + 18);  // one more tile of double-double partials
 }
 
+// bms_dense_product (engine_blocks.hip) and the two launchers behind it (kernels_gemm.hip): every refusal of include/scri_amd.h comes
+// back before a device is touched or anything is launched, and an empty product is BMS_OK.  The arrays are never read.
+void dense_product_arguments() {
+  bms_ctx dummy;
+  alignas(16) static double a[64], b[64], c[64], off[8];
+  const int64_t M = 5, N = 70, K = 18;  // pitches of the complex forms: lda >= 36, ldb >= 256, ldc >= 140; real form: 18, 128, 70
+  auto call = [&](int form, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t m, int64_t n, int64_t k,
+                  const void* o = nullptr, const void* s = nullptr) { return bms_dense_product(&dummy, form, A, lda, B, ldb, C, ldc, m, n, k, o, s); };
+  REQUIRE(bms_dense_product(nullptr, BMS_PRODUCT_COMPLEX, a, 36, b, 256, c, 140, M, N, K, nullptr, nullptr) == BMS_ERR_INVALID);
+  for (int form : {BMS_PRODUCT_COMPLEX, BMS_PRODUCT_REAL, BMS_PRODUCT_COMPLEX_4M}) {
+    const bool real = form == BMS_PRODUCT_REAL;
+    const int64_t lda = real ? 18 : 36, ldb = real ? 128 : 256, ldc = real ? 70 : 140;
+    REQUIRE(call(form, nullptr, lda, b, ldb, c, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, nullptr, ldb, c, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, nullptr, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, -1, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, -1, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, N, 0) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda - 2, b, ldb, c, ldc, M, N, K) == BMS_ERR_INVALID && std::strstr(bms_last_error(&dummy), "pitch") != nullptr);
+    REQUIRE(call(form, a, lda, b, ldb - 2, c, ldc, M, N, K) == BMS_ERR_INVALID);  // below the PADDED width
+    REQUIRE(call(form, a, lda, b, ldc, c, ldc, M, N, K) == BMS_ERR_INVALID);      // the unpadded width
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc - 2, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a + 1, lda, b, ldb, c, ldc, M, N, K) == BMS_ERR_INVALID && std::strstr(bms_last_error(&dummy), "aligned") != nullptr);
+    REQUIRE(call(form, a, lda, b + 1, ldb, c, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda + 1, b, ldb, c, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb + 1, c, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, (char*)c + 4, ldc, M, N, K) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, N, K, (char*)off + 4, nullptr) == BMS_ERR_INVALID);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, N, K, nullptr, (char*)off + 4) == BMS_ERR_INVALID);
+    if (real) {
+      REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, N, K - 1) == BMS_ERR_INVALID && std::strstr(bms_last_error(&dummy), "even K") != nullptr);
+    } else {
+      REQUIRE(call(form, a, lda, b, ldb, c + 1, ldc, M, N, K) == BMS_ERR_INVALID);
+      REQUIRE(call(form, a, lda, b, ldb, c, ldc + 1, M, N, K) == BMS_ERR_INVALID);
+    }
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, (int64_t)1 << 31, K) == BMS_ERR_UNSUPPORTED);
+    REQUIRE(call(form, a, (int64_t)1 << 33, b, ldb, c, ldc, M, N, (int64_t)1 << 31) == BMS_ERR_UNSUPPORTED);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, (int64_t)1 << 40, N, K) == BMS_ERR_UNSUPPORTED);  // more tiles than a grid holds
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, 0, N, K) == BMS_OK);
+    REQUIRE(call(form, a, lda, b, ldb, c, ldc, M, 0, K) == BMS_OK);
+  }
+  for (int form : {-1, 3}) REQUIRE(call(form, a, 36, b, 256, c, 140, M, N, K) == BMS_ERR_INVALID && std::strstr(bms_last_error(&dummy), "form") != nullptr);
+  // the launchers' own preconditions (kernels.h): what every internal caller is held to
+  REQUIRE(launch_dgemm(nullptr, a, 18, b, 128, c, 70, M, 70, 17, nullptr, nullptr) == hipErrorInvalidValue);  // odd K
+  REQUIRE(launch_dgemm(nullptr, a, 18, b, 128, c, 70, M, 70, 0, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_dgemm(nullptr, a + 1, 18, b, 128, c, 70, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_dgemm(nullptr, a, 19, b, 128, c, 70, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_dgemm(nullptr, a, 18, b, 129, c, 70, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_dgemm(nullptr, a, 18, b, 128, c, 70, 0, 70, 17, nullptr, nullptr) == hipSuccess);  // nothing to do
+  REQUIRE(launch_zgemm3m(nullptr, a, 36, b, 256, c, 140, M, 70, 0, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_zgemm3m(nullptr, a + 1, 36, b, 256, c, 140, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_zgemm3m(nullptr, a, 36, b + 1, 256, c, 140, M, 70, 18, nullptr, nullptr, true) == hipErrorInvalidValue);
+  REQUIRE(launch_zgemm3m(nullptr, a, 36, b, 256, c + 1, 140, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_zgemm3m(nullptr, a, 37, b, 256, c, 140, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_zgemm3m(nullptr, a, 36, b, 256, c, 141, M, 70, 18, nullptr, nullptr) == hipErrorInvalidValue);
+  REQUIRE(launch_zgemm3m(nullptr, a, 36, b, 256, c, 140, M, 0, 18, nullptr, nullptr) == hipSuccess);
+}
+
 }  // namespace
 
 int main() {
@@ -582,6 +640,7 @@ int main() {
   sample_waveform_plan();
   paired_xor_arguments();
   com_motion_arguments();
+  dense_product_arguments();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
