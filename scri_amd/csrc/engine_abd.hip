@@ -292,7 +292,7 @@ static int transform_abd_impl(bms_ctx* c, const double* u, const void* raw, int 
                                                              n_pix, nm - skip + 1, DP.col_scale + 2 * cA, ev));
       } else if (bsg) {
         TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, Rf, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO,
-                                                                       kt.d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG, &spread));
+                                                                       kt.d_x, d_skewa, d_skewb, T.tt, c0, c1_, Gf, ldG, c->n_cu, &spread));
       } else {
         TIMED(c, BMS_TAG_SPLINE_FORWARD,
               launch_spline_forward(S, grids.y[f], Rf, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO));

@@ -157,6 +157,7 @@ extern "C" int bms_ctx_create(int device, bms_ctx** out) try {
   if (e != hipSuccess) return fail(nullptr, BMS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
   bms_ctx* c = new bms_ctx;
   c->device = device;
+  c->n_cu = prop.multiProcessorCount;
   e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete c;

@@ -744,7 +744,7 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
       TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m(S, d_Af + (g0 - row0) * ld_af, ld_af, F[0].d_B + 2 * cA, ldb, d_Y, ldg, rows_in, n_pix,
                                                       n_modes_in + 1, nullptr, d_scale));
       TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_Y, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO, kt.d_x, d_skewa,
-                                                                     d_skewb, T.tt, c0, c1, d_G, ldG, &spread));
+                                                                     d_skewb, T.tt, c0, c1, d_G, ldG, c->n_cu, &spread));
     } else {
     if (psi)
       if ((rc = dev_buf_t(c, "Yaux", (size_t)rows_in * ldg, &d_Yaux))) return rc;
@@ -771,11 +771,11 @@ static int transform_modes_impl(bms_ctx* c, const bms_wm_input* in, const bms_tr
     // spline along time on the shared knots, evaluated on the distorted slices
     if (bsg && sep_fields && psi && no_boost) {  // (eliminated on the modes above: d_Y holds coefficients already)
       TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_Y, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO, kt.d_x, d_skewa,
-                                                                     d_skewb, T.tt, c0, c1, d_G, ldG, &spread));
+                                                                     d_skewb, T.tt, c0, c1, d_G, ldG, c->n_cu, &spread));
     } else if (bsg) {  // mixing is time dependent: eliminate on the grid, then the coefficient-only back substitution
       TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_bspline_forward_modes(S, d_Y, ldg, n_pix, d_R, ldg, g0, rows_in, n, kt.d_bsfwd, SPLINE_TILE, SPLINE_HALO, 0));
       TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_bspline_backward_eval(S, d_R, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_bstab, SPLINE_TILE, SPLINE_HALO, kt.d_x, d_skewa,
-                                                                     d_skewb, T.tt, c0, c1, d_G, ldG, &spread));
+                                                                     d_skewb, T.tt, c0, c1, d_G, ldG, c->n_cu, &spread));
     } else {
     TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_Y, d_R, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO));
     TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_backward_eval(S, d_Y, d_R, ldg, n_pix, g0, rows_in, n, kt.d_x, kt.d_tab, plan.spline_tile, SPLINE_HALO,

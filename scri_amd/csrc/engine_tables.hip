@@ -172,11 +172,6 @@ int ensure_delta_resident(bms_ctx* c, int ell_min, int ell_max, bool* ok, RotRes
   snprintf(name, sizeof name, "rot_res_tab_%d_%d", ell_min, ell_max);
   int rc = dev_buf_t(c, "rot_res_counter", 4, d_counter);
   if (rc) return rc;
-  if (!c->n_cu) {
-    hipDeviceProp_t prop;
-    HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
-    c->n_cu = prop.multiProcessorCount;
-  }
   double* dt = nullptr;
   if ((rc = dev_buf_t(c, name, (size_t)P->tab_doubles, &dt))) return rc;
   *d_tab = dt;
@@ -427,7 +422,7 @@ int run_analysis(bms_ctx* c, const AnalysisPlan& A, const double* d_G, long long
   const long long P2 = 2LL * A.n_pix, ld = ld_cols ? ld_cols : P2;  // row stride of d_G
   if (A.fused) {
     TIMED(c, BMS_TAG_ANALYSIS_FUSED, launch_analysis_fused(S, d_G, ld, rows, A.n_theta, A.n_phi, A.L, A.n_out,
-                                                           A.d_mindex, A.d_T, A.d_dcs, d_out, ldo, col_of_pixel, A.spin, !c->opt.on(OPT_NO_SPLIT_ANALYSIS)));
+                                                           A.d_mindex, A.d_T, A.d_dcs, d_out, ldo, col_of_pixel, A.spin, c->n_cu, !c->opt.on(OPT_NO_SPLIT_ANALYSIS)));
   } else if (A.large) {
     if (col_of_pixel) return fail(c, BMS_ERR_UNSUPPORTED, "internal: sorted columns need the fused analysis");
     double* d_F;
@@ -784,11 +779,6 @@ int build_synthesis(bms_ctx* c, int n_theta, int n_phi, int spin, int ell_min, i
     }
   }
   P = SynthesisPlan();
-  if (!c->n_cu) {
-    hipDeviceProp_t prop;
-    HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
-    c->n_cu = prop.multiProcessorCount;
-  }
   std::vector<int> meta;
   int len = 0;
   if (c->opt.on(OPT_NO_SEPARABLE_SYNTHESIS) || !synthesis_split_plan(n_theta, n_phi, ell_min, ell_max, P.g, meta, P.lds, P.nt, len)) P.nt = 0;

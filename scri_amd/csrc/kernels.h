@@ -144,7 +144,7 @@ hipError_t launch_dft_cs_matrix(hipStream_t stream, int n_phi, int L, double* D)
 // rings are read from their ring's column times the spin phase e^{-+ i spin phi_k}
 hipError_t launch_analysis_fused(hipStream_t stream, const double* G, long long ldg, long long n_rows, int n_theta, int n_phi,
                                  int L, int n_out, const int* m_index, const double* T, const double* D, double* out,
-                                 long long ldo, const int* col_of_pixel, int spin, bool allow_split = true);
+                                 long long ldo, const int* col_of_pixel, int spin, int n_cu, bool allow_split = true);
 
 // series of 2 or 3 samples (ABD flavour): line / parabola through the samples, rows 0..n-1 of Y
 hipError_t launch_short_series_eval(hipStream_t stream, const double* Y, long long ld, int n_cols, int n, const double* x,
@@ -315,7 +315,8 @@ struct BsplineSpread {
 hipError_t launch_bspline_backward_eval(hipStream_t stream, const double* C, long long ld, int n_cols, long long g0,
                                         long long n_rows, long long n_knots, const double* x, const BsplineTable* table,
                                         int tile, int halo, const double* base, const double* skew_a, const double* skew_b,
-                                        double tt, long long i_lo, long long i_hi, double* out, long long ldo, const BsplineSpread* spread = nullptr);
+                                        double tt, long long i_lo, long long i_hi, double* out, long long ldo, int n_cu,
+                                        const BsplineSpread* spread = nullptr);
 
 // ---- time-series calculus and grid products (kernels_series.hip; scri/modes_time_series.py:72-202)
 // spline slopes s_j at all knots from the forward-pass result R (S != R)

@@ -3,15 +3,118 @@
 //
 // The Huffenberger-Wandelt analysis collapses exactly (oracle/spinsfast_ref.py, tests/test_oracle_wigner.py) to
 //     a_lm = sum_j [q_j / n_phi] sLambda_lm(theta_j) F_m(theta_j),      F_m(theta_j) = sum_k f_jk exp(-i m phi_k)
-// with real theta-quadrature weights q_j.  Step 1 (phi-DFT) is a thin real GEMM [rows n_theta x 2 n_phi] . [2 n_phi x
-// 2 (2L+1)] against the matrix built by dft_matrix_kernel (run through dgemm_mfma_kernel); step 2 is
-// theta_quadrature_kernel below.  Compared with the dense quadrature GEMM this is ~10x less arithmetic and sums
-// n_phi and n_theta terms per output instead of 2 n_pix (shorter fp64 chains => smaller rounding error).
+// with real theta-quadrature weights q_j: a phi transform per ring (step 1), then a theta quadrature per mode (step 2).
+// Compared with the dense quadrature GEMM this is ~10x less arithmetic and sums n_phi and n_theta terms per output
+// instead of 2 n_pix (shorter fp64 chains => smaller rounding error).
+//
+// Four routes through this file, in the order build_analysis (engine_tables.hip) tries them; nk = n_phi / 2 + 1:
+//   two-role kernel    launch_analysis_fused -> analysis_split_kernel: 3 <= n_theta <= 40, nk <= 20, L <= 16, at most 6 front
+//                      and 10 waves, two rows or more (split_analysis_supported).  One kernel, the grid row never leaves the
+//                      chip; products and quadrature on different waves.  Grids in natural or gathered column order.
+//   one-role kernel    launch_analysis_fused -> analysis_fused[_wide]_kernel: what the two-role kernel refuses of n_theta <=
+//                      40, nk <= 24, L <= 32 (wide: L > 16), n_out <= 512 (fused_analysis_supported).
+//   two-kernel route   launch_analysis_large -> phi_dft_folded_kernel, theta_quadrature_mfma_kernel: n_theta <= 104, nk <=
+//                      64, L <= 32 (large_analysis_supported), F[t][m][ring] in HBM between the two.  Natural order only.
+//   older pair         launch_dft_matrix once, then per call a thin real GEMM [rows n_theta x 2 n_phi] . [2 n_phi x 2 (2L+1)]
+//                      (dgemm_mfma_kernel) and launch_theta_quadrature -> theta_quadrature_kernel: every other n_theta <= 104.
+// (Beyond n_theta = 104 the engine runs the dense quadrature GEMM; nothing of that is here.)
+// The first three fold the ring about phi = 0 and share the pieces under "Shared device pieces" below.
 #include "wigner.h"
 #include <cstdlib>
+#include <type_traits>
 #include "kernels.h"
 
 namespace bms {
+
+typedef double v4d_t __attribute__((ext_vector_type(4)));
+template <int N>
+using int_c = std::integral_constant<int, N>;  // a template argument handed to a generic lambda (the with_* functions below)
+
+// k-steps of four along a ring folded about phi = 0 (k = 0 .. n_phi / 2)
+static int folded_k_steps(int n_phi) { return (n_phi / 2 + 1 + 3) / 4; }
+
+// a launch with dynamic LDS beyond the default limit
+template <class K, class... Args>
+static hipError_t launch_with_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+  hipError_t e = allow_dynamic_lds((const void*)kernel);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  return hipGetLastError();
+}
+
+// ---- Shared device pieces.  Each keeps the order of operations of the kernels it was written out in: results to the bit.
+
+// (sin, cos)(2 pi r / n_phi).  r is the CALLER's integer reduction of m k: only dft_matrix_kernel meets negative
+// remainders (and lifts them by n_phi).
+__device__ __forceinline__ void twiddle(double r, int n_phi, double* sn, double* co) {
+  sincospi(2.0 * r / (double)n_phi, sn, co);
+}
+
+// sample k's partner under the fold, x_{n_phi - k} (k = 0 and the Nyquist sample of an even ring are their own)
+__device__ __forceinline__ int fold_partner(int k, int n_phi) { return k == 0 ? 0 : n_phi - k; }
+
+// C = E . cos and S = O . sin, KS k-steps of four, NTC column tiles of 16 (m = 16 n + fi + 1): the lane's A operands are ea[4 s]
+// and oa[4 s] in LDS, its B fragments bc[s SS + n SN] and bs[..] -- LDS in the one-role kernel, registers in phi_dft_folded_kernel.
+// (Returned by value: with the accumulators as reference arguments two instances of the one-role kernel got other registers.)
+template <int NTC>
+struct FoldedAcc {
+  v4d_t c[NTC], s[NTC];
+};
+template <int KS, int NTC, int SS, int SN>
+__device__ __forceinline__ FoldedAcc<NTC> folded_products(const double* ea, const double* oa, const double* bc, const double* bs) {
+  FoldedAcc<NTC> a;
+#pragma unroll
+  for (int n = 0; n < NTC; ++n) a.c[n] = a.s[n] = v4d_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const double ae = ea[4 * s], ao = oa[4 * s];
+#pragma unroll
+    for (int n = 0; n < NTC; ++n) {
+      a.c[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ae, bc[s * SS + n * SN], a.c[n], 0, 0, 0);
+      a.s[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ao, bs[s * SS + n * SN], a.s[n], 0, 0, 0);
+    }
+  }
+  return a;
+}
+
+// m = 0: the plain sum of one folded operand row (two partial sums, even and odd k)
+template <int KS>
+__device__ __forceinline__ double folded_row_sum(const double* rp) {
+  double c0 = 0.0, c1 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4 * KS; k += 2) {
+    c0 += rp[k];
+    c1 += rp[k + 1];
+  }
+  return c0 + c1;
+}
+
+// both signs of m from the cos and sin products:  F_{+-m} = (C_re +- S_im) + i (C_im -+ S_re)
+struct PlusMinus {
+  double2 plus, minus;
+};
+__device__ __forceinline__ PlusMinus recombine(double cre, double cim, double sre, double sim) {
+  return {double2{cre + sim, cim - sre}, double2{cre - sim, cim + sre}};
+}
+
+// one output mode of the VALU theta quadrature: sum_j t[j] f[j] over NT rings (NT even), F_m(theta_j) read as 16-byte
+// (re, im) pairs, even and odd rings in chains of their own that are added at the end.  t: the T row in registers or in
+// LDS.  Rings beyond n_theta carry zero weights and zero F: no bounds tests.
+template <int NT, class TRow>
+__device__ __forceinline__ double2 quadrature_row(const TRow& t, const double2* f) {
+  double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
+#pragma unroll
+  for (int j = 0; j + 1 < NT; j += 2) {
+    const double2 f0 = f[j], f1 = f[j + 1];
+    ar = fma(t[j], f0.x, ar);
+    ai = fma(t[j], f0.y, ai);
+    br = fma(t[j + 1], f1.x, br);
+    bi = fma(t[j + 1], f1.y, bi);
+  }
+  return double2{ar + br, ai + bi};
+}
+
+// ---- The older pair: phi-DFT matrix for the GEMM, theta table (every route's), VALU theta quadrature
 
 // B[2k][2mi] = cos(m phi_k), B[2k][2mi+1] = -sin(m phi_k), B[2k+1][2mi] = sin(m phi_k), B[2k+1][2mi+1] = cos(m phi_k);
 // mi = m + L, phi_k = 2 pi k / n_phi; the angle is reduced in integers before the sincos.
@@ -23,7 +126,7 @@ __global__ __launch_bounds__(256) void dft_matrix_kernel(int n_phi, int L, doubl
   long long r = ((long long)m * k) % n_phi;
   if (r < 0) r += n_phi;
   double s, c;
-  sincospi(2.0 * (double)r / (double)n_phi, &s, &c);
+  twiddle((double)r, n_phi, &s, &c);
   double* r0 = B + (2LL * k) * ldb + 2 * mi;
   double* r1 = r0 + ldb;
   r0[0] = c;
@@ -78,6 +181,8 @@ __global__ __launch_bounds__(MAXT) void theta_quadrature_kernel(const double* __
     for (int e = threadIdx.x * 2; e < tile; e += blockDim.x * 2)
       *reinterpret_cast<double2*>(Fs + e) = *reinterpret_cast<const double2*>(src + e);
     __syncthreads();
+    // (quadrature_row's chains written out: through the shared function this kernel, which sits at its register limit, is
+    // scheduled differently -- <40, 1024> then spills 8 registers instead of 6)
     double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
 #pragma unroll
     for (int j = 0; j + 1 < NT; j += 2) {
@@ -92,38 +197,30 @@ __global__ __launch_bounds__(MAXT) void theta_quadrature_kernel(const double* __
   }
 }
 
+// which theta_quadrature_kernel<NT, MAXT>: the T row lives in registers, NT doubles per thread, so larger grids get
+// smaller workgroups
+template <class Go>
+static hipError_t with_tq_instance(int n_theta, Go go) {
+  if (n_theta <= 24) return go(int_c<24>{}, int_c<1024>{});
+  if (n_theta <= 40) return go(int_c<40>{}, int_c<1024>{});
+  if (n_theta <= 72) return go(int_c<72>{}, int_c<512>{});
+  if (n_theta <= 104) return go(int_c<104>{}, int_c<256>{});
+  return hipErrorInvalidValue;
+}
+
 hipError_t launch_theta_quadrature(hipStream_t stream, const double* F, long long n_rows, int n_theta, int nm, int n_out,
                                    const int* m_index, const double* T, double* out, long long ldo) {
   if (n_rows <= 0 || n_out <= 0) return hipSuccess;
-  const int nt_pad = n_theta <= 24 ? 24 : n_theta <= 40 ? 40 : n_theta <= 72 ? 72 : 104;
-  const size_t lds = sizeof(double) * (size_t)nt_pad * 2 * nm;
   const long long by = n_rows < 2048 ? n_rows : 2048;
-  // the T row lives in registers: NT doubles per thread, so larger grids get smaller workgroups
-#define LAUNCH_TQ(NT, MAXT)                                                                                              \
-  {                                                                                                                      \
-    int threads = ((n_out + 63) / 64) * 64;                                                                              \
-    if (threads > MAXT) threads = MAXT;                                                                                  \
-    const int bx = (n_out + threads - 1) / threads;                                                                      \
-    hipError_t e = allow_dynamic_lds((const void*)theta_quadrature_kernel<NT, MAXT>);                            \
-    if (e != hipSuccess) return e;                                                                                       \
-    hipLaunchKernelGGL((theta_quadrature_kernel<NT, MAXT>), dim3(bx, (unsigned)by), dim3(threads), lds, stream, F, n_rows,  \
-                       n_theta, nm, n_out, m_index, T, out, ldo);                                                        \
-  }
-  if (n_theta <= 24)
-    LAUNCH_TQ(24, 1024)
-  else if (n_theta <= 40)
-    LAUNCH_TQ(40, 1024)
-  else if (n_theta <= 72)
-    LAUNCH_TQ(72, 512)
-  else if (n_theta <= 104)
-    LAUNCH_TQ(104, 256)
-  else
-    return hipErrorInvalidValue;
-#undef LAUNCH_TQ
-  return hipGetLastError();
+  return with_tq_instance(n_theta, [&](auto NT, auto MAXT) {
+    const size_t lds = sizeof(double) * (size_t)NT.value * 2 * nm;
+    int threads = ((n_out + 63) / 64) * 64;
+    if (threads > MAXT.value) threads = MAXT.value;
+    const int bx = (n_out + threads - 1) / threads;
+    return launch_with_lds(theta_quadrature_kernel<NT.value, MAXT.value>, dim3(bx, (unsigned)by), dim3(threads), lds, stream, F, n_rows,
+                           n_theta, nm, n_out, m_index, T, out, ldo);
+  });
 }
-
-
 
 // =====================================================================================================================
 // Fused analysis: one workgroup per time step, the grid row never leaves the chip between the two steps.
@@ -141,8 +238,6 @@ hipError_t launch_theta_quadrature(hipStream_t stream, const double* F, long lon
 //                   16-byte (re, im) pairs.
 // HBM traffic = the algorithmic minimum: read the grid row once (16 n_pix B), write the modes once (16 n_out B).
 // =====================================================================================================================
-typedef double v4d_t __attribute__((ext_vector_type(4)));
-
 constexpr int F_PA = 26;    // LDS pitch (doubles) of the folded operand rows: 2 x odd >= 24 -> conflict-free fragment reads
 constexpr int F_KSMAX = 6;  // k-steps of 4 along the folded ring: n_phi / 2 + 1 <= 24 (kernels are built for 3, 5 and 6)
 constexpr int F_EPT_MAX = 4;  // (ring, sample pair) items per thread: n_theta (n_phi/2 + 1) <= 40 x 21 <= 4 x 256 threads (kernels for 2, 3, 4)
@@ -166,7 +261,7 @@ __global__ __launch_bounds__(256) void dft_cs_matrix_kernel(int n_phi, int L, in
   const int k = id / L, c = id % L;
   const long long r = ((long long)(c + 1) * k) % n_phi;
   double sn, co;
-  sincospi(2.0 * (double)r / (double)n_phi, &sn, &co);
+  twiddle((double)r, n_phi, &sn, &co);
   D[(long long)k * pd + c] = co;
   D[(long long)(4 * ks + k) * pd + c] = sn;
 }
@@ -232,7 +327,7 @@ __device__ __forceinline__ void analysis_fused_body(const double* __restrict__ G
     const int e = tid + q * nthreads;
     const bool ok = e < g.n_theta * g.nk;
     const int j = ok ? e / g.nk : 0, kk = ok ? e - j * g.nk : 0;
-    const int k2 = kk == 0 ? 0 : g.n_phi - kk;
+    const int k2 = fold_partner(kk, g.n_phi);
     slot[q] = ok ? fused_row(j) * F_PA + kk : -1;
     const int g1 = j * g.n_phi + kk, g2 = j * g.n_phi + k2;
     off1[q] = 2 * (col_of_pixel ? col_of_pixel[g1] : g1);
@@ -241,6 +336,8 @@ __device__ __forceinline__ void analysis_fused_body(const double* __restrict__ G
     // a pole ring is stored as its pixel k = 0: pixel k is that value times e^{-i s phi_k} (north) / e^{+i s phi_k} (south)
     if (col_of_pixel && ok && (j == 0 || j == g.n_theta - 1)) {
       const double sg = j == 0 ? -1.0 : 1.0;
+      // (not twiddle(): the remainders keep the sign of spin, and through twiddle() every one-role kernel took three
+      // scalar registers more)
       const double a1 = sg * (double)((g.spin * kk) % g.n_phi) / (double)g.n_phi;
       const double a2 = sg * (double)((g.spin * k2) % g.n_phi) / (double)g.n_phi;
       double2 fa, fb;
@@ -293,29 +390,11 @@ __device__ __forceinline__ void analysis_fused_body(const double* __restrict__ G
       const double* op = Os + (tm * 16 + fi) * F_PA + fk;
       const double* cp = Dc + fk * PD + fi;
       const double* sp = Dn + fk * PD + fi;
-      v4d_t ac[NTC], as[NTC];
-#pragma unroll
-      for (int n = 0; n < NTC; ++n) ac[n] = as[n] = v4d_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const double ae = ep[4 * s], ao = op[4 * s];
-#pragma unroll
-        for (int n = 0; n < NTC; ++n) {
-          ac[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ae, cp[4 * s * PD + 16 * n], ac[n], 0, 0, 0);
-          as[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ao, sp[4 * s * PD + 16 * n], as[n], 0, 0, 0);
-        }
-      }
+      const FoldedAcc<NTC> acc = folded_products<KS, NTC, 4 * PD, 16>(ep, op, cp, sp);
       // m = 0: plain sums of the folded rows (16 lanes, one operand row each)
       if (fk == 0) {
-        const double* rp = Es + (tm * 16 + fi) * F_PA;
-        double c0 = 0.0, c1 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4 * KS; k += 2) {
-          c0 += rp[k];
-          c1 += rp[k + 1];
-        }
         const int ring = tm * 8 + (fi & 3) + 4 * (fi >> 3), part = (fi >> 2) & 1;
-        reinterpret_cast<double*>(Fs + g.L * PJ + ring)[part] = c0 + c1;
+        reinterpret_cast<double*>(Fs + g.L * PJ + ring)[part] = folded_row_sum<KS>(Es + (tm * 16 + fi) * F_PA);
       }
       // both signs of m from registers: results r = 2h (re), 2h+1 (im) of ring 8 tm + fk + 4h, column m = 16 n + fi + 1
 #pragma unroll
@@ -325,41 +404,17 @@ __device__ __forceinline__ void analysis_fused_body(const double* __restrict__ G
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int ring = tm * 8 + fk + 4 * h;
-            const double cre = ac[n][2 * h], cim = ac[n][2 * h + 1], sre = as[n][2 * h], sim = as[n][2 * h + 1];
-            Fs[(g.L + m) * PJ + ring] = double2{cre + sim, cim - sre};
-            Fs[(g.L - m) * PJ + ring] = double2{cre - sim, cim + sre};
+            const PlusMinus f = recombine(acc.c[n][2 * h], acc.c[n][2 * h + 1], acc.s[n][2 * h], acc.s[n][2 * h + 1]);
+            Fs[(g.L + m) * PJ + ring] = f.plus;
+            Fs[(g.L - m) * PJ + ring] = f.minus;
           }
         }
       }
     }
     __syncthreads();  // F complete
-    // ---- step 2: theta quadrature
-    if (live) {
-      // rings beyond n_theta carry zero weights and zero F: no bounds tests
-      double pr0 = 0.0, pi0 = 0.0, pr1 = 0.0, pi1 = 0.0;
-#pragma unroll
-      for (int j = 0; j + 1 < NT; j += 2) {
-        const double2 v0 = fp[j], v1 = fp[j + 1];
-        pr0 = fma(tj[j], v0.x, pr0);
-        pi0 = fma(tj[j], v0.y, pi0);
-        pr1 = fma(tj[j + 1], v1.x, pr1);
-        pi1 = fma(tj[j + 1], v1.y, pi1);
-      }
-      *reinterpret_cast<double2*>(out + t * ldo + 2LL * o) = double2{pr0 + pr1, pi0 + pi1};
-    }
-    if (sec) {
-      double pr0 = 0.0, pi0 = 0.0, pr1 = 0.0, pi1 = 0.0;
-#pragma unroll
-      for (int j = 0; j + 1 < NT; j += 2) {
-        const double2 v0 = fp2[j], v1 = fp2[j + 1];
-        const double w0 = t2[j], w1 = t2[j + 1];
-        pr0 = fma(w0, v0.x, pr0);
-        pi0 = fma(w0, v0.y, pi0);
-        pr1 = fma(w1, v1.x, pr1);
-        pi1 = fma(w1, v1.y, pi1);
-      }
-      *reinterpret_cast<double2*>(out + t * ldo + 2LL * o2) = double2{pr0 + pr1, pi0 + pi1};
-    }
+    // ---- step 2: theta quadrature (the second mode with its T row in LDS)
+    if (live) *reinterpret_cast<double2*>(out + t * ldo + 2LL * o) = quadrature_row<NT>(tj, fp);
+    if (sec) *reinterpret_cast<double2*>(out + t * ldo + 2LL * o2) = quadrature_row<NT>(t2, fp2);
   };
   long long t = blockIdx.x;
   if (t < n_rows) fetch(t, pa0, pb0);
@@ -393,7 +448,7 @@ __global__ __launch_bounds__(512) void analysis_fused_wide_kernel(
 }
 
 static int fused_ks(int n_phi) {
-  const int ks = (n_phi / 2 + 1 + 3) / 4;
+  const int ks = folded_k_steps(n_phi);
   return ks <= 3 ? 3 : ks <= 5 ? 5 : 6;
 }
 
@@ -504,7 +559,7 @@ __global__ __launch_bounds__(640, 1) void analysis_split_kernel(
     for (int s = 0; s < KS; ++s) {
       const int k = 4 * s + fk;
       const bool ok = okr && k < g.nk;
-      const int k2 = k == 0 ? 0 : g.n_phi - k;
+      const int k2 = fold_partner(k, g.n_phi);
       const int g1 = ok ? j * g.n_phi + k : 0, g2 = ok ? j * g.n_phi + k2 : 0;
       offa[s] = 8 * (2 * (col_of_pixel ? col_of_pixel[g1] : g1) + r * (int)ldg);  // bytes from the pair's first row
       offb[s] = 8 * (2 * (col_of_pixel ? col_of_pixel[g2] : g2) + r * (int)ldg);
@@ -514,7 +569,7 @@ __global__ __launch_bounds__(640, 1) void analysis_split_kernel(
       const int m = fi + 1;
       const long long rr = ((long long)m * k) % g.n_phi;
       double sv, cv;
-      sincospi(2.0 * (double)rr / (double)g.n_phi, &sv, &cv);
+      twiddle((double)rr, g.n_phi, &sv, &cv);
       const bool okb = k < g.nk && m <= g.L;
       cs[s] = okb ? cv : 0.0;
       sn[s] = okb ? sv : 0.0;
@@ -558,7 +613,8 @@ __global__ __launch_bounds__(640, 1) void analysis_split_kernel(
     for (int it = 0; p < n_pairs; p += stride, it ^= 1) {
       double2* Fb = Fs + it * 2 * fsz;
       // k-step by k-step: fold, ask for the same samples of the next pair (their registers are free from here on, and
-      // the request is in flight under everything up to the next trip's fold), four products
+      // the request is in flight under everything up to the next trip's fold), four products.  This fold stays apart from
+      // folded_products: its operands never touch LDS, and the next pair's loads and the sched_barrier sit inside the k loop.
       const auto next = descriptor(p + stride);
       const double2 pole_value = xp;
       xp = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(next, pole_off, 0, 0));
@@ -589,8 +645,9 @@ __global__ __launch_bounds__(640, 1) void analysis_split_kernel(
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         if (fo[v] >= 0) {
-          Fb[fo[v] + (g.L + m) * PJ] = double2{cr[v] + si[v], ci[v] - sr[v]};
-          Fb[fo[v] + (g.L - m) * PJ] = double2{cr[v] - si[v], ci[v] + sr[v]};
+          const PlusMinus f = recombine(cr[v], ci[v], sr[v], si[v]);
+          Fb[fo[v] + (g.L + m) * PJ] = f.plus;
+          Fb[fo[v] + (g.L - m) * PJ] = f.minus;
         }
       }
       if (pole_fo >= 0) Fb[pole_fo] = double2{(double)g.n_phi * pole_value.x, (double)g.n_phi * pole_value.y};
@@ -633,6 +690,7 @@ __global__ __launch_bounds__(640, 1) void analysis_split_kernel(
       __syncthreads();
       const double2* fa = Fs + it * 2 * fsz + fbase;
       const double2* fb = fa + fsz;
+      // (not quadrature_row: ONE chain per row over all j, for the two rows of the pair -- another rounding order)
       double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
@@ -674,19 +732,48 @@ int split_analysis_supported(int n_theta, int n_phi, int L, int n_out, bool dedu
   return 1;
 }
 
-template <typename K>
-static hipError_t launch_fused_t(K kernel, hipStream_t stream, dim3 grid, dim3 block, size_t lds, const double* G, long long ldg,
-                                 long long n_rows, const FusedGeom& g, const int* m_index, const double* T, const double* D,
-                                 double* out, long long ldo, const int* col_of_pixel) {
-  hipError_t e = allow_dynamic_lds((const void*)kernel);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kernel, grid, block, lds, stream, G, ldg, n_rows, g, m_index, T, D, out, ldo, col_of_pixel);
-  return hipGetLastError();
+// ---- which instance runs: go(...) launches the kernel whose template arguments it is handed as std::integral_constant
+
+// analysis_split_kernel<NT, KS>: nt of split_analysis_supported, three or five k-steps
+template <class Go>
+static hipError_t with_split_instance(int nt, int ks, Go go) {
+  const auto with_ks = [&](auto NT) { return ks <= 3 ? go(NT, int_c<3>{}) : go(NT, int_c<5>{}); };
+  if (nt == 24) return with_ks(int_c<24>{});
+  if (nt == 38) return with_ks(int_c<38>{});
+  return with_ks(int_c<40>{});
+}
+
+// The one place that says which analysis_fused[_wide]_kernel<NT, KS, EPT> exist: those a shape can reach.  The fold has at
+// most NT x 4 KS items and a workgroup 256 threads or more, hence EPT <= ceil(NT 4 KS / 256); and <40, 6, 2> of the one-role
+// kernel would take 525 items or more on over 256 threads, i.e. n_out > 320, which l <= 16 (n_out <= 289) never has.
+// tests/test_oracle_analysis_exact.py enumerates the launcher's whole domain against this list.
+constexpr bool fused_instance_exists(bool wide, int nt, int ks, int ept) {
+  return ept >= 2 && ept <= (nt * 4 * ks + 255) / 256 && (wide || !(nt == 40 && ks == 6 && ept == 2));
+}
+
+// wide: 16 < L; NT 24 | 40 by n_theta; ks = FusedGeom::ks (3, 5 or 6); as few items per thread as the grid needs (each one
+// costs registers for the two rows in flight).  A tuple that does not exist: hipErrorInvalidValue.
+template <class Go>
+static hipError_t with_fused_instance(bool wide, int n_theta, int ks, int ept, Go go) {
+  const auto with_ept = [&](auto W, auto NT, auto KS) {
+    const auto at = [&](auto EPT) -> hipError_t {
+      if constexpr (fused_instance_exists(decltype(W)::value, decltype(NT)::value, decltype(KS)::value, decltype(EPT)::value))
+        return go(W, NT, KS, EPT);
+      else
+        return hipErrorInvalidValue;
+    };
+    return ept <= 2 ? at(int_c<2>{}) : ept == 3 ? at(int_c<3>{}) : at(int_c<4>{});
+  };
+  const auto with_ks = [&](auto W, auto NT) {
+    return ks == 3 ? with_ept(W, NT, int_c<3>{}) : ks == 5 ? with_ept(W, NT, int_c<5>{}) : with_ept(W, NT, int_c<6>{});
+  };
+  const auto with_nt = [&](auto W) { return n_theta <= 24 ? with_ks(W, int_c<24>{}) : with_ks(W, int_c<40>{}); };
+  return wide ? with_nt(std::true_type{}) : with_nt(std::false_type{});
 }
 
 hipError_t launch_analysis_fused(hipStream_t stream, const double* G, long long ldg, long long n_rows, int n_theta, int n_phi,
                                  int L, int n_out, const int* m_index, const double* T, const double* D, double* out,
-                                 long long ldo, const int* col_of_pixel, int spin, bool allow_split) {
+                                 long long ldo, const int* col_of_pixel, int spin, int n_cu, bool allow_split) {
   if (n_rows <= 0) return hipSuccess;
   FusedGeom g;
   size_t lds;
@@ -705,35 +792,15 @@ hipError_t launch_analysis_fused(hipStream_t stream, const double* G, long long 
       const long long pair_bytes = 16 * ldg;
       sg.ahead = BMS_PROBE_ENV("SCRI_AMD_SPLIT_PREFETCH") ? atoi(BMS_PROBE_ENV("SCRI_AMD_SPLIT_PREFETCH"))
                                                    : (col_of_pixel && pair_bytes >= (32 << 10) && 96 * pair_bytes <= (4LL << 20) ? 1 : 0);
-      static const long long cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return (long long)n;
-      }();
       const long long n_pairs = (n_rows + 1) / 2;
       // one workgroup per CU at cfg3 (10 waves); small shapes need fewer waves and get two or three
       const long long per_cu = 10 / (sg.nf + sg.nb) < 3 ? 10 / (sg.nf + sg.nb) : 3;
-      const long long max_blocks = cus * per_cu;
+      const long long max_blocks = n_cu * per_cu;
       const dim3 sgrid((unsigned)(n_pairs < max_blocks ? n_pairs : max_blocks)), sblock(64 * (sg.nf + sg.nb));
-      const int ks = (sg.nk + 3) / 4;
-#define SPLIT_GO(NT, KS)                                                                                                   \
-  {                                                                                                                        \
-    hipError_t e = allow_dynamic_lds((const void*)analysis_split_kernel<NT, KS>);                                                                         \
-    if (e != hipSuccess) return e;                                                                                         \
-    hipLaunchKernelGGL((analysis_split_kernel<NT, KS>), sgrid, sblock, slds, stream, G, ldg, n_rows, sg, m_index, T, out, ldo, \
-                       col_of_pixel);                                                                                      \
-    return hipGetLastError();                                                                                              \
-  }
-#define SPLIT_KS(NT)              \
-  {                               \
-    if (ks <= 3) SPLIT_GO(NT, 3)  \
-    SPLIT_GO(NT, 5)               \
-  }
-      if (nt == 24) SPLIT_KS(24)
-      if (nt == 38) SPLIT_KS(38)
-      SPLIT_KS(40)
-#undef SPLIT_KS
-#undef SPLIT_GO
+      return with_split_instance(nt, folded_k_steps(n_phi), [&](auto NT, auto KS) {
+        return launch_with_lds(analysis_split_kernel<NT.value, KS.value>, sgrid, sblock, slds, stream, G, ldg, n_rows, sg, m_index, T, out,
+                               ldo, col_of_pixel);
+      });
     }
   }
   g.spin = spin;
@@ -742,41 +809,21 @@ hipError_t launch_analysis_fused(hipStream_t stream, const double* G, long long 
   if (threads < 256) threads = 256;
   // persistent workgroups, two per CU (what registers and LDS allow): measured 0.76 ms at 2 x CUs vs 1.00 ms at 3 x
   // (tail) and 1.16 ms at 1 x on cfg3
-  static const long long max_blocks = [] {
-    if (BMS_PROBE_ENV("SCRI_AMD_FUSED_BLOCKS")) return atoll(BMS_PROBE_ENV("SCRI_AMD_FUSED_BLOCKS"));
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    return 2LL * cus;
-  }();
+  static const char* const blocks_env = BMS_PROBE_ENV("SCRI_AMD_FUSED_BLOCKS");
+  const long long max_blocks = blocks_env ? atoll(blocks_env) : 2LL * n_cu;
   const long long blocks = n_rows < max_blocks ? n_rows : max_blocks;
   const dim3 grid((unsigned)blocks), block(threads);
-#define FUSED_GO(K) return launch_fused_t(K, stream, grid, block, lds, G, ldg, n_rows, g, m_index, T, D, out, ldo, col_of_pixel)
-#define FUSED_EPT(KERNEL, NT, KS)                        \
-  {                                                      \
-    if (ept <= 2) FUSED_GO((KERNEL<NT, KS, 2>));         \
-    if (ept == 3) FUSED_GO((KERNEL<NT, KS, 3>));         \
-    FUSED_GO((KERNEL<NT, KS, 4>));                       \
-  }
-#define FUSED_KS(NT)                                              \
-  if (L <= 16) {                                                  \
-    if (g.ks == 3) FUSED_EPT(analysis_fused_kernel, NT, 3)        \
-    if (g.ks == 5) FUSED_EPT(analysis_fused_kernel, NT, 5)        \
-    FUSED_EPT(analysis_fused_kernel, NT, 6)                       \
-  }                                                               \
-  if (g.ks == 3) FUSED_EPT(analysis_fused_wide_kernel, NT, 3)     \
-  if (g.ks == 5) FUSED_EPT(analysis_fused_wide_kernel, NT, 5)     \
-  FUSED_EPT(analysis_fused_wide_kernel, NT, 6)
-  // items per thread of the fold: as few as the grid needs (each one costs registers for the two rows in flight)
-  const int ept = (n_theta * g.nk + threads - 1) / threads;
+  const int ept = (n_theta * g.nk + threads - 1) / threads;  // items per thread of the fold
   if (ept > F_EPT_MAX) return hipErrorInvalidValue;
-  if (n_theta <= 24) {
-    FUSED_KS(24)
-  }
-  FUSED_KS(40)
-#undef FUSED_EPT
-#undef FUSED_KS
-#undef FUSED_GO
+  return with_fused_instance(L > 16, n_theta, g.ks, ept, [&](auto W, auto NT, auto KS, auto EPT) {
+    const auto launch = [&](auto kernel) {
+      return launch_with_lds(kernel, grid, block, lds, stream, G, ldg, n_rows, g, m_index, T, D, out, ldo, col_of_pixel);
+    };
+    if constexpr (W.value)
+      return launch(analysis_fused_wide_kernel<NT.value, KS.value, EPT.value>);
+    else
+      return launch(analysis_fused_kernel<NT.value, KS.value, EPT.value>);
+  });
 }
 
 // =====================================================================================================================
@@ -804,7 +851,7 @@ __global__ __launch_bounds__(64) void phi_dft_folded_kernel(const double* __rest
     for (int n = 0; n < NTC; ++n) {
       const int k = 4 * s + fk, m = 16 * n + fi + 1;
       double sn = 0.0, co = 0.0;
-      if (k < nk && m <= L) sincospi(2.0 * (double)(((long long)m * k) % n_phi) / (double)n_phi, &sn, &co);
+      if (k < nk && m <= L) twiddle((double)(((long long)m * k) % n_phi), n_phi, &sn, &co);
       bc[s][n] = co, bs[s][n] = sn;
     }
   for (int e = lane; e < 16 * PA; e += 64) Es[e] = Os[e] = 0.0;
@@ -817,13 +864,15 @@ __global__ __launch_bounds__(64) void phi_dft_folded_kernel(const double* __rest
   for (int i = 0; i < NPRE; ++i) {
     const int e = lane + 64 * i;
     const int r = e / nk, kk = e - r * nk;
-    const int k2 = kk == 0 ? 0 : n_phi - kk;
+    const int k2 = fold_partner(kk, n_phi);
     ga[i] = e < 8 * nk ? 2 * (r * n_phi + kk) : -1;
     gb[i] = (e < 8 * nk && k2 != kk) ? 2 * (r * n_phi + k2) : -1;
     so[i] = (r << 16) | (((r & 3) + 8 * (r >> 2)) * PA + kk);
   }
   double2 pa[NPRE], pb[NPRE];
-#define DFT_LOAD(ITEM)                                                                                          \
+  // (DFT_LOAD here and TQ_LOAD of the quadrature kernel stay two: sample pairs of a ring tile against single values of eight time
+  // steps, other bounds -- one body for both would branch on its caller)
+#define DFT_LOAD(ITEM)                                                                                         \
   {                                                                                                             \
     const long long t_ = (ITEM) / mt;                                                                           \
     const int rt_ = (int)((ITEM)-t_ * mt);                                                                      \
@@ -854,28 +903,11 @@ __global__ __launch_bounds__(64) void phi_dft_folded_kernel(const double* __rest
       }
     if (item + gridDim.x < n_items) DFT_LOAD(item + gridDim.x)
     // (one wave: its LDS writes are visible to its own reads in program order)
-    v4d_t ac[NTC], as[NTC];
-#pragma unroll
-    for (int n = 0; n < NTC; ++n) ac[n] = as[n] = v4d_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const double ae = Es[fi * PA + 4 * s + fk], ao = Os[fi * PA + 4 * s + fk];
-#pragma unroll
-      for (int n = 0; n < NTC; ++n) {
-        ac[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ae, bc[s][n], ac[n], 0, 0, 0);
-        as[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ao, bs[s][n], as[n], 0, 0, 0);
-      }
-    }
+    const FoldedAcc<NTC> acc = folded_products<KS, NTC, NTC, 1>(Es + fi * PA + fk, Os + fi * PA + fk, &bc[0][0], &bs[0][0]);
     // m = 0: plain sums of the folded rows
     if (fk == 0) {
-      double c0 = 0.0, c1 = 0.0;
-#pragma unroll
-      for (int k = 0; k < 4 * KS; k += 2) {
-        c0 += Es[fi * PA + k];
-        c1 += Es[fi * PA + k + 1];
-      }
       const int ring = (fi & 3) + 4 * (fi >> 3), part = (fi >> 2) & 1;
-      reinterpret_cast<double*>(Ft + L * 8 + ring)[part] = c0 + c1;
+      reinterpret_cast<double*>(Ft + L * 8 + ring)[part] = folded_row_sum<KS>(Es + fi * PA);
     }
 #pragma unroll
     for (int n = 0; n < NTC; ++n) {
@@ -884,9 +916,9 @@ __global__ __launch_bounds__(64) void phi_dft_folded_kernel(const double* __rest
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int ring = fk + 4 * h;
-          const double cre = ac[n][2 * h], cim = ac[n][2 * h + 1], sre = as[n][2 * h], sim = as[n][2 * h + 1];
-          Ft[(L + m) * 8 + ring] = double2{cre + sim, cim - sre};
-          Ft[(L - m) * 8 + ring] = double2{cre - sim, cim + sre};
+          const PlusMinus f = recombine(acc.c[n][2 * h], acc.c[n][2 * h + 1], acc.s[n][2 * h], acc.s[n][2 * h + 1]);
+          Ft[(L + m) * 8 + ring] = f.plus;
+          Ft[(L - m) * 8 + ring] = f.minus;
         }
       }
     }
@@ -988,68 +1020,53 @@ __global__ __launch_bounds__(256) void theta_quadrature_mfma_kernel(const double
     }
   }
 }
+#undef TQ_LOAD
 
 int large_analysis_supported(int n_theta, int n_phi, int L) {
-  const int ks = (n_phi / 2 + 1 + 3) / 4;
-  return n_theta <= 104 && ks <= 16 && L >= 1 && L <= 32;
+  return n_theta <= 104 && folded_k_steps(n_phi) <= 16 && L >= 1 && L <= 32;
 }
 int large_analysis_jp(int n_theta) { return ((n_theta + 7) / 8) * 8; }
+
+// phi_dft_folded_kernel<KS, NTC>: 7, 10, 13 or 16 k-steps; one or two column tiles over m = 1 .. L
+template <class Go>
+static hipError_t with_dft_instance(int ks, int L, Go go) {
+  const auto with_ks = [&](auto NTC) {
+    return ks <= 7 ? go(int_c<7>{}, NTC) : ks <= 10 ? go(int_c<10>{}, NTC) : ks <= 13 ? go(int_c<13>{}, NTC) : go(int_c<16>{}, NTC);
+  };
+  return L <= 16 ? with_ks(int_c<1>{}) : with_ks(int_c<2>{});
+}
+
+// theta_quadrature_mfma_kernel<KQ, NTQ>: 11, 18 or 26 steps of four rings; one to three column tiles over the l of one m
+template <class Go>
+static hipError_t with_tq_mfma_instance(int kq, int ntq, Go go) {
+  const auto with_kq = [&](auto NTQ) { return kq <= 11 ? go(int_c<11>{}, NTQ) : kq <= 18 ? go(int_c<18>{}, NTQ) : go(int_c<26>{}, NTQ); };
+  return ntq <= 1 ? with_kq(int_c<1>{}) : ntq == 2 ? with_kq(int_c<2>{}) : with_kq(int_c<3>{});
+}
 
 hipError_t launch_analysis_large(hipStream_t stream, const double* G, long long ldg, long long n_rows, int n_theta, int n_phi,
                                  int L, int ell_min_out, const double* T, double* F, double* out, long long ldo) {
   if (n_rows <= 0) return hipSuccess;
   const int jp = large_analysis_jp(n_theta), nm = 2 * L + 1;
-  const int ks = (n_phi / 2 + 1 + 3) / 4;
   const int mt = (n_theta + 7) / 8;
   const size_t lds1 = sizeof(double2) * (size_t)nm * 8;
   const long long items = n_rows * mt;
   const unsigned grid1 = (unsigned)(items < 256 * 16 ? items : 256 * 16);
-#define DFT_GO(KS, NTC)                                                                                              \
-  hipLaunchKernelGGL((phi_dft_folded_kernel<KS, NTC>), dim3(grid1), dim3(64), lds1, stream, G, ldg, n_rows, n_theta, n_phi, L, jp, F)
-#define DFT_KS(NTC)      \
-  if (ks <= 7)           \
-    DFT_GO(7, NTC);      \
-  else if (ks <= 10)     \
-    DFT_GO(10, NTC);     \
-  else if (ks <= 13)     \
-    DFT_GO(13, NTC);     \
-  else                   \
-    DFT_GO(16, NTC);
-  if (L <= 16) {
-    DFT_KS(1)
-  } else {
-    DFT_KS(2)
-  }
-#undef DFT_KS
-#undef DFT_GO
-  hipError_t e = hipGetLastError();
+  hipError_t e = with_dft_instance(folded_k_steps(n_phi), L, [&](auto KS, auto NTC) {
+    hipLaunchKernelGGL((phi_dft_folded_kernel<KS.value, NTC.value>), dim3(grid1), dim3(64), lds1, stream, G, ldg, n_rows, n_theta, n_phi, L,
+                       jp, F);
+    return hipGetLastError();
+  });
   if (e != hipSuccess) return e;
   const int kq = (n_theta + 3) / 4;
   static const int rows_per_block = BMS_PROBE_ENV("SCRI_AMD_TQ_ROWS") ? atoi(BMS_PROBE_ENV("SCRI_AMD_TQ_ROWS")) : 256;
   const dim3 grid2(nm, (unsigned)((n_rows + rows_per_block - 1) / rows_per_block));
   // columns of one m: l = max(|m|, ell_min_out) .. L, at most L + 1 - ell_min_out
   const int ntq = (L + 1 - ell_min_out + 15) / 16;
-#define TQ_GO(KQ, NTQ)                                                                                                     \
-  hipLaunchKernelGGL((theta_quadrature_mfma_kernel<KQ, NTQ>), grid2, dim3(256), 0, stream, F, n_rows, n_theta, L, jp, ell_min_out, \
-                     rows_per_block, T, out, ldo)
-#define TQ_KQ(NTQ)   \
-  if (kq <= 11)      \
-    TQ_GO(11, NTQ);  \
-  else if (kq <= 18) \
-    TQ_GO(18, NTQ);  \
-  else               \
-    TQ_GO(26, NTQ);
-  if (ntq <= 1) {
-    TQ_KQ(1)
-  } else if (ntq == 2) {
-    TQ_KQ(2)
-  } else {
-    TQ_KQ(3)
-  }
-#undef TQ_KQ
-#undef TQ_GO
-#undef TQ_LOAD
-  return hipGetLastError();
+  return with_tq_mfma_instance(kq, ntq, [&](auto KQ, auto NTQ) {
+    hipLaunchKernelGGL((theta_quadrature_mfma_kernel<KQ.value, NTQ.value>), grid2, dim3(256), 0, stream, F, n_rows, n_theta, L, jp,
+                       ell_min_out, rows_per_block, T, out, ldo);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace bms

@@ -765,7 +765,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 hipError_t launch_bspline_backward_eval(hipStream_t stream, const double* C, long long ld, int n_cols, long long g0,
                                         long long n_rows, long long n_knots, const double* x, const BsplineTable* table,
                                         int tile, int halo, const double* base, const double* skew_a, const double* skew_b,
-                                        double tt, long long i_lo, long long i_hi, double* out, long long ldo, const BsplineSpread* spread) {
+                                        double tt, long long i_lo, long long i_hi, double* out, long long ldo, int n_cu, const BsplineSpread* spread) {
   static const int tile_env = BMS_PROBE_ENV("SCRI_AMD_SPLINE_TILE_BWD") ? atoi(BMS_PROBE_ENV("SCRI_AMD_SPLINE_TILE_BWD")) : 0;
   if (n_rows <= 0 || n_cols <= 0 || i_hi <= i_lo) return hipSuccess;
   if (tile_env > 0) {
@@ -774,11 +774,7 @@ hipError_t launch_bspline_backward_eval(hipStream_t stream, const double* C, lon
     // A wave's time grows with tile + halo knots and the launch takes a whole number of rounds of resident waves
     // (16 per CU) plus a tail: measured over 96..1280-knot tiles on the three benchmark shapes (21, 154 and 7 column
     // blocks), time ~ (ceil(waves / slots) + 1/4) (tile + halo) ranks the candidates within a few per cent.
-    static const long long slots = [] {
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-      return 16LL * cus;
-    }();
+    const long long slots = 16LL * n_cu;
     const int cand[4] = {96, 160, 320, 640};
     double best = 1e300;
     for (int t : cand) {

@@ -196,3 +196,34 @@ def test_a_flipped_pole_phase_is_caught_by_one_hot_and_band_limited_rows():
     with pytest.raises(AssertionError, match="E_got"):
         an.check("split", _apply(wrong, f), a, ref, "flipped pole phase, band-limited")
     an.check("split", _apply(good, f), a, ref, "the right matrix, band-limited")
+
+
+# the analysis_fused[_wide]_kernel<NT, KS, EPT> that exist (fused_instance_exists, kernels_analysis.hip), as (wide, NT, KS, EPT)
+FUSED_BUILT = ({(w, 24, 3, 2) for w in (False, True)} | {(w, 24, 5, 2) for w in (False, True)}
+               | {(w, 24, 6, e) for w in (False, True) for e in (2, 3)} | {(w, 40, 3, 2) for w in (False, True)}
+               | {(w, 40, ks, e) for w in (False, True) for ks in (5, 6) for e in (2, 3, 4)}) - {(False, 40, 6, 2)}
+
+
+def test_the_fused_launcher_reaches_exactly_the_instances_that_are_built():
+    """every shape fused_analysis_supported accepts gets one of the 21 instances, never a refusal, and each of the 21 is reached: the
+    launcher's dispatch instantiates no other, so a shape outside this set would come back as hipErrorInvalidValue"""
+    assert len(FUSED_BUILT) == 21
+    reached = set()
+    for L in range(1, 33):
+        n_outs = {an.n_out_of(L, lo) for lo in range(L + 1)}
+        for n_out in n_outs:
+            for n_theta in range(2, 41):
+                for n_phi in range(2, 48):
+                    if not an.fused_takes(n_theta, n_phi, L, n_out):
+                        continue
+                    inst = an.fused_instance(n_theta, n_phi, L, n_out)
+                    assert inst is not None, (n_theta, n_phi, L, n_out)
+                    reached.add(inst[:4])
+    assert reached == FUSED_BUILT, (sorted(reached - FUSED_BUILT), sorted(FUSED_BUILT - reached))
+    # and the rule the predicate states: at most ceil(NT 4 KS / 256) items per thread; no <40, 6, 2> of the one-role kernel
+    assert FUSED_BUILT == {(w, nt, ks, e) for w in (False, True) for nt in (24, 40) for ks in (3, 5, 6) for e in (2, 3, 4)
+                           if e <= (nt * 4 * ks + 255) // 256 and (w or (nt, ks, e) != (40, 6, 2))}
+    # A_CASES runs every one of them on the GPU
+    ran = {an.fused_instance(c.n_theta, c.n_phi, c.L, an.n_out_of(c.L, c.ell_min))[:4] for c in an.A_CASES
+           if an.family_of(c).startswith("fused")}
+    assert ran == FUSED_BUILT
