@@ -473,6 +473,9 @@ int bms_coprecessing_frame(bms_ctx* ctx, const double* t, int64_t n_times, const
  * value does not depend on the others.  A NULL pointer, a bad `mem`, n < 2, m < 0, non-finite or not strictly increasing t_in and
  * non-finite t_out are refused (BMS_ERR_INVALID) before anything is staged; the rotors themselves are not inspected. */
 int bms_squad(bms_ctx* ctx, const double* t_in, int64_t n, const void* R_in, int mem, const double* t_out, int64_t m, void* out);
+/* blocks the scans of the frame chain (the prefix product of rotors, the sign maps of the axis) cut a series of n steps into (tests
+ * place series lengths around one block and around one chunk of block totals); a size, not a status */
+int64_t bms_frame_scan_blocks(int64_t n);
 
 /* ---- time-and-phase alignment of two waveforms from correlation moments (scri_amd/alignment.py; DESIGN: "Alignment as moments") ----
  * The moving waveform A: time axis ta[na] (host, na >= 4, strictly increasing), values ya and knot slopes sa of its not-a-knot cubic

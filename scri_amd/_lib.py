@@ -179,6 +179,7 @@ SIGNATURES = {
     "bms_corotating_frame": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_dp, ctypes.c_double, c_vp, c_dp, c_dp]),
     "bms_coprecessing_frame": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_dp, c_i64, c_int, c_vp, c_dp, c_dp]),
     "bms_squad": (c_int, [c_vp, c_dp, c_i64, c_vp, c_int, c_dp, c_i64, c_vp]),
+    "bms_frame_scan_blocks": (c_i64, [c_i64]),
     "bms_align_moments": (c_int, [c_vp, c_dp, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_i64, c_vp, c_i64,
                                    ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_dp, c_i64, c_int, c_dp]),
     "bms_align_residual": (c_int, [c_vp, c_dp, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_i64, c_vp, c_i64,

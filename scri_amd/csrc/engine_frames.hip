@@ -140,6 +140,8 @@ int squad_checks(bms_ctx* c, const double* t_in, int64_t n, const double* t_out,
 
 }  // namespace
 
+extern "C" int64_t bms_frame_scan_blocks(int64_t n) { return frame_scan_blocks(n); }
+
 extern "C" int bms_squad(bms_ctx* c, const double* t_in, int64_t n, const void* R_in, int mem, const double* t_out, int64_t m,
                          void* out) try {
   if (!c || !t_in || !R_in || !t_out || !out) return fail(c, BMS_ERR_INVALID, "NULL argument");

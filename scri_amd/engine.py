@@ -1155,6 +1155,11 @@ def squad(R_in, t_in, t_out, ctx=None, out=None):
     return out
 
 
+def frame_scan_blocks(n):
+    """blocks the scans of the frame chain cut a series of n steps into (bms_frame_scan_blocks)"""
+    return int(_lib.load().bms_frame_scan_blocks(int(n)))
+
+
 def frame_adjust(frame, right=None, truncate_tolerance=0.0, want_log=False, want_spinors=False, ctx=None):
     """In place on frame[N, 4] (bms_frame_adjust): times the constant rotor `right`, normalised, optionally exp of its logarithm rounded
     to the bits above truncate_tolerance.  Returns (rounded log-frame or None, spinors [N, 4 doubles] = (w + i z, y + i x) or None),

@@ -13,6 +13,8 @@ import pytest
 
 from oracle import mode_calculations_ref as mc
 from oracle import quat, rotations_ref
+from tests.helpers.frame_cases import assert_neighbour_cosines_clear_of_half as _assert_neighbour_cosines_clear_of_half
+from tests.helpers.frame_cases import continuous_loop as _continuous_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -51,28 +53,6 @@ def _precessing_chirp(n, seed=4):
     R = _precessing_rotors(t, spin=0.0)
     # rotate_physical_system(R) = rotate_decomposition_basis(R^-1)
     return t, rotations_ref.rotate_by_series(data, quat.as_spinor_array(quat.qconj(R)), 2, 8)
-
-
-def _continuous_loop(dpa, rough, i_index):
-    """the sign rule of scri/mode_calculations.py:316-363, restated: the anchor points along `rough`; going outwards a vector is
-    flipped when it is further from its (fixed) neighbour than its own length; all normalised"""
-    dpa = np.array(dpa, dtype=float)
-    if np.dot(rough, dpa[i_index]) < 0.0:
-        dpa[i_index] *= -1
-    for i in range(i_index - 1, -1, -1):
-        d = dpa[i] - dpa[i + 1]
-        if d @ d > dpa[i] @ dpa[i]:
-            dpa[i] *= -1
-    for i in range(i_index + 1, dpa.shape[0]):
-        d = dpa[i] - dpa[i - 1]
-        if d @ d > dpa[i] @ dpa[i]:
-            dpa[i] *= -1
-    return dpa / np.linalg.norm(dpa, axis=1)[:, None]
-
-
-def _assert_neighbour_cosines_clear_of_half(raw):
-    cos = np.sum(raw[1:] * raw[:-1], axis=1) / (np.linalg.norm(raw[1:], axis=1) * np.linalg.norm(raw[:-1], axis=1))
-    assert np.abs(np.abs(cos) - 0.5).min() >= 0.1, np.abs(np.abs(cos) - 0.5).min()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. residency
