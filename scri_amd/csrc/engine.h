@@ -639,6 +639,113 @@ BMS_INTERNAL void drop_setup_caches(bms_ctx* c);
 BMS_INTERNAL bool cached_window(bms_ctx* c, bool abd, int64_t& i_lo, int64_t& i_hi);
 BMS_INTERNAL void keep_window(bms_ctx* c, bool abd, int64_t i_lo, int64_t i_hi);
 BMS_INTERNAL int stage_in(bms_ctx* c, const char* name, const void* src, int mem, size_t bytes, const double** dev);
+// ---- the arguments of a building-block entry: `int mem` says whether the caller's arrays are host or device memory
+// The refusal of a bad `mem` in the words every entry uses (`who`: the entries that prefix their messages with their name), then the
+// context's device; select_device = false for the entries whose size checks stand between the two.
+inline int entry_mem(bms_ctx* c, int mem, const char* who = nullptr, bool select_device = true) {
+  if (!valid_mem(mem)) return who ? fail(c, BMS_ERR_INVALID, "%s: mem is BMS_HOST or BMS_DEVICE, got %d", who, mem)
+                                  : fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  if (select_device) HIP_TRY(c, hipSetDevice(c->device));
+  return BMS_OK;
+}
+
+// The staging of one call's arrays, for the entries of the shape "stage inputs, run kernels, copy outputs back, wait".  Device arrays
+// pass through; host arrays go up into named work-space blocks and results come home from such blocks.  finish() queues the copies
+// home in the order they were declared, waits ONCE on the context's stream (read then, as the entries always did) and returns the
+// status.  If the call leaves before finish() -- a refusal or a HIP error after a copy was queued -- the destructor waits on the
+// stream instead, so that no queued work still reads or writes the caller's arrays when the error is returned (before this struct
+// such exits returned at once: the one change of behaviour it brings, on failure paths only).  No heap allocation: MAX_BACK records.
+struct CallIO {
+  static constexpr int MAX_BACK = 4;
+  struct Back {
+    void* dst;
+    const void* dev;
+    size_t bytes, rows, dst_pitch;  // rows != 0: `rows` rows of `bytes` bytes, dense on the device, `dst_pitch` bytes apart at home
+    hipMemcpyKind kind;
+  };
+  bms_ctx* c;
+  int mem;
+  bool finished = false;
+  Back back[MAX_BACK];
+  int n_back = 0;
+  CallIO(bms_ctx* c_, int mem_) : c(c_), mem(mem_) { c->host_copy_queued = false; }
+  CallIO(const CallIO&) = delete;
+  CallIO& operator=(const CallIO&) = delete;
+  ~CallIO() {  // (host_copy_queued: raised by every copy the helper issues, and by upload() / upload_times() beside it)
+    if (c->host_copy_queued && !finished) (void)hipStreamSynchronize(c->stream);
+  }
+  bool host() const { return mem == BMS_HOST; }
+  // an input of `bytes` bytes: the caller's device pointer, or a copy of the host array in block `name` (of block_bytes, if larger)
+  template <class T>
+  int in(const char* name, const void* src, size_t bytes, const T** dev, size_t block_bytes = 0) {
+    if (!host()) {
+      *dev = static_cast<const T*>(src);
+      return BMS_OK;
+    }
+    void* p;
+    if (int rc = dev_buf(c, name, std::max(bytes, block_bytes), &p)) return rc;
+    *dev = static_cast<const T*>(p);
+    c->host_copy_queued = true;
+    HIP_TRY(c, hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return BMS_OK;
+  }
+  // a copy of `bytes` bytes from the device to `dst` at finish(), whatever `mem` is: the outputs that always go to the host
+  // (dst == NULL: an output the caller did not ask for), and with `kind` the result of an in-place entry on its way back
+  int copy_back(void* dst, const void* dev, size_t bytes, hipMemcpyKind kind = hipMemcpyDeviceToHost, size_t rows = 0, size_t dst_pitch = 0) {
+    if (!dst) return BMS_OK;
+    if (n_back == MAX_BACK) return fail(c, BMS_ERR_INVALID, "internal: more than %d outputs in one call", MAX_BACK);
+    back[n_back++] = {dst, dev, bytes, rows, dst_pitch, kind};
+    return BMS_OK;
+  }
+  // an output of `count` elements: the caller's device pointer, or block `name`, which finish() copies to the host array
+  template <class T>
+  int out(const char* name, void* dst, size_t count, T** dev) {
+    *dev = static_cast<T*>(dst);
+    if (!host() || !dst) return BMS_OK;
+    if (int rc = dev_buf_t(c, name, count, dev)) return rc;
+    return copy_back(dst, *dev, count * sizeof(T));
+  }
+  // the same for `rows` rows of `cols` elements that lie `ld_dst` elements apart in a HOST array (dense in the block; a device
+  // array is written in place, with its own pitch)
+  template <class T>
+  int out_rows(const char* name, void* dst, size_t rows, size_t cols, size_t ld_dst, T** dev) {
+    *dev = static_cast<T*>(dst);
+    if (!host() || !dst) return BMS_OK;
+    if (int rc = dev_buf_t(c, name, rows * cols, dev)) return rc;
+    return copy_back(dst, *dev, cols * sizeof(T), hipMemcpyDeviceToHost, rows, ld_dst * sizeof(T));
+  }
+  // an array the kernels work on in place: it starts as `src` and ends in `dst` (which may be `src`).  Device memory: `dst` itself,
+  // after a copy of `src` unless the two are one array; host memory: block `name`, filled from `src` and copied to `dst` by finish()
+  template <class T>
+  int inout(const char* name, const void* src, void* dst, size_t count, T** dev) {
+    *dev = static_cast<T*>(dst);
+    if (host())
+      if (int rc = dev_buf_t(c, name, count, dev)) return rc;
+    if (host() || src != dst) c->host_copy_queued = true;  // (a copy out of or into one of the caller's arrays)
+    if (host() || src != dst) HIP_TRY(c, hipMemcpyAsync(*dev, src, count * sizeof(T), host() ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    return host() ? copy_back(dst, *dev, count * sizeof(T)) : BMS_OK;
+  }
+  int finish() {
+    hipStream_t S = c->stream;
+    for (int i = 0; i < n_back; ++i) {
+      const Back& b = back[i];
+      if (b.rows)
+        HIP_TRY(c, hipMemcpy2DAsync(b.dst, b.dst_pitch, b.dev, b.bytes, b.bytes, b.rows, b.kind, S));
+      else
+        HIP_TRY(c, hipMemcpyAsync(b.dst, b.dev, b.bytes, b.kind, S));
+    }
+    HIP_TRY(c, hipStreamSynchronize(S));
+    finished = true;
+    return BMS_OK;
+  }
+};
+
+// what the entries that read modes c16[n][ld] of l = ell_min .. ell_max through the angular-velocity kernel refuse; *n_modes on success
+BMS_INTERNAL int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, int* n_modes);
+// <Ldt> f8[n][3], <LL> f8[n][9] and omega f8[n][3] of the modes d_y (knots and tables of their time axis: d_x, d_tab, tile) side by side
+// in block "av_out", through blocks "R" and "S": the launches bms_angular_velocity and bms_corotating_frame share (engine_blocks.hip)
+BMS_INTERNAL int angular_velocity_on_device(bms_ctx* c, const double* d_y, int64_t ld, int64_t n, int ell_min, int n_modes, const double* d_x,
+                                            const SplineTable* d_tab, int tile, double** d_res);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

@@ -30,7 +30,7 @@ int align_increasing(bms_ctx* c, const char* what, const double* t, int64_t n) {
 
 int align_checks(bms_ctx* c, const AlignHost& h) {
   if (!c || !h.ta || !h.ya || !h.sa || !h.col_a || !h.tw || !h.w || !h.b || !h.col_b) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(h.mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", h.mem);
+  if (int rc0 = entry_mem(c, h.mem, nullptr, false)) return rc0;  // (the device is selected once every check has passed)
   if (h.n_cols <= 0) return fail(c, BMS_ERR_INVALID, "need at least one common column, got %d", h.n_cols);
   if (h.nw < 2) return fail(c, BMS_ERR_INVALID, "the window needs at least 2 rows, got %lld", (long long)h.nw);
   if (h.na < 4) return fail(c, BMS_ERR_INVALID, "the spline of the moving waveform needs at least 4 time steps, got %lld", (long long)h.na);
@@ -48,7 +48,7 @@ int align_checks(bms_ctx* c, const AlignHost& h) {
 }
 
 // the small host arrays of a call, packed into one upload each: doubles (ta, tw, w, extra) and ints (col_a, col_b, extra)
-int align_stage(bms_ctx* c, const AlignHost& h, const double* extra_d, int64_t n_extra_d, const int32_t* extra_i, int n_extra_i,
+int align_stage(bms_ctx* c, CallIO& io, const AlignHost& h, const double* extra_d, int64_t n_extra_d, const int32_t* extra_i, int n_extra_i,
                 std::vector<double>& pack_d, std::vector<int32_t>& pack_i, AlignSeries& a, const double** d_extra_d, const int** d_extra_i) {
   pack_d.clear(), pack_i.clear();
   pack_d.insert(pack_d.end(), h.ta, h.ta + h.na);
@@ -76,9 +76,9 @@ int align_stage(bms_ctx* c, const AlignHost& h, const double* extra_d, int64_t n
   for (int k = 0; k < h.n_cols; ++k) top_a = std::max(top_a, (int)h.col_a[k]), top_b = std::max(top_b, (int)h.col_b[k]);
   const double *dy, *ds, *db;
   const size_t bytes_a = ((size_t)(h.na - 1) * h.ld_a + top_a + 1) * 16, bytes_b = ((size_t)(h.nw - 1) * h.ld_b + top_b + 1) * 16;
-  if ((rc = stage_in(c, "al_values", h.ya, h.mem, bytes_a, &dy))) return rc;
-  if ((rc = stage_in(c, "al_slopes", h.sa, h.mem, bytes_a, &ds))) return rc;
-  if ((rc = stage_in(c, "al_fixed", h.b, h.mem, bytes_b, &db))) return rc;
+  if ((rc = io.in("al_values", h.ya, bytes_a, &dy))) return rc;
+  if ((rc = io.in("al_slopes", h.sa, bytes_a, &ds))) return rc;
+  if ((rc = io.in("al_fixed", h.b, bytes_b, &db))) return rc;
   a.Y = reinterpret_cast<const double2*>(dy), a.S = reinterpret_cast<const double2*>(ds), a.B = reinterpret_cast<const double2*>(db);
   return BMS_OK;
 }
@@ -104,12 +104,13 @@ extern "C" int bms_align_moments(bms_ctx* c, const double* ta, int64_t na, const
   }
   if (nd == 0) return BMS_OK;
   HIP_TRY(c, hipSetDevice(c->device));
+  CallIO io(c, mem);
   std::vector<double> pack_d;
   std::vector<int32_t> pack_i;
   AlignSeries a;
   const double* d_dts;
   const int* d_slot;
-  if ((rc = align_stage(c, h, dts, nd, m_slot, n_cols, pack_d, pack_i, a, &d_dts, &d_slot))) return rc;
+  if ((rc = align_stage(c, io, h, dts, nd, m_slot, n_cols, pack_d, pack_i, a, &d_dts, &d_slot))) return rc;
   const int nv = 1 + 2 * n_slots, n_ord = order + 1;
   // a launch covers as many offsets as its partial sums have room for; an offset's moments do not depend on the cut
   const size_t per_offset = (size_t)align_row_tiles(nw) * n_ord * nv * sizeof(double);
@@ -120,9 +121,8 @@ extern "C" int bms_align_moments(bms_ctx* c, const double* ta, int64_t na, const
   if ((rc = dev_buf_t(c, "al_out", (size_t)n_ord * nd * nv, &d_out))) return rc;
   for (int64_t d0 = 0; d0 < nd; d0 += slice)
     TIMED(c, BMS_TAG_POINTWISE, launch_align_moments(c->stream, a, d_slot, n_slots, d_dts + d0, std::min(slice, nd - d0), d0, nd, order, d_partial, d_out));
-  HIP_TRY(c, hipMemcpyAsync(out, d_out, sizeof(double) * n_ord * nd * nv, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  if ((rc = io.copy_back(out, d_out, sizeof(double) * n_ord * nd * nv))) return rc;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_align_residual(bms_ctx* c, const double* ta, int64_t na, const void* ya, const void* sa, int64_t ld_a, const int32_t* col_a,
@@ -134,18 +134,18 @@ extern "C" int bms_align_residual(bms_ctx* c, const double* ta, int64_t na, cons
   if (!m_of || !out) return fail(c, BMS_ERR_INVALID, "NULL argument");
   if (!std::isfinite(dt) || !std::isfinite(dphi)) return fail(c, BMS_ERR_INVALID, "the offset and the turn must be finite");
   HIP_TRY(c, hipSetDevice(c->device));
+  CallIO io(c, mem);
   std::vector<double> pack_d, phase(2 * (size_t)n_cols);
   std::vector<int32_t> pack_i;
   for (int k = 0; k < n_cols; ++k) phase[2 * k] = std::cos(m_of[k] * dphi), phase[2 * k + 1] = std::sin(m_of[k] * dphi);
   AlignSeries a;
   const double* d_phase;
   const int* d_none;
-  if ((rc = align_stage(c, h, phase.data(), 2 * (int64_t)n_cols, nullptr, 0, pack_d, pack_i, a, &d_phase, &d_none))) return rc;
+  if ((rc = align_stage(c, io, h, phase.data(), 2 * (int64_t)n_cols, nullptr, 0, pack_d, pack_i, a, &d_phase, &d_none))) return rc;
   double *d_partial, *d_out;
   if ((rc = dev_buf_t(c, "al_partial", (size_t)2 * align_row_tiles(nw), &d_partial))) return rc;
   if ((rc = dev_buf_t(c, "al_out", (size_t)2, &d_out))) return rc;
   TIMED(c, BMS_TAG_POINTWISE, launch_align_residual(c->stream, a, d_phase, dt, d_partial, d_out));
-  HIP_TRY(c, hipMemcpyAsync(out, d_out, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  if ((rc = io.copy_back(out, d_out, sizeof(double) * 2))) return rc;
+  return io.finish();
 } BMS_CATCH(c)

@@ -109,8 +109,7 @@ extern "C" int bms_swsh_grid(bms_ctx* c, const double* rotors, int64_t n, int sp
 extern "C" int bms_map2salm(bms_ctx* c, const void* grid, int mem, int64_t n_maps, int n_theta, int n_phi, int spin,
                             int ell_min, int ell_max, void* modes_out) try {
   if (!c || !grid || !modes_out) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n_theta < 2 || n_phi < 1 || ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bad sizes");
   if (ell_max > MAX_ELL || (long long)n_theta * n_phi > (1LL << 26)) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d on %d x %d: too large", ell_max, n_theta, n_phi);
   if (n_maps <= 0) return BMS_OK;
@@ -118,49 +117,64 @@ extern "C" int bms_map2salm(bms_ctx* c, const void* grid, int mem, int64_t n_map
   int rc;
   AnalysisPlan ana;
   if ((rc = build_analysis(c, "m2s", n_theta, n_phi, spin, ell_min, ell_max, ana))) return rc;
+  CallIO io(c, mem);
   const double* d_in;
-  if ((rc = stage_in(c, "in_data", grid, mem, (size_t)n_maps * n_pix * 16, &d_in))) return rc;
-  double* d_out = (double*)modes_out;
-  if (mem == BMS_HOST)
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_maps * n_out * 2, &d_out))) return rc;
+  double* d_out;
+  if ((rc = io.in("in_data", grid, (size_t)n_maps * n_pix * 16, &d_in))) return rc;
+  if ((rc = io.out("out_data", modes_out, (size_t)n_maps * n_out * 2, &d_out))) return rc;
   if ((rc = run_analysis(c, ana, d_in, n_maps, d_out, 2LL * n_out))) return rc;
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(modes_out, d_out, (size_t)n_maps * n_out * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
+
+namespace {
+
+// What bms_cubic_spline and bms_spline_derivative do alike before their own kernels: the checks (`order`: the derivative's, refused
+// where that entry always refused it; sorted_new: the evaluation points must not decrease), the knots with their tables, the
+// evaluation points and the series on the device, and the forward sweep into block "R".  n_new <= 0: BMS_OK with d_y == NULL.
+struct SplineSetup {
+  double *d_x = nullptr, *d_R = nullptr;
+  const double *d_xn = nullptr, *d_y = nullptr;
+  SplineTable* d_tab = nullptr;
+  int tile = SPLINE_TILE;
+};
+
+int spline_setup(bms_ctx* c, CallIO& io, const double* x, int64_t n, const void* y, int64_t ld, int64_t n_cols, const double* x_new, int64_t n_new,
+                 const int* order, bool sorted_new, SplineSetup& s) {
+  if (n < 4) return fail(c, BMS_ERR_UNSUPPORTED, "cubic spline needs at least 4 knots, got %lld", (long long)n);
+  if (ld < n_cols || n_cols <= 0) return fail(c, BMS_ERR_INVALID, "bad column count / stride");
+  if (order && (*order < -16 || *order > 3)) return fail(c, BMS_ERR_INVALID, "derivative order %d outside [-16, 3]", *order);
+  for (int64_t i = 1; i < n; ++i)
+    if (!(x[i] > x[i - 1])) return fail(c, BMS_ERR_INVALID, "knots must be strictly increasing");
+  for (int64_t i = 1; sorted_new && i < n_new; ++i)
+    if (!(x_new[i] >= x_new[i - 1])) return fail(c, BMS_ERR_INVALID, "evaluation points must be non-decreasing");
+  if (n_new <= 0) return BMS_OK;
+  int rc;
+  void* d_xn;
+  if ((rc = upload_times(c, x, n, 0, n, 0, n, &s.d_x, &s.d_tab))) return rc;
+  if ((rc = upload(c, "times_new", x_new, 8 * (size_t)n_new, &d_xn))) return rc;
+  s.d_xn = (const double*)d_xn;
+  if ((rc = io.in("in_data", y, (size_t)n * ld * 16, &s.d_y))) return rc;
+  if ((rc = dev_buf_t(c, "R", (size_t)n * ld * 2, &s.d_R))) return rc;
+  s.tile = spline_tile_for(x, n);
+  TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(c->stream, s.d_y, s.d_R, 2 * ld, (int)n_cols, 0, n, n, s.d_x, s.d_tab, s.tile, SPLINE_HALO));
+  return BMS_OK;
+}
+
+}  // namespace
 
 extern "C" int bms_cubic_spline(bms_ctx* c, const double* x, int64_t n, const void* y, int64_t ld, int64_t n_cols, int mem,
                                 const double* x_new, int64_t n_new, void* out) try {
   if (!c || !x || !y || !x_new || !out) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (n < 4) return fail(c, BMS_ERR_UNSUPPORTED, "cubic spline needs at least 4 knots, got %lld", (long long)n);
-  if (ld < n_cols || n_cols <= 0) return fail(c, BMS_ERR_INVALID, "bad column count / stride");
-  for (int64_t i = 1; i < n; ++i)
-    if (!(x[i] > x[i - 1])) return fail(c, BMS_ERR_INVALID, "knots must be strictly increasing");
-  for (int64_t i = 1; i < n_new; ++i)
-    if (!(x_new[i] >= x_new[i - 1])) return fail(c, BMS_ERR_INVALID, "evaluation points must be non-decreasing");
-  if (n_new <= 0) return BMS_OK;
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   int rc;
-  double* d_x;
-  void* d_xn;
-  SplineTable* d_tab;
-  if ((rc = upload_times(c, x, n, 0, n, 0, n, &d_x, &d_tab))) return rc;
-  if ((rc = upload(c, "times_new", x_new, 8 * (size_t)n_new, &d_xn))) return rc;
-  const double* d_y;
-  if ((rc = stage_in(c, "in_data", y, mem, (size_t)n * ld * 16, &d_y))) return rc;
-  double* d_R;
-  if ((rc = dev_buf_t(c, "R", (size_t)n * ld * 2, &d_R))) return rc;
-  double* d_out = (double*)out;
-  if (mem == BMS_HOST)
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_new * n_cols * 2, &d_out))) return rc;
-  const int tile = spline_tile_for(x, n);
-  TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(c->stream, d_y, d_R, 2 * ld, (int)n_cols, 0, n, n, (const double*)d_x, d_tab, tile, SPLINE_HALO));
-  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_backward_eval(c->stream, d_y, d_R, 2 * ld, (int)n_cols, 0, n, n, (const double*)d_x, d_tab, tile,
-                                         SPLINE_HALO, (const double*)d_xn, nullptr, nullptr, 0.0, 0, n_new, d_out, 2 * n_cols));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n_new * n_cols * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  CallIO io(c, mem);
+  SplineSetup s;
+  if ((rc = spline_setup(c, io, x, n, y, ld, n_cols, x_new, n_new, nullptr, true, s)) || !s.d_y) return rc;
+  double* d_out;
+  if ((rc = io.out("out_data", out, (size_t)n_new * n_cols * 2, &d_out))) return rc;
+  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_backward_eval(c->stream, s.d_y, s.d_R, 2 * ld, (int)n_cols, 0, n, n, s.d_x, s.d_tab, s.tile,
+                                         SPLINE_HALO, s.d_xn, nullptr, nullptr, 0.0, 0, n_new, d_out, 2 * n_cols));
+  return io.finish();
 } BMS_CATCH(c)
 
 // scipy CubicSpline(x, y).derivative(k) / .antiderivative(-k) evaluated at x_new (ModesTimeSeries.interpolate with
@@ -168,32 +182,17 @@ extern "C" int bms_cubic_spline(bms_ctx* c, const double* x, int64_t n, const vo
 extern "C" int bms_spline_derivative(bms_ctx* c, const double* x, int64_t n, const void* y, int64_t ld, int64_t n_cols, int mem,
                                      const double* x_new, int64_t n_new, int order, void* out) try {
   if (!c || !x || !y || !x_new || !out) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (n < 4) return fail(c, BMS_ERR_UNSUPPORTED, "cubic spline needs at least 4 knots, got %lld", (long long)n);
-  if (ld < n_cols || n_cols <= 0) return fail(c, BMS_ERR_INVALID, "bad column count / stride");
-  if (order < -16 || order > 3) return fail(c, BMS_ERR_INVALID, "derivative order %d outside [-16, 3]", order);
-  for (int64_t i = 1; i < n; ++i)
-    if (!(x[i] > x[i - 1])) return fail(c, BMS_ERR_INVALID, "knots must be strictly increasing");
-  if (n_new <= 0) return BMS_OK;
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   int rc;
-  double* d_x;
-  void* d_xn;
-  SplineTable* d_tab;
-  if ((rc = upload_times(c, x, n, 0, n, 0, n, &d_x, &d_tab))) return rc;
-  if ((rc = upload(c, "times_new", x_new, 8 * (size_t)n_new, &d_xn))) return rc;
-  const double* d_y;
-  if ((rc = stage_in(c, "in_data", y, mem, (size_t)n * ld * 16, &d_y))) return rc;
-  double *d_R, *d_S, *d_P1 = nullptr, *d_P2 = nullptr, *d_carry = nullptr;
-  if ((rc = dev_buf_t(c, "R", (size_t)n * ld * 2, &d_R))) return rc;
+  CallIO io(c, mem);
+  SplineSetup s;
+  if ((rc = spline_setup(c, io, x, n, y, ld, n_cols, x_new, n_new, &order, false, s)) || !s.d_y) return rc;
+  const double *d_y = s.d_y, *d_x = s.d_x, *d_xn = s.d_xn;
+  double *d_S, *d_out, *d_P1 = nullptr, *d_P2 = nullptr, *d_carry = nullptr;
   if ((rc = dev_buf_t(c, "S", (size_t)n * ld * 2, &d_S))) return rc;
   hipStream_t S = c->stream;
-  const int tile = spline_tile_for(x, n);
-  TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_y, d_R, 2 * ld, (int)n_cols, 0, n, n, d_x, d_tab, tile, SPLINE_HALO));
-  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_slopes(S, d_R, d_S, 2 * ld, (int)n_cols, n, d_tab, tile, SPLINE_HALO));
-  double* d_out = (double*)out;
-  if (mem == BMS_HOST)
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_new * n_cols * 2, &d_out))) return rc;
+  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_slopes(S, s.d_R, d_S, 2 * ld, (int)n_cols, n, s.d_tab, s.tile, SPLINE_HALO));
+  if ((rc = io.out("out_data", out, (size_t)n_new * n_cols * 2, &d_out))) return rc;
   if (order < -2) {  // any antiderivative order (scri/modes_time_series.py:88-89): one array of knot values per level
     const int k = -order;
     double* d_Pall;
@@ -201,24 +200,19 @@ extern "C" int bms_spline_derivative(bms_ctx* c, const double* x, int64_t n, con
     if ((rc = dev_buf_t(c, "P_levels", (size_t)k * level_stride, &d_Pall))) return rc;
     if ((rc = dev_buf_t(c, "P_carry", (size_t)spline_prefix_carry_size(n, (int)n_cols), &d_carry))) return rc;
     TIMED(c, BMS_TAG_POINTWISE, launch_spline_prefix_levels(S, d_y, d_S, 2 * ld, (int)n_cols, n, d_x, d_Pall, level_stride, d_carry, k));
-    TIMED(c, BMS_TAG_POINTWISE, launch_spline_antiderivative_eval(S, d_y, d_S, d_Pall, level_stride, 2 * ld, (int)n_cols, n, d_x,
-                                                                  (const double*)d_xn, n_new, k, d_out, 2 * n_cols));
-    if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n_new * n_cols * 16, hipMemcpyDeviceToHost, S));
-    HIP_TRY(c, hipStreamSynchronize(S));
-    return BMS_OK;
+    TIMED(c, BMS_TAG_POINTWISE, launch_spline_antiderivative_eval(S, d_y, d_S, d_Pall, level_stride, 2 * ld, (int)n_cols, n, d_x, d_xn, n_new, k,
+                                                                  d_out, 2 * n_cols));
+  } else {
+    if (order < 0) {
+      if ((rc = dev_buf_t(c, "P1", (size_t)n * ld * 2, &d_P1))) return rc;
+      if (order < -1)
+        if ((rc = dev_buf_t(c, "P2", (size_t)n * ld * 2, &d_P2))) return rc;
+      if ((rc = dev_buf_t(c, "P_carry", (size_t)spline_prefix_carry_size(n, (int)n_cols), &d_carry))) return rc;
+      TIMED(c, BMS_TAG_POINTWISE, launch_spline_prefix(S, d_y, d_S, 2 * ld, (int)n_cols, n, d_x, d_P1, d_P2, d_carry, -order));
+    }
+    TIMED(c, BMS_TAG_POINTWISE, launch_spline_hermite_eval(S, d_y, d_S, d_P1, d_P2, 2 * ld, (int)n_cols, n, d_x, d_xn, n_new, order, d_out, 2 * n_cols));
   }
-  if (order < 0) {
-    if ((rc = dev_buf_t(c, "P1", (size_t)n * ld * 2, &d_P1))) return rc;
-    if (order < -1)
-      if ((rc = dev_buf_t(c, "P2", (size_t)n * ld * 2, &d_P2))) return rc;
-    if ((rc = dev_buf_t(c, "P_carry", (size_t)spline_prefix_carry_size(n, (int)n_cols), &d_carry))) return rc;
-    TIMED(c, BMS_TAG_POINTWISE, launch_spline_prefix(S, d_y, d_S, 2 * ld, (int)n_cols, n, d_x, d_P1, d_P2, d_carry, -order));
-  }
-  TIMED(c, BMS_TAG_POINTWISE, launch_spline_hermite_eval(S, d_y, d_S, d_P1, d_P2, 2 * ld, (int)n_cols, n, d_x, (const double*)d_xn,
-                                                         n_new, order, d_out, 2 * n_cols));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n_new * n_cols * 16, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 // Angular velocity of a waveform from its modes (scri/mode_calculations.py:403-432 with LdtVector :46-57 and LLMatrix
@@ -226,40 +220,49 @@ extern "C" int bms_spline_derivative(bms_ctx* c, const double* x, int64_t n, con
 extern "C" int bms_angular_velocity(bms_ctx* c, const double* t, int64_t n, const void* data, int64_t ld, int ell_min, int ell_max,
                                     int mem, double* ldt_out, double* ll_out, double* omega_out) try {
   if (!c || !t || !data) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n < 4) return fail(c, BMS_ERR_UNSUPPORTED, "the time derivative needs at least 4 time steps, got %lld", (long long)n);
-  if (ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bad ell range");
-  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
-  const int n_modes = LM_total_size(ell_min, ell_max);
-  if (ld < n_modes) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
-  if (!angular_velocity_supported(n_modes))
-    return fail(c, BMS_ERR_UNSUPPORTED, "%d modes (ell = %d .. %d): the angular-velocity kernel holds a time step's modes and their derivatives in LDS and takes at most %d modes",
-                n_modes, ell_min, ell_max, angular_velocity_max_modes());
+  int rc, n_modes;
+  if ((rc = modes_checks(c, ell_min, ell_max, ld, &n_modes))) return rc;
   for (int64_t i = 1; i < n; ++i)
     if (!(t[i] > t[i - 1])) return fail(c, BMS_ERR_INVALID, "time array must be strictly increasing (index %lld)", (long long)i);
-  int rc;
-  double* d_x;
+  CallIO io(c, mem);
+  double *d_x, *d_res;
   SplineTable* d_tab;
   if ((rc = upload_times(c, t, n, 0, n, 0, n, &d_x, &d_tab))) return rc;
   const double* d_y;
-  if ((rc = stage_in(c, "in_data", data, mem, (size_t)n * ld * 16, &d_y))) return rc;
-  double *d_R, *d_S, *d_res;
+  if ((rc = io.in("in_data", data, (size_t)n * ld * 16, &d_y))) return rc;
+  if ((rc = angular_velocity_on_device(c, d_y, ld, n, ell_min, n_modes, d_x, d_tab, spline_tile_for(t, n), &d_res))) return rc;
+  if ((rc = io.copy_back(ldt_out, d_res, sizeof(double) * 3 * n))) return rc;
+  if ((rc = io.copy_back(ll_out, d_res + 3 * n, sizeof(double) * 9 * n))) return rc;
+  if ((rc = io.copy_back(omega_out, d_res + 12 * n, sizeof(double) * 3 * n))) return rc;
+  return io.finish();
+} BMS_CATCH(c)
+
+int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, int* n_modes) {
+  if (ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bad ell range");
+  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
+  *n_modes = LM_total_size(ell_min, ell_max);
+  if (ld < *n_modes) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
+  if (!angular_velocity_supported(*n_modes))
+    return fail(c, BMS_ERR_UNSUPPORTED, "%d modes (ell = %d .. %d): the angular-velocity kernel holds a time step's modes and their derivatives in LDS and takes at most %d modes",
+                *n_modes, ell_min, ell_max, angular_velocity_max_modes());
+  return BMS_OK;
+}
+
+int angular_velocity_on_device(bms_ctx* c, const double* d_y, int64_t ld, int64_t n, int ell_min, int n_modes, const double* d_x,
+                               const SplineTable* d_tab, int tile, double** d_res) {
+  int rc;
+  double *d_R, *d_S;
   if ((rc = dev_buf_t(c, "R", (size_t)n * ld * 2, &d_R))) return rc;
   if ((rc = dev_buf_t(c, "S", (size_t)n * ld * 2, &d_S))) return rc;
-  if ((rc = dev_buf_t(c, "av_out", (size_t)n * 15, &d_res))) return rc;
+  if ((rc = dev_buf_t(c, "av_out", (size_t)n * 15, d_res))) return rc;
   hipStream_t S = c->stream;
-  const int tile = spline_tile_for(t, n);
   TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_y, d_R, 2 * ld, n_modes, 0, n, n, d_x, d_tab, tile, SPLINE_HALO));
   TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_slopes(S, d_R, d_S, 2 * ld, n_modes, n, d_tab, tile, SPLINE_HALO));
-  double *d_ldt = d_res, *d_ll = d_res + 3 * n, *d_om = d_res + 12 * n;
-  TIMED(c, BMS_TAG_POINTWISE, launch_angular_velocity(S, d_y, d_S, 2 * ld, n, ell_min, n_modes, d_ldt, d_ll, d_om));
-  if (ldt_out) HIP_TRY(c, hipMemcpyAsync(ldt_out, d_ldt, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, S));
-  if (ll_out) HIP_TRY(c, hipMemcpyAsync(ll_out, d_ll, sizeof(double) * 9 * n, hipMemcpyDeviceToHost, S));
-  if (omega_out) HIP_TRY(c, hipMemcpyAsync(omega_out, d_om, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
+  TIMED(c, BMS_TAG_POINTWISE, launch_angular_velocity(S, d_y, d_S, 2 * ld, n, ell_min, n_modes, *d_res, *d_res + 3 * n, *d_res + 12 * n));
   return BMS_OK;
-} BMS_CATCH(c)
+}
 
 // Frame from angular velocity: dR/dt = (1/2) Omega R with Omega(t) the not-a-knot cubic spline through omega[n][3]
 // (quaternion.integrate_angular_velocity as called by corotating_frame, scri/mode_calculations.py:470-471).  The state is
@@ -355,14 +358,14 @@ extern "C" int bms_integrate_angular_velocity(bms_ctx* c, const double* t, int64
 extern "C" int bms_salm2map(bms_ctx* c, const void* modes, int mem, int64_t n_maps, int spin, int ell_max, int n_theta, int n_phi,
                             void* grid_out) try {
   if (!c || !modes || !grid_out) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (ell_max < 0 || n_theta < 2 || n_phi < 1 || std::abs(spin) > 4) return fail(c, BMS_ERR_INVALID, "bad sizes");
   if (ell_max > MAX_ELL || (long long)n_theta * n_phi > (1LL << 26)) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d on %d x %d: too large", ell_max, n_theta, n_phi);
   if (n_maps <= 0) return BMS_OK;
   const int n_pix = n_theta * n_phi, nm = (ell_max + 1) * (ell_max + 1);
   hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   const long long P2 = 2LL * n_pix, ldb = round_up(P2, 128);
   // the equiangular grid itself: separable (kernels_synthesis_large.hip) wherever that kernel takes the shape
   SynthesisPlan syn;
@@ -384,19 +387,16 @@ extern "C" int bms_salm2map(bms_ctx* c, const void* modes, int mem, int64_t n_ma
     TIMED(c, BMS_TAG_SETUP, launch_swsh_matrix_complex(S, (const double*)vp, n_pix, spin, 0, ell_max, d_B, ldb));
   }
   const double* d_a;
-  if ((rc = stage_in(c, "in_data", modes, mem, (size_t)n_maps * nm * 16, &d_a))) return rc;
-  double* d_G = (double*)grid_out;
-  if (mem == BMS_HOST)
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_maps * P2, &d_G))) return rc;
+  double* d_G;
+  if ((rc = io.in("in_data", modes, (size_t)n_maps * nm * 16, &d_a))) return rc;
+  if ((rc = io.out("out_data", grid_out, (size_t)n_maps * P2, &d_G))) return rc;
   if (syn.large) {
     SynthesisPlan two = syn;
     two.nt = 0;  // (the one-kernel form wants padded rows)
     if ((rc = run_synthesis(c, two, d_a, 2LL * nm, n_maps, nullptr, d_G, P2))) return rc;
   } else
   TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m(S, d_a, 2LL * nm, d_B, ldb, d_G, P2, n_maps, n_pix, nm, nullptr, nullptr));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(grid_out, d_G, (size_t)n_maps * n_pix * 16, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 // sf.Modes.evaluate(R): the field at arbitrary directions / frames, out[t][p] = sum_k modes[t][k] sY_k(R_p) -- the dense contraction of
@@ -406,8 +406,8 @@ extern "C" int bms_salm2map(bms_ctx* c, const void* modes, int mem, int64_t n_ma
 extern "C" int bms_evaluate_modes(bms_ctx* c, const void* modes, int mem, int64_t n_rows, int64_t ld, int spin, int ell_min, int ell_max,
                                   const double* rotors, int64_t n_rotors, void* out) try {
   if (!c || !modes || !rotors || !out) return BMS_ERR_INVALID;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  HIP_TRY(c, hipSetDevice(c->device));  // (this entry always selected the device before it looked at `mem`)
+  if (int rc0 = entry_mem(c, mem, nullptr, false)) return rc0;
   if (n_rows < 0 || n_rotors < 0 || ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bad sizes");
   if (ell_max > MAX_ELL || n_rotors > (1LL << 26)) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d at %lld directions: too large", ell_max, (long long)n_rotors);
   const int nm = LM_total_size(ell_min, ell_max);
@@ -415,6 +415,7 @@ extern "C" int bms_evaluate_modes(bms_ctx* c, const void* modes, int mem, int64_
   if (n_rows == 0 || n_rotors == 0) return BMS_OK;
   hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   void* d_rot;
   if ((rc = upload(c, "ev_rotors", rotors, 32 * (size_t)n_rotors, &d_rot))) return rc;
   const int n_pix = (int)n_rotors;
@@ -425,18 +426,16 @@ extern "C" int bms_evaluate_modes(bms_ctx* c, const void* modes, int mem, int64_
   TIMED(c, BMS_TAG_SETUP, launch_swsh_matrix_complex(S, (const double*)d_rot, n_pix, spin, ell_min, ell_max, d_B, ldb));
   const double* d_a = (const double*)modes;
   long long lda = 2 * ld;
-  double* d_out = (double*)out;
-  if (mem == BMS_HOST) {
+  double* d_out;
+  if (mem == BMS_HOST) {  // (the rows go up without their padding: a 2-D copy, not io.in)
     double* a;
     if ((rc = dev_buf_t(c, "in_data", (size_t)n_rows * nm * 2, &a))) return rc;
     HIP_TRY(c, hipMemcpy2DAsync(a, (size_t)nm * 16, modes, (size_t)ld * 16, (size_t)nm * 16, (size_t)n_rows, hipMemcpyHostToDevice, S));
     d_a = a, lda = 2LL * nm;
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_rows * n_pix * 2, &d_out))) return rc;
   }
+  if ((rc = io.out("out_data", out, (size_t)n_rows * n_pix * 2, &d_out))) return rc;
   TIMED(c, BMS_TAG_GEMM_SYNTHESIS, launch_zgemm3m(S, d_a, lda, d_B, ldb, d_out, 2LL * n_pix, n_rows, n_pix, nm, nullptr, nullptr));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n_rows * n_pix * 16, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));  // (the rotors were staged from the caller's array)
-  return BMS_OK;
+  return io.finish();  // (the rotors were staged from the caller's array)
 } BMS_CATCH(c)
 
 // Mode-space operators of sf.Modes / ModesTimeSeries (eth, ethbar, bar, real, sums of different l ranges, scalar and per-row
@@ -447,7 +446,7 @@ extern "C" int bms_mode_map(bms_ctx* c, void* out, int64_t ld_out, int64_t n_row
                             const int32_t* idx_a, const void* coef_a, int conj_a, const void* b, int64_t ld_b,
                             const int32_t* idx_b, const void* coef_b, int conj_b, const double* row_scale, int mem) try {
   if (!c || !out || !a || !idx_a || !coef_a) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  if (int rc0 = entry_mem(c, mem, nullptr, false)) return rc0;
   if (b && (!idx_b || !coef_b)) return BMS_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
   if (n_rows < 0 || n_cols <= 0 || ld_out < n_cols || ld_a <= 0 || (b && ld_b <= 0)) return fail(c, BMS_ERR_INVALID, "bad sizes");
@@ -460,6 +459,7 @@ extern "C" int bms_mode_map(bms_ctx* c, void* out, int64_t ld_out, int64_t n_row
   if (max_a >= ld_a || (b && max_b >= ld_b)) return fail(c, BMS_ERR_INVALID, "a source column lies beyond the row stride");
   hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   void* vp;
   ModeMapSide A{}, B{};
   if ((rc = upload(c, "mm_idx_a", idx_a, sizeof(int32_t) * n_cols, &vp))) return rc;
@@ -477,54 +477,32 @@ extern "C" int bms_mode_map(bms_ctx* c, void* out, int64_t ld_out, int64_t n_row
     B.conj = conj_b;
   }
   const double* d_rs = row_scale;
-  double* d_out = (double*)out;
-  if (mem == BMS_HOST) {
-    const double* d;
-    if ((rc = stage_in(c, "in_data", a, mem, ((size_t)(n_rows - 1) * ld_a + max_a + 1) * 16, &d))) return rc;
-    A.data = d;
-    if (b) {
-      if ((rc = stage_in(c, "in_aux0", b, mem, ((size_t)(n_rows - 1) * ld_b + max_b + 1) * 16, &d))) return rc;
-      B.data = d;
-    }
-    if (row_scale) {
-      if ((rc = upload(c, "mm_rows", row_scale, 8 * (size_t)n_rows, &vp))) return rc;
-      d_rs = (const double*)vp;
-    }
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_rows * n_cols * 2, &d_out))) return rc;
-  } else {
-    A.data = (const double*)a;
-    B.data = (const double*)b;
-  }
+  double* d_out;
+  if ((rc = io.in("in_data", a, ((size_t)(n_rows - 1) * ld_a + max_a + 1) * 16, &A.data))) return rc;
+  if (b && (rc = io.in("in_aux0", b, ((size_t)(n_rows - 1) * ld_b + max_b + 1) * 16, &B.data))) return rc;
+  if (row_scale && (rc = io.in("mm_rows", row_scale, 8 * (size_t)n_rows, &d_rs))) return rc;
+  if ((rc = io.out_rows("out_data", out, (size_t)n_rows, 2 * (size_t)n_cols, 2 * (size_t)ld_out, &d_out))) return rc;
   TIMED(c, BMS_TAG_POINTWISE, launch_mode_map(S, d_out, mem == BMS_HOST ? n_cols : ld_out, n_rows, n_cols, A, B, d_rs));
-  if (mem == BMS_HOST)
-    HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)ld_out * 16, d_out, (size_t)n_cols * 16, (size_t)n_cols * 16, (size_t)n_rows,
-                                hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));  // the tables were staged from caller memory
-  return BMS_OK;
+  return io.finish();  // (the tables were staged from caller memory)
 } BMS_CATCH(c)
 
 extern "C" int bms_row_norm(bms_ctx* c, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int take_sqrt, double* out) try {
   if (!c || !data || !out) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n_rows < 0 || n_cols < 0 || ld < n_cols) return fail(c, BMS_ERR_INVALID, "bad sizes");
   if (n_rows == 0) return BMS_OK;
-  hipStream_t S = c->stream;
-  int rc;
-  const double* d_in = (const double*)data;
-  double* d_out = out;
-  if (mem == BMS_HOST) {
-    if (n_cols == 0) {
-      std::memset(out, 0, sizeof(double) * n_rows);
-      return BMS_OK;
-    }
-    if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
-    if ((rc = dev_buf_t(c, "norm_out", (size_t)n_rows, &d_out))) return rc;
+  if (mem == BMS_HOST && n_cols == 0) {
+    std::memset(out, 0, sizeof(double) * n_rows);
+    return BMS_OK;
   }
-  TIMED(c, BMS_TAG_POINTWISE, launch_row_norm(S, d_in, ld, n_rows, n_cols, take_sqrt, d_out));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, sizeof(double) * n_rows, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  int rc;
+  CallIO io(c, mem);
+  const double* d_in;
+  double* d_out;
+  if ((rc = io.in("in_data", data, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
+  if ((rc = io.out("norm_out", out, (size_t)n_rows, &d_out))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_row_norm(c->stream, d_in, ld, n_rows, n_cols, take_sqrt, d_out));
+  return io.finish();
 } BMS_CATCH(c)
 
 // The plain dense products on operands of the caller (include/scri_amd.h states the contract): a thin wrapper of launch_zgemm3m /
@@ -568,59 +546,46 @@ extern "C" int64_t bms_polar_tile_rows(void) { return POLAR_TILE_ROWS; }
 extern "C" int bms_polar(bms_ctx* c, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int unwrap, double* abs_out,
                          double* arg_out, int64_t ld_out) try {
   if (!c || !data || (!abs_out && !arg_out)) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n_rows < 0 || n_cols < 0 || ld < n_cols || ld_out < n_cols) return fail(c, BMS_ERR_INVALID, "bad sizes");
   if (n_rows == 0 || n_cols == 0) return BMS_OK;
   if (n_rows > (int64_t)0x7fffffff * POLAR_TILE_ROWS || n_cols > 65535 * 64) return fail(c, BMS_ERR_UNSUPPORTED, "the series is too long or too wide");
   if (mem == BMS_DEVICE && (((uintptr_t)data & 15) || (((uintptr_t)abs_out | (uintptr_t)arg_out) & 7)))
     return fail(c, BMS_ERR_INVALID, "device arrays must be aligned to their elements");
-  hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   const double* d_in;
-  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
-  double *d_abs = abs_out, *d_arg = arg_out;
-  long long ldo = ld_out;
-  if (mem == BMS_HOST) {
-    ldo = n_cols;
-    if (abs_out && (rc = dev_buf_t(c, "polar_abs", (size_t)n_rows * n_cols, &d_abs))) return rc;
-    if (arg_out && (rc = dev_buf_t(c, "polar_arg", (size_t)n_rows * n_cols, &d_arg))) return rc;
-  }
+  double *d_abs, *d_arg;
+  if ((rc = io.in("in_data", data, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
+  if ((rc = io.out_rows("polar_abs", abs_out, (size_t)n_rows, (size_t)n_cols, (size_t)ld_out, &d_abs))) return rc;
+  if ((rc = io.out_rows("polar_arg", arg_out, (size_t)n_rows, (size_t)n_cols, (size_t)ld_out, &d_arg))) return rc;
   long long* d_carry = nullptr;
   if (unwrap && arg_out)
     if ((rc = dev_buf_t(c, "polar_carry", (size_t)polar_carry_words(n_rows, n_cols), &d_carry))) return rc;
-  TIMED(c, BMS_TAG_POINTWISE, launch_polar(S, d_in, ld, n_rows, n_cols, unwrap, d_abs, d_arg, ldo, d_carry));
-  if (mem == BMS_HOST) {
-    if (abs_out)
-      HIP_TRY(c, hipMemcpy2DAsync(abs_out, (size_t)ld_out * 8, d_abs, (size_t)n_cols * 8, (size_t)n_cols * 8, (size_t)n_rows, hipMemcpyDeviceToHost, S));
-    if (arg_out)
-      HIP_TRY(c, hipMemcpy2DAsync(arg_out, (size_t)ld_out * 8, d_arg, (size_t)n_cols * 8, (size_t)n_cols * 8, (size_t)n_rows, hipMemcpyDeviceToHost, S));
-  }
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  TIMED(c, BMS_TAG_POINTWISE, launch_polar(c->stream, d_in, ld, n_rows, n_cols, unwrap, d_abs, d_arg, mem == BMS_HOST ? n_cols : ld_out, d_carry));
+  return io.finish();
 } BMS_CATCH(c)
 
 // the "data must be finite" check of WaveformBase.ensure_validity (scri/waveform_base.py:299-367) where the data are
 extern "C" int bms_count_nonfinite(bms_ctx* c, const void* data, int64_t ld, int64_t n_rows, int n_cols, int mem, int64_t* count,
                                    int64_t* first_row) try {
   if (!c || !data || !count || !first_row) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n_rows < 0 || n_cols < 0 || ld < n_cols) return fail(c, BMS_ERR_INVALID, "bad sizes");
   if (n_rows == 0 || n_cols == 0) return BMS_OK;
   if (mem == BMS_DEVICE && ((uintptr_t)data & 15)) return fail(c, BMS_ERR_INVALID, "device arrays must be aligned to their elements");
   hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   const double* d_in;
-  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
+  if ((rc = io.in("in_data", data, ((size_t)(n_rows - 1) * ld + n_cols) * 16, &d_in))) return rc;
   unsigned long long* d_acc;
   if ((rc = dev_buf_t(c, "polar_acc", 2, &d_acc))) return rc;
   HIP_TRY(c, hipMemsetAsync(d_acc, 0, 8, S));
   HIP_TRY(c, hipMemsetAsync(d_acc + 1, 0xff, 8, S));
   TIMED(c, BMS_TAG_POINTWISE, launch_count_nonfinite(S, d_in, ld, n_rows, n_cols, d_acc));
   unsigned long long acc[2];
-  HIP_TRY(c, hipMemcpyAsync(acc, d_acc, 16, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
+  if ((rc = io.copy_back(acc, d_acc, 16)) || (rc = io.finish())) return rc;
   *count = (int64_t)acc[0];
   *first_row = acc[0] ? (int64_t)acc[1] : -1;
   return BMS_OK;
@@ -631,8 +596,7 @@ extern "C" int bms_count_nonfinite(bms_ctx* c, const void* data, int64_t ld, int
 extern "C" int bms_grid_multiply(bms_ctx* c, const void* a, int spin_a, int ell_max_a, const void* b, int spin_b, int ell_max_b,
                                  int mem, int64_t n_times, int working_ell_max, int output_ell_max, void* out) try {
   if (!c || !a || !b || !out) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (ell_max_a < 0 || ell_max_b < 0 || working_ell_max < 1 || output_ell_max < 0 || output_ell_max > working_ell_max)
     return fail(c, BMS_ERR_INVALID, "bad l ranges (need 0 <= output_ell_max <= working_ell_max)");
   if (ell_max_a > MAX_ELL || ell_max_b > MAX_ELL || working_ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "l beyond %d", MAX_ELL);
@@ -654,6 +618,7 @@ extern "C" int bms_grid_multiply(bms_ctx* c, const void* a, int spin_a, int ell_
   const int n_out = (output_ell_max + 1) * (output_ell_max + 1);
   hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   // grid rotors R(theta_j, phi_k) in the natural order the analysis expects
   std::vector<double> rot(4 * (size_t)n_pix);
   for (int j = 0; j < n_theta; ++j)
@@ -686,11 +651,10 @@ extern "C" int bms_grid_multiply(bms_ctx* c, const void* a, int spin_a, int ell_
   AnalysisPlan ana;
   if ((rc = build_analysis(c, "gm", n_theta, n_phi, spin_a + spin_b, 0, output_ell_max, ana))) return rc;
   const double *d_a, *d_b;
-  if ((rc = stage_in(c, "in_data", a, mem, (size_t)n_times * nma * 16, &d_a))) return rc;
-  if ((rc = stage_in(c, "in_aux0", b, mem, (size_t)n_times * nmb * 16, &d_b))) return rc;
-  double* d_out = (double*)out;
-  if (mem == BMS_HOST)
-    if ((rc = dev_buf_t(c, "out_data", (size_t)n_times * n_out * 2, &d_out))) return rc;
+  double* d_out;
+  if ((rc = io.in("in_data", a, (size_t)n_times * nma * 16, &d_a))) return rc;
+  if ((rc = io.in("in_aux0", b, (size_t)n_times * nmb * 16, &d_b))) return rc;
+  if ((rc = io.out("out_data", out, (size_t)n_times * n_out * 2, &d_out))) return rc;
   // (the separable kernel reads one more complex number per row -- the eliminated constant of the transformation's series: the
   // operands are copied to rows with a zero there)
   // (the two-kernel form reads the plain rows)
@@ -728,42 +692,36 @@ extern "C" int bms_grid_multiply(bms_ctx* c, const void* a, int spin_a, int ell_
     TIMED(c, BMS_TAG_POINTWISE, launch_cmul(S, d_Ga, d_Gb, d_Ga, rows * (long long)n_pix));
     if ((rc = run_analysis(c, ana, d_Ga, rows, d_out + r0 * n_out * 2, 2LL * n_out))) return rc;
   }
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n_times * n_out * 16, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 // ====================================================================================================== storage formats
 // scri/utilities.py:194-232: XOR differencing of a time series in place (rows of 64-bit words)
 extern "C" int bms_xor_timeseries(bms_ctx* c, void* data, int mem, int64_t n_rows, int64_t words_per_row, int reverse) try {
   if (!c || !data) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n_rows < 0 || words_per_row < 0) return fail(c, BMS_ERR_INVALID, "negative size");
   if (n_rows == 0 || words_per_row == 0) return BMS_OK;
   const size_t bytes = (size_t)n_rows * words_per_row * 8;
-  hipStream_t S = c->stream;
   int rc;
-  uint64_t *d_in = (uint64_t*)data, *d_out, *d_carry = nullptr;
-  if (mem == BMS_HOST) {
-    if ((rc = dev_buf_t(c, "bits_in", bytes / 8, &d_in))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(d_in, data, bytes, hipMemcpyHostToDevice, S));
-  }
+  CallIO io(c, mem);
+  const uint64_t* d_in;
+  uint64_t *d_out, *d_carry = nullptr;
+  if ((rc = io.in("bits_in", data, bytes, &d_in))) return rc;
   if ((rc = dev_buf_t(c, "bits_out", bytes / 8, &d_out))) return rc;
   if (reverse)
     if ((rc = dev_buf_t(c, "bits_carry", (size_t)xor_carry_words(n_rows, words_per_row), &d_carry))) return rc;
-  TIMED(c, BMS_TAG_POINTWISE, launch_xor_timeseries(S, d_in, d_out, d_carry, n_rows, words_per_row, reverse));
-  HIP_TRY(c, hipMemcpyAsync(data, d_out, bytes, mem == BMS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  TIMED(c, BMS_TAG_POINTWISE, launch_xor_timeseries(c->stream, d_in, d_out, d_carry, n_rows, words_per_row, reverse));
+  // (in place for the caller, out of place on the device: the result goes back over `data` in either kind of memory)
+  if ((rc = io.copy_back(data, d_out, bytes, mem == BMS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice))) return rc;
+  return io.finish();
 } BMS_CATCH(c)
 
 // scri/utilities.py:271-406: the function multishuffle(shuffle_widths, forward) returns, applied to n elements
 extern "C" int bms_multishuffle(bms_ctx* c, const void* in, void* out, int mem, int64_t n, const int* widths, int n_widths,
                                 int forward) try {
   if (!c || !in || !out || !widths) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   int bit_width = 0;
   for (int i = 0; i < n_widths; ++i) {
     if (widths[i] < 1) return fail(c, BMS_ERR_INVALID, "shuffle widths must be positive");
@@ -774,47 +732,39 @@ extern "C" int bms_multishuffle(bms_ctx* c, const void* in, void* out, int mem, 
   if (n < 0) return fail(c, BMS_ERR_INVALID, "negative size");
   if (n == 0) return BMS_OK;
   const size_t bytes = (size_t)n * (bit_width / 8);
-  hipStream_t S = c->stream;
   int rc;
-  const void* d_in = in;
+  CallIO io(c, mem);
+  const void* d_in;
   void* d_out = out;
-  if (mem == BMS_HOST) {
-    uint64_t *a, *b;
-    if ((rc = dev_buf_t(c, "bits_in", (bytes + 7) / 8 + 1, &a))) return rc;
-    if ((rc = dev_buf_t(c, "bits_out", (bytes + 7) / 8 + 1, &b))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(a, in, bytes, hipMemcpyHostToDevice, S));
-    d_in = a, d_out = b;
+  const size_t words = (bytes + 7) / 8 + 1;  // (the blocks of a host call: whole words and one to spare)
+  if ((rc = io.in("bits_in", in, bytes, &d_in, 8 * words))) return rc;
+  if (io.host()) {  // (the elements go home, not the block's padding: not io.out)
+    uint64_t* b;
+    if ((rc = dev_buf_t(c, "bits_out", words, &b)) || (rc = io.copy_back(out, b, bytes))) return rc;
+    d_out = b;
   }
-  TIMED(c, BMS_TAG_POINTWISE, launch_multishuffle(S, d_in, d_out, n, widths, n_widths, bit_width, forward));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  TIMED(c, BMS_TAG_POINTWISE, launch_multishuffle(c->stream, d_in, d_out, n, widths, n_widths, bit_width, forward));
+  return io.finish();
 } BMS_CATCH(c)
 
 // scri/utilities.py:235-268: Fletcher-32 over the data viewed as 16-bit words (n_bytes must be even)
 extern "C" int bms_fletcher32(bms_ctx* c, const void* data, int mem, int64_t n_bytes, uint32_t* checksum) try {
   if (!c || !checksum || (!data && n_bytes)) return BMS_ERR_INVALID;
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n_bytes < 0 || (n_bytes & 1)) return fail(c, BMS_ERR_INVALID, "the data must be viewable as 16-bit words");
   *checksum = 0;
   if (n_bytes == 0) return BMS_OK;
   hipStream_t S = c->stream;
   int rc;
-  const void* d_in = data;
-  if (mem == BMS_HOST) {
-    uint64_t* a;
-    if ((rc = dev_buf_t(c, "bits_in", (size_t)(n_bytes + 7) / 8, &a))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(a, data, (size_t)n_bytes, hipMemcpyHostToDevice, S));
-    d_in = a;
-  }
+  CallIO io(c, mem);
+  const void* d_in;
+  if ((rc = io.in("bits_in", data, (size_t)n_bytes, &d_in, (size_t)(n_bytes + 7) / 8 * 8))) return rc;
   unsigned long long* d_acc;
   if ((rc = dev_buf_t(c, "bits_acc", 2, &d_acc))) return rc;
   HIP_TRY(c, hipMemsetAsync(d_acc, 0, 16, S));
   TIMED(c, BMS_TAG_POINTWISE, launch_fletcher32(S, d_in, n_bytes / 2, d_acc));
   unsigned long long acc[2];
-  HIP_TRY(c, hipMemcpyAsync(acc, d_acc, 16, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
+  if ((rc = io.copy_back(acc, d_acc, 16)) || (rc = io.finish())) return rc;
   *checksum = (uint32_t)((acc[1] % 65535) << 16 | (acc[0] % 65535));
   return BMS_OK;
 } BMS_CATCH(c)
@@ -836,7 +786,7 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 // modes c16[n_times][ld_modes] on one side, words u64[n_times][2 n_modes] on the other; per row of a piece the device holds both
 BMS_INTERNAL int plan_paired_xor(bms_ctx* c, const char* who, const void* modes, int64_t ld_modes, const void* words, int64_t n_times,
                                  int ell_min, int ell_max, int mem, PairedPlan& P) {
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "%s: mem is BMS_HOST or BMS_DEVICE, got %d", who, mem);
+  if (int rc = entry_mem(c, mem, who, false)) return rc;  // (the device is selected by the entry, once the plan stands)
   if (n_times < 0) return fail(c, BMS_ERR_INVALID, "%s: negative n_times", who);
   if (ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "%s: need 0 <= ell_min <= ell_max, got [%d, %d]", who, ell_min, ell_max);
   if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "%s: ell_max = %d beyond %d", who, ell_max, MAX_ELL);

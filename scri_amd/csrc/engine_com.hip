@@ -10,55 +10,47 @@ extern "C" int bms_com_motion(bms_ctx* c, const double* t, const double* x_a, co
                               const double* m_b, int64_t n_m_b, int64_t n, int matter, int mem, double* t_out, double* com_out) try {
   if (!c) return BMS_ERR_INVALID;
   if (!x_a || !x_b || !m_a || !m_b || !com_out || (matter && (!t || !t_out))) return fail(c, BMS_ERR_INVALID, "bms_com_motion: NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "bms_com_motion: mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  if (int rc0 = entry_mem(c, mem, "bms_com_motion", false)) return rc0;  // (the size checks come before the device is selected)
   if (n < 1) return fail(c, BMS_ERR_INVALID, "bms_com_motion: need at least one sample, got %lld", (long long)n);
   if ((n_m_a != 1 && n_m_a != n) || (n_m_b != 1 && n_m_b != n))
     return fail(c, BMS_ERR_INVALID, "bms_com_motion: a mass is one value or one per sample (%lld), got %lld and %lld", (long long)n, (long long)n_m_a,
                 (long long)n_m_b);
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   const double *d_t = t, *d_xa, *d_xb, *d_ma, *d_mb;
-  if ((rc = stage_in(c, "com_xa", x_a, mem, (size_t)n * 24, &d_xa))) return rc;
-  if ((rc = stage_in(c, "com_xb", x_b, mem, (size_t)n * 24, &d_xb))) return rc;
-  if ((rc = stage_in(c, "com_ma", m_a, mem, (size_t)n_m_a * 8, &d_ma))) return rc;
-  if ((rc = stage_in(c, "com_mb", m_b, mem, (size_t)n_m_b * 8, &d_mb))) return rc;
-  if (matter && (rc = stage_in(c, "com_t", t, mem, (size_t)n * 8, &d_t))) return rc;
-  double *d_com = com_out, *d_tout = t_out;
-  if (mem == BMS_HOST) {
-    if ((rc = dev_buf_t(c, "com_track", (size_t)n * 3, &d_com))) return rc;
-    if (matter && (rc = dev_buf_t(c, "com_tout", (size_t)n, &d_tout))) return rc;
-  }
-  TIMED(c, BMS_TAG_POINTWISE, launch_com_track(S, d_t, d_xa, d_xb, d_ma, n_m_a, d_mb, n_m_b, n, matter, d_tout, d_com));
-  if (mem == BMS_HOST) {
-    HIP_TRY(c, hipMemcpyAsync(com_out, d_com, (size_t)n * 24, hipMemcpyDeviceToHost, S));
-    if (matter) HIP_TRY(c, hipMemcpyAsync(t_out, d_tout, (size_t)n * 8, hipMemcpyDeviceToHost, S));
-  }
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  if ((rc = io.in("com_xa", x_a, (size_t)n * 24, &d_xa))) return rc;
+  if ((rc = io.in("com_xb", x_b, (size_t)n * 24, &d_xb))) return rc;
+  if ((rc = io.in("com_ma", m_a, (size_t)n_m_a * 8, &d_ma))) return rc;
+  if ((rc = io.in("com_mb", m_b, (size_t)n_m_b * 8, &d_mb))) return rc;
+  if (matter && (rc = io.in("com_t", t, (size_t)n * 8, &d_t))) return rc;
+  double *d_com, *d_tout = t_out;
+  if ((rc = io.out("com_track", com_out, (size_t)n * 3, &d_com))) return rc;
+  if (matter && (rc = io.out("com_tout", t_out, (size_t)n, &d_tout))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_com_track(c->stream, d_t, d_xa, d_xb, d_ma, n_m_a, d_mb, n_m_b, n, matter, d_tout, d_com));
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_com_fit(bms_ctx* c, const double* t, const double* com, int64_t n, int mem, double skip_beginning_fraction,
                            double skip_ending_fraction, int fit_acceleration, bms_com_fit_result* result) try {
   if (!c) return BMS_ERR_INVALID;
   if (!t || !com || !result) return fail(c, BMS_ERR_INVALID, "bms_com_fit: NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "bms_com_fit: mem is BMS_HOST or BMS_DEVICE, got %d", mem);
+  if (int rc0 = entry_mem(c, mem, "bms_com_fit", false)) return rc0;
   if (n < 2) return fail(c, BMS_ERR_INVALID, "bms_com_fit: need at least 2 samples, got %lld", (long long)n);
   if (!std::isfinite(skip_beginning_fraction) || !std::isfinite(skip_ending_fraction))
     return fail(c, BMS_ERR_INVALID, "bms_com_fit: the skip fractions must be finite, got %g and %g", skip_beginning_fraction, skip_ending_fraction);
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t S = c->stream;
   int rc;
+  CallIO io(c, mem);
   const double *d_t, *d_com;
-  if ((rc = stage_in(c, "com_t", t, mem, (size_t)n * 8, &d_t))) return rc;
-  if ((rc = stage_in(c, "com_track", com, mem, (size_t)n * 24, &d_com))) return rc;
+  if ((rc = io.in("com_t", t, (size_t)n * 8, &d_t))) return rc;
+  if ((rc = io.in("com_track", com, (size_t)n * 24, &d_com))) return rc;
   double *d_work, *d_out;
   if ((rc = dev_buf_t(c, "com_work", (size_t)com_fit_work_doubles(n), &d_work))) return rc;
   if ((rc = dev_buf_t(c, "com_out", (size_t)COM_FIT_OUT, &d_out))) return rc;
-  TIMED(c, BMS_TAG_POINTWISE, launch_com_fit(S, d_t, d_com, n, skip_beginning_fraction, skip_ending_fraction, fit_acceleration != 0, d_work, d_out));
+  TIMED(c, BMS_TAG_POINTWISE, launch_com_fit(c->stream, d_t, d_com, n, skip_beginning_fraction, skip_ending_fraction, fit_acceleration != 0, d_work, d_out));
   double out[COM_FIT_OUT];
-  HIP_TRY(c, hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
+  if ((rc = io.copy_back(out, d_out, sizeof(out))) || (rc = io.finish())) return rc;
   for (int k = 0; k < 3; ++k) {
     result->x_i[k] = out[k], result->v_i[k] = out[3 + k], result->a_i[k] = out[6 + k];
     for (int m = 0; m < 3; ++m) result->moments[m][k] = out[13 + 3 * m + k];

@@ -102,29 +102,6 @@ int rotor_omega(bms_ctx* c, const FrameAxis& ax, int64_t n, const double* d_R, d
   return BMS_OK;
 }
 
-// a per-step input array of `mem` on the device, and the device array an output of `mem` is computed into
-int in_array(bms_ctx* c, const char* name, const double* src, int mem, size_t count, const double** dev) {
-  return stage_in(c, name, src, mem, 8 * count, dev);
-}
-int out_array(bms_ctx* c, const char* name, double* dst, int mem, size_t count, double** dev) {
-  if (mem == BMS_DEVICE) {
-    *dev = dst;
-    return BMS_OK;
-  }
-  return dev_buf_t(c, name, count, dev);
-}
-
-int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, int* n_modes) {
-  if (ell_min < 0 || ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bad ell range");
-  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "ell_max = %d is beyond %d", ell_max, MAX_ELL);
-  *n_modes = LM_total_size(ell_min, ell_max);
-  if (ld < *n_modes) return fail(c, BMS_ERR_INVALID, "row stride smaller than the number of modes");
-  if (!angular_velocity_supported(*n_modes))
-    return fail(c, BMS_ERR_UNSUPPORTED, "%d modes (ell = %d .. %d): the angular-velocity kernel holds a time step's modes and their derivatives in LDS and takes at most %d modes",
-                *n_modes, ell_min, ell_max, angular_velocity_max_modes());
-  return BMS_OK;
-}
-
 // what bms_squad refuses in its two host arrays, before anything is staged
 int squad_checks(bms_ctx* c, const double* t_in, int64_t n, const double* t_out, int64_t m) {
   if (n < 2) return fail(c, BMS_ERR_INVALID, "squad needs at least 2 rotors, got %lld", (long long)n);
@@ -145,108 +122,90 @@ extern "C" int64_t bms_frame_scan_blocks(int64_t n) { return frame_scan_blocks(n
 extern "C" int bms_squad(bms_ctx* c, const double* t_in, int64_t n, const void* R_in, int mem, const double* t_out, int64_t m,
                          void* out) try {
   if (!c || !t_in || !R_in || !t_out || !out) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = squad_checks(c, t_in, n, t_out, m))) return rc;
+  if ((rc = entry_mem(c, mem)) || (rc = squad_checks(c, t_in, n, t_out, m))) return rc;
   if (m == 0) return BMS_OK;
+  CallIO io(c, mem);
   void *d_t, *d_u;
   const double* d_R;
   double *d_AB, *d_out;
   if ((rc = upload(c, "times", t_in, 8 * (size_t)n, &d_t))) return rc;
   if ((rc = upload(c, "times_new", t_out, 8 * (size_t)m, &d_u))) return rc;
-  if ((rc = in_array(c, "fr_in", (const double*)R_in, mem, (size_t)n * 4, &d_R))) return rc;
+  if ((rc = io.in("fr_in", R_in, 8 * (size_t)n * 4, &d_R))) return rc;
   if ((rc = dev_buf_t(c, "fr_squad_AB", (size_t)n * 8, &d_AB))) return rc;
-  if ((rc = out_array(c, "fr_out", (double*)out, mem, (size_t)m * 4, &d_out))) return rc;
+  if ((rc = io.out("fr_out", out, (size_t)m * 4, &d_out))) return rc;
   hipStream_t S = c->stream;
   TIMED(c, BMS_TAG_POINTWISE, launch_squad_control(S, d_R, (const double*)d_t, n, d_AB));
   TIMED(c, BMS_TAG_POINTWISE, launch_squad_eval(S, d_R, (const double*)d_t, n, d_AB, (const double*)d_u, m, d_out));
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(out, d_out, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_frame_from_angular_velocity(bms_ctx* c, const double* t, int64_t n, const double* omega, int mem, const double R0[4],
                                                double tolerance, double* R_out) try {
   if (!c || !t || !omega || !R0 || !R_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = check_time_axis(c, t, n))) return rc;
+  if ((rc = entry_mem(c, mem)) || (rc = check_time_axis(c, t, n))) return rc;
+  CallIO io(c, mem);
   FrameAxis ax;
   if ((rc = frame_axis(c, t, n, ax))) return rc;
   const double* d_om;
   double* d_R;
-  if ((rc = in_array(c, "fr_in", omega, mem, (size_t)n * 3, &d_om))) return rc;
-  if ((rc = out_array(c, "fr_out", R_out, mem, (size_t)n * 4, &d_R))) return rc;
+  if ((rc = io.in("fr_in", omega, 8 * (size_t)n * 3, &d_om))) return rc;
+  if ((rc = io.out("fr_out", R_out, (size_t)n * 4, &d_R))) return rc;
   if ((rc = frame_from_omega(c, ax, n, d_om, R0, tolerance, d_R))) return rc;
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(R_out, d_R, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_dominant_axis(bms_ctx* c, const double* ll, int64_t n, int mem, const double rough[3], int64_t rough_index,
                                  double* axis_out) try {
   if (!c || !ll || !rough || !axis_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n < 1) return fail(c, BMS_ERR_INVALID, "need at least one time step, got %lld", (long long)n);
   if (rough_index < 0 || rough_index >= n) return fail(c, BMS_ERR_INVALID, "rough_index %lld outside [0, %lld)", (long long)rough_index, (long long)n);
   int rc;
+  CallIO io(c, mem);
   const double* d_ll;
   double* d_axis;
-  if ((rc = in_array(c, "fr_in", ll, mem, (size_t)n * 9, &d_ll))) return rc;
-  if ((rc = out_array(c, "fr_out", axis_out, mem, (size_t)n * 3, &d_axis))) return rc;
+  if ((rc = io.in("fr_in", ll, 8 * (size_t)n * 9, &d_ll))) return rc;
+  if ((rc = io.out("fr_out", axis_out, (size_t)n * 3, &d_axis))) return rc;
   if ((rc = dominant_axis(c, n, d_ll, rough, rough_index, d_axis))) return rc;
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(axis_out, d_axis, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_minimal_rotation(bms_ctx* c, const double* t, int64_t n, const double* R, int mem, int iterations, double* R_out) try {
   if (!c || !t || !R || !R_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (iterations < 1) return fail(c, BMS_ERR_INVALID, "iterations must be positive, got %d", iterations);
   int rc;
   if ((rc = check_time_axis(c, t, n))) return rc;
+  CallIO io(c, mem);
   FrameAxis ax;
   if ((rc = frame_axis(c, t, n, ax))) return rc;
-  double* d_R;
-  if ((rc = out_array(c, "fr_out", R_out, mem, (size_t)n * 4, &d_R))) return rc;
-  if (mem == BMS_HOST)
-    HIP_TRY(c, hipMemcpyAsync(d_R, R, sizeof(double) * 4 * n, hipMemcpyHostToDevice, c->stream));
-  else if (R != R_out)
-    HIP_TRY(c, hipMemcpyAsync(d_R, R, sizeof(double) * 4 * n, hipMemcpyDeviceToDevice, c->stream));
+  double* d_R;  // (R_out itself on the device, after a copy of R unless the two are one array)
+  if ((rc = io.inout("fr_out", R, R_out, (size_t)n * 4, &d_R))) return rc;
   if ((rc = minimal_rotation(c, ax, n, d_R, iterations))) return rc;
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(R_out, d_R, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_rotor_angular_velocity(bms_ctx* c, const double* t, int64_t n, const double* R, int mem, double* omega_out) try {
   if (!c || !t || !R || !omega_out) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = check_time_axis(c, t, n))) return rc;
+  if ((rc = entry_mem(c, mem)) || (rc = check_time_axis(c, t, n))) return rc;
+  CallIO io(c, mem);
   FrameAxis ax;
   if ((rc = frame_axis(c, t, n, ax))) return rc;
   const double* d_R;
   double* d_om;
-  if ((rc = in_array(c, "fr_in", R, mem, (size_t)n * 4, &d_R))) return rc;
-  if ((rc = out_array(c, "fr_out", omega_out, mem, (size_t)n * 3, &d_om))) return rc;
+  if ((rc = io.in("fr_in", R, 8 * (size_t)n * 4, &d_R))) return rc;
+  if ((rc = io.out("fr_out", omega_out, (size_t)n * 3, &d_om))) return rc;
   if ((rc = rotor_omega(c, ax, n, d_R, d_om))) return rc;
-  if (mem == BMS_HOST) HIP_TRY(c, hipMemcpyAsync(omega_out, d_om, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_frame_adjust(bms_ctx* c, double* frame, int64_t n, int mem, const double right[4], double truncate_tolerance,
                                 double* log_out, void* spinors_out) try {
   if (!c || !frame) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   if (n < 0) return fail(c, BMS_ERR_INVALID, "negative size");
   if (n == 0) return BMS_OK;
   double pow2 = 0.0;
@@ -255,63 +214,42 @@ extern "C" int bms_frame_adjust(bms_ctx* c, double* frame, int64_t n, int mem, c
     pow2 = std::exp2(-std::floor(std::log2(2 * truncate_tolerance)));
   }
   int rc;
-  double *d_frame = frame, *d_log = log_out, *d_sp = (double*)spinors_out;
-  if (mem == BMS_HOST) {
-    void* vp;
-    if ((rc = upload(c, "fr_in", frame, sizeof(double) * 4 * n, &vp))) return rc;
-    d_frame = (double*)vp;
-    if (log_out && (rc = dev_buf_t(c, "fr_out", (size_t)n * 4, &d_log))) return rc;
-    if (spinors_out && (rc = dev_buf_t(c, "fr_spinors", (size_t)n * 4, &d_sp))) return rc;
-  }
+  CallIO io(c, mem);
+  double *d_frame, *d_log, *d_sp;
+  if ((rc = io.inout("fr_in", frame, frame, (size_t)n * 4, &d_frame))) return rc;
+  if ((rc = io.out("fr_out", log_out, (size_t)n * 4, &d_log))) return rc;
+  if ((rc = io.out("fr_spinors", spinors_out, (size_t)n * 4, &d_sp))) return rc;
   Vec4 rt = {{1.0, 0.0, 0.0, 0.0}};
   if (right)
     for (int i = 0; i < 4; ++i) rt.v[i] = right[i];
-  hipStream_t S = c->stream;
-  TIMED(c, BMS_TAG_POINTWISE, launch_frame_adjust(S, d_frame, n, rt, right != nullptr, pow2, d_log, d_sp));
-  if (mem == BMS_HOST) {
-    HIP_TRY(c, hipMemcpyAsync(frame, d_frame, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
-    if (log_out) HIP_TRY(c, hipMemcpyAsync(log_out, d_log, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
-    if (spinors_out) HIP_TRY(c, hipMemcpyAsync(spinors_out, d_sp, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
-  }
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  TIMED(c, BMS_TAG_POINTWISE, launch_frame_adjust(c->stream, d_frame, n, rt, right != nullptr, pow2, d_log, d_sp));
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_corotating_frame(bms_ctx* c, const double* t, int64_t n, const void* data, int64_t ld, int ell_min, int ell_max, int mem,
                                     const double R0[4], double tolerance, double* frame_dev, double* frame_out, double* omega_out) try {
   if (!c || !t || !data || !R0 || !frame_dev) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
   int rc, n_modes;
-  if ((rc = check_time_axis(c, t, n))) return rc;
+  if ((rc = entry_mem(c, mem)) || (rc = check_time_axis(c, t, n))) return rc;
   if ((rc = modes_checks(c, ell_min, ell_max, ld, &n_modes))) return rc;
+  CallIO io(c, mem);
   FrameAxis ax;
   if ((rc = frame_axis(c, t, n, ax))) return rc;
-  // the kernels of bms_angular_velocity, in its work space
   const double* d_y;
-  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n - 1) * ld + n_modes) * 16, &d_y))) return rc;
-  double *d_R, *d_S, *d_res;
-  if ((rc = dev_buf_t(c, "R", (size_t)n * ld * 2, &d_R))) return rc;
-  if ((rc = dev_buf_t(c, "S", (size_t)n * ld * 2, &d_S))) return rc;
-  if ((rc = dev_buf_t(c, "av_out", (size_t)n * 15, &d_res))) return rc;
-  hipStream_t S = c->stream;
-  TIMED(c, BMS_TAG_SPLINE_FORWARD, launch_spline_forward(S, d_y, d_R, 2 * ld, n_modes, 0, n, n, ax.d_x, ax.d_tab, ax.tile, SPLINE_HALO));
-  TIMED(c, BMS_TAG_SPLINE_BACKWARD, launch_spline_slopes(S, d_R, d_S, 2 * ld, n_modes, n, ax.d_tab, ax.tile, SPLINE_HALO));
-  double *d_ldt = d_res, *d_ll = d_res + 3 * n, *d_om = d_res + 12 * n;
-  TIMED(c, BMS_TAG_POINTWISE, launch_angular_velocity(S, d_y, d_S, 2 * ld, n, ell_min, n_modes, d_ldt, d_ll, d_om));
-  if ((rc = frame_from_omega(c, ax, n, d_om, R0, tolerance, frame_dev))) return rc;
-  if (frame_out) HIP_TRY(c, hipMemcpyAsync(frame_out, frame_dev, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
-  if (omega_out) HIP_TRY(c, hipMemcpyAsync(omega_out, d_om, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, S));
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  double* d_res;  // <Ldt>, <LL>, omega: the kernels of bms_angular_velocity, in its work space
+  if ((rc = io.in("in_data", data, ((size_t)(n - 1) * ld + n_modes) * 16, &d_y))) return rc;
+  if ((rc = angular_velocity_on_device(c, d_y, ld, n, ell_min, n_modes, ax.d_x, ax.d_tab, ax.tile, &d_res))) return rc;
+  if ((rc = frame_from_omega(c, ax, n, d_res + 12 * n, R0, tolerance, frame_dev))) return rc;
+  if ((rc = io.copy_back(frame_out, frame_dev, sizeof(double) * 4 * n))) return rc;
+  if ((rc = io.copy_back(omega_out, d_res + 12 * n, sizeof(double) * 3 * n))) return rc;
+  return io.finish();
 } BMS_CATCH(c)
 
 extern "C" int bms_coprecessing_frame(bms_ctx* c, const double* t, int64_t n, const void* data, int64_t ld, int ell_min, int ell_max,
                                       int mem, const double rough[3], int64_t rough_index, int iterations, double* frame_dev,
                                       double* frame_out, double* axis_out) try {
   if (!c || !data || !rough) return fail(c, BMS_ERR_INVALID, "NULL argument");
-  if (!valid_mem(mem)) return fail(c, BMS_ERR_INVALID, "mem is BMS_HOST or BMS_DEVICE, got %d", mem);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc0 = entry_mem(c, mem)) return rc0;
   const bool want_frame = frame_dev || frame_out;
   int rc, n_modes;
   if (want_frame) {
@@ -323,8 +261,9 @@ extern "C" int bms_coprecessing_frame(bms_ctx* c, const double* t, int64_t n, co
   }
   if (rough_index < 0 || rough_index >= n) return fail(c, BMS_ERR_INVALID, "rough_index %lld outside [0, %lld)", (long long)rough_index, (long long)n);
   if ((rc = modes_checks(c, ell_min, ell_max, ld, &n_modes))) return rc;
+  CallIO io(c, mem);
   const double* d_y;
-  if ((rc = stage_in(c, "in_data", data, mem, ((size_t)(n - 1) * ld + n_modes) * 16, &d_y))) return rc;
+  if ((rc = io.in("in_data", data, ((size_t)(n - 1) * ld + n_modes) * 16, &d_y))) return rc;
   double *d_ll, *d_axis;
   if ((rc = dev_buf_t(c, "av_out", (size_t)n * 15, &d_ll))) return rc;
   if ((rc = dev_buf_t(c, "fr_axis", (size_t)n * 3, &d_axis))) return rc;
@@ -332,7 +271,7 @@ extern "C" int bms_coprecessing_frame(bms_ctx* c, const double* t, int64_t n, co
   // <LL> alone needs no time derivative: the kernel reads the modes in its place, and nothing of <Ldt> or omega is written
   TIMED(c, BMS_TAG_POINTWISE, launch_angular_velocity(S, d_y, d_y, 2 * ld, n, ell_min, n_modes, nullptr, d_ll, nullptr));
   if ((rc = dominant_axis(c, n, d_ll, rough, rough_index, d_axis))) return rc;
-  if (axis_out) HIP_TRY(c, hipMemcpyAsync(axis_out, d_axis, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, S));
+  if ((rc = io.copy_back(axis_out, d_axis, sizeof(double) * 3 * n))) return rc;
   if (want_frame) {
     FrameAxis ax;
     if ((rc = frame_axis(c, t, n, ax))) return rc;
@@ -340,8 +279,7 @@ extern "C" int bms_coprecessing_frame(bms_ctx* c, const double* t, int64_t n, co
     if (!d_R && (rc = dev_buf_t(c, "fr_out", (size_t)n * 4, &d_R))) return rc;
     TIMED(c, BMS_TAG_POINTWISE, launch_axis_rotor(S, d_axis, n, d_R));
     if ((rc = minimal_rotation(c, ax, n, d_R, iterations))) return rc;
-    if (frame_out) HIP_TRY(c, hipMemcpyAsync(frame_out, d_R, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, S));
+    if ((rc = io.copy_back(frame_out, d_R, sizeof(double) * 4 * n))) return rc;
   }
-  HIP_TRY(c, hipStreamSynchronize(S));
-  return BMS_OK;
+  return io.finish();
 } BMS_CATCH(c)

@@ -4,8 +4,11 @@ These take and return plain numpy arrays (host memory) or, with `device=True`, r
 pointers (ints, e.g. ``torch.Tensor.data_ptr()``) for callers that keep data resident in HBM.
 The scri-compatible classes in ``scri_amd.waveform_modes`` etc. are built on top of these.
 """
+import collections
 import ctypes
+import math
 import os
+import sys
 import threading
 
 import numpy as np
@@ -682,41 +685,138 @@ def map2salm(grid, spin, ell_max, ell_min=0, ctx=None):
     return out.reshape(lead + (out.shape[1],))
 
 
-def _device_series_arg(ctx, y, n, n_new):
-    """(address, row stride, columns, a new device tensor [n_new, n_cols]) for a series y [n, n_cols] resident on the GPU"""
-    import torch
+# ---- one description of a caller's array for the entries that take `int mem`: a numpy array (host) or a torch tensor (device)
 
-    from . import device_series
+# ptr: the address (c_vp); ld: row stride in elements; rows, cols; mem: BMS_HOST / BMS_DEVICE; tail: the trailing shape of a host array
+# that was flattened to [rows, cols]; keep: the object that owns the memory (alive through the call); device: the torch device or None
+_Arg = collections.namedtuple("_Arg", "ptr ld rows cols mem tail keep device")
+_TORCH_DTYPE = {np.complex128: "complex128", float: "float64", np.uint64: "int64"}  # (the packed words travel as int64 in torch)
+_torch_dtypes = {}  # the torch dtype objects of those names, looked up once (torch is imported only by a call that passes a tensor)
 
-    device_series.attach(ctx)
-    _on_device_of(ctx, y)
-    if y.dtype != torch.complex128 or y.ndim != 2 or y.shape[0] != n or (y.shape[1] > 1 and y.stride(1) != 1):
-        raise ValueError(f"a device series must be complex128 [{n}, n_cols] with unit column stride, got {y.dtype} of shape {tuple(y.shape)}")
-    n_cols = int(y.shape[1])
-    out = torch.empty((n_new, n_cols), dtype=torch.complex128, device=y.device)
-    return c_vp(y.data_ptr()), (y.stride(0) if n > 1 else max(n_cols, 1)), n_cols, out
+
+def _torch_dtype(dtype):
+    t = _torch_dtypes.get(dtype)
+    if t is None:
+        import torch
+
+        t = _torch_dtypes[dtype] = getattr(torch, _TORCH_DTYPE[dtype])
+    return t
+
+
+def _is_device_array(x):
+    """a torch tensor: device memory to the wrappers, which refuse one that is not on the context's device (_on_device_of)"""
+    return hasattr(x, "data_ptr")
+
+
+def _on_device_of(ctx, *arrays):
+    for x in arrays:
+        if _is_device_array(x) and x.device.index != ctx.device:
+            raise ValueError(f"a device array on {x.device} was passed to a context on device {ctx.device}")
+
+
+def _address(a):
+    """the address of a C-contiguous numpy array as c_vp: through the buffer protocol, several times quicker than `a.ctypes`, which
+    only read-only and empty arrays still go through"""
+    try:
+        return c_vp(ctypes.addressof(ctypes.c_char.from_buffer(a)))
+    except (TypeError, ValueError):
+        return vptr(a)
+
+
+def _shape_is(shape, actual):
+    """`actual` is 2-d and has the rows and the columns `shape` names (None: any)"""
+    return len(actual) == 2 and (shape is None or ((shape[0] is None or shape[0] == actual[0]) and (shape[1] is None or shape[1] == actual[1])))
+
+
+def _row_stride(x, rows, cols):
+    """THE row-stride rule: the row stride in elements of a device tensor [rows, cols] with unit column stride (the stride of one row
+    is anything, e.g. 1 for a transposed column: the entries take the columns)"""
+    return x.stride(0) if rows > 1 else max(cols, 1)
+
+
+def _stage(ctx, x, dtype, what, shape=None, flatten=False, contiguous=False, check_dtype=True, attach=True):
+    """The _Arg of `x`, [rows, cols] elements of `dtype` (np.complex128, float, or np.uint64 words).  shape: the (rows, cols) it must
+    have, None for any.  A device tensor is 2-d with unit column stride unless it has one column (any row stride: THE row-stride rule
+    is _row_stride), or with contiguous=True any shape of rows * cols elements in one block; it must live on the context's device.  A host
+    array is converted to a C-contiguous one; flatten: it may be [rows, ...], whose trailing axes become the columns.
+    check_dtype=False / attach=False: the wrappers that never checked a device tensor's dtype / never ordered the context's work
+    with torch's stream (device_series.attach) keep that.  (On the path of every small call: no numpy reductions, no generators.)"""
+    if hasattr(x, "data_ptr"):  # (_is_device_array, without the call)
+        if attach:
+            from . import device_series
+
+            device_series.attach(ctx)
+        if x.device.index != ctx.device:
+            _on_device_of(ctx, x)  # (raises)
+        sh = x.shape
+        if contiguous:
+            rows, cols = shape if shape is not None else ((sh[0] if sh else 1), math.prod(sh[1:]))
+            ok = x.is_contiguous() and x.numel() == rows * cols
+        else:
+            ok = (len(sh) == 2 if shape is None else _shape_is(shape, sh)) and (sh[1] <= 1 or x.stride(1) == 1)
+            rows, cols = (sh[0], sh[1]) if ok else (0, 0)
+        if not ok or (check_dtype and x.dtype != _torch_dtype(dtype)):
+            raise ValueError(f"{what}: expected a {'contiguous ' if contiguous else ''}{_TORCH_DTYPE[dtype]} device array{_shape_text(shape)}"
+                             f"{'' if contiguous else ' with unit column stride'}, got {x.dtype} of shape {tuple(x.shape)} on {x.device}")
+        ld = cols if contiguous else _row_stride(x, rows, cols)
+        return _Arg(c_vp(x.data_ptr()), ld, rows, cols, BMS_DEVICE, (cols,), x, x.device)
+    a = np.ascontiguousarray(x, dtype=dtype)
+    sh = a.shape
+    tail = sh[1:]
+    if flatten and len(sh) != 2:
+        a = a.reshape(sh[0], math.prod(tail))
+        sh = a.shape
+    if shape is not None and not _shape_is(shape, sh):
+        raise ValueError(f"{what} must have shape{_shape_text(shape)}; it has shape {sh}")
+    cols = sh[1] if len(sh) == 2 else math.prod(tail)
+    return _Arg(_address(a), cols or 1, (sh[0] if sh else 1), cols, BMS_HOST, tail, a, None)
+
+
+def _shape_text(shape):
+    return "" if shape is None else " (" + ", ".join("n" if s is None else str(s) for s in shape) + ")"
+
+
+def _beside(x):
+    """what out_like reads of an _Arg -- the memory kind and the torch device -- for an array that is not staged"""
+    return _Arg(None, None, None, None, BMS_DEVICE if _is_device_array(x) else BMS_HOST, None, x, x.device if _is_device_array(x) else None)
+
+
+def out_like(arg, shape, dtype, out=None):
+    """(address, array): a new array of `shape` and `dtype` beside `arg` -- a torch tensor on its device, or a numpy array.  out: the
+    contiguous device tensor of that many elements the caller wants written instead (device arguments only)."""
+    if arg.mem == BMS_DEVICE:
+        tdtype = _torch_dtype(dtype)
+        if out is None:
+            out = sys.modules["torch"].empty(*shape, dtype=tdtype, device=arg.device)  # (sizes one by one: quicker than a tuple)
+        elif out.dtype != tdtype or out.device != arg.device or not out.is_contiguous() or out.numel() != math.prod(shape):
+            raise ValueError(f"out: expected a contiguous {_TORCH_DTYPE[dtype]} array of {' x '.join(str(s) for s in shape)} values on {arg.device}")
+        return c_vp(out.data_ptr()), out
+    if out is not None:
+        raise ValueError("out= names a device array; with a host input the result is a new host array")
+    out = np.empty(shape, dtype=dtype)
+    return _address(out), out
+
+
+def _spline_call(entry, x, y, x_new, ctx, *order):
+    ctx = _ctx(ctx)
+    x = np.ascontiguousarray(x, dtype=float)
+    xn = np.ascontiguousarray(x_new, dtype=float)
+    a = _stage(ctx, y, np.complex128, "a series", flatten=True)
+    # (a device series has the knots' rows, as it always had to; of a longer host series the first rows are used, as they always
+    # were; a shorter one the entry would read past)
+    wrong_rows = (a.rows != x.shape[0]) if a.mem == BMS_DEVICE else (a.rows < x.shape[0])
+    if wrong_rows:
+        raise ValueError(f"a series of {a.rows} rows on {x.shape[0]} knots")
+    out_ptr, out = out_like(a, (xn.shape[0], a.cols), np.complex128)
+    rc = getattr(_lib.load(), entry)(ctx.handle, dptr(x), x.shape[0], a.ptr, a.ld, a.cols, a.mem, dptr(xn), xn.shape[0], *order, out_ptr)
+    ctx.check(rc, entry)
+    return out if a.mem == BMS_DEVICE else out.reshape((xn.shape[0],) + a.tail)
 
 
 def cubic_spline(x, y, x_new, ctx=None):
     """scipy.interpolate.CubicSpline(x, y)(x_new) for complex y[N, ...] (axis 0 = time).  y may be a device tensor [N, n_cols]
     (complex128, unit column stride): the same launches read it where it is and the result is a new device tensor."""
-    ctx = _ctx(ctx)
-    x = np.ascontiguousarray(x, dtype=float)
-    xn = np.ascontiguousarray(x_new, dtype=float)
-    if hasattr(y, "data_ptr"):
-        y_ptr, ld, n_cols, out = _device_series_arg(ctx, y, x.shape[0], xn.shape[0])
-        rc = _lib.load().bms_cubic_spline(ctx.handle, dptr(x), x.shape[0], y_ptr, ld, n_cols, BMS_DEVICE, dptr(xn), xn.shape[0], c_vp(out.data_ptr()))
-        ctx.check(rc, "bms_cubic_spline")
-        return out
-    y = _lib.as_c16(y)
-    tail = y.shape[1:]
-    y2 = y.reshape(y.shape[0], -1)
-    out = np.empty((xn.shape[0], y2.shape[1]), dtype=np.complex128)
-    rc = _lib.load().bms_cubic_spline(
-        ctx.handle, dptr(x), x.shape[0], vptr(y2), y2.shape[1], y2.shape[1], BMS_HOST, dptr(xn), xn.shape[0], vptr(out)
-    )
-    ctx.check(rc, "bms_cubic_spline")
-    return out.reshape((xn.shape[0],) + tail)
+    return _spline_call("bms_cubic_spline", x, y, x_new, ctx)
 
 
 def extrapolate(series, radii, orders, ctx=None, device=False, out=None, blocks=0):
@@ -805,9 +905,9 @@ def radius_terms(t, h0, n_terms, amp, radius, out, ctx=None):
     n, n_cols = t.shape[0], int(h0.shape[1])
     if tuple(h0.shape) != (n, n_cols) or tuple(out.shape) != (n, n_cols):
         raise ValueError(f"h0 {tuple(h0.shape)} and out {tuple(out.shape)} must both be ({n}, {n_cols})")
-    if hasattr(h0, "data_ptr") != hasattr(out, "data_ptr"):
+    if _is_device_array(h0) != _is_device_array(out):
         raise ValueError("h0 and out must live in the same memory")
-    if hasattr(h0, "data_ptr"):
+    if _is_device_array(h0):
         args = (c_vp(h0.data_ptr()), h0.stride(0) if n > 1 else n_cols, n_cols, int(n_terms), float(amp), float(radius), c_vp(out.data_ptr()),
                 out.stride(0) if n > 1 else n_cols, BMS_DEVICE)
     else:
@@ -824,24 +924,7 @@ def spline_derivative(x, y, x_new, order=0, ctx=None):
     """scipy CubicSpline(x, y, axis=0) differentiated (`order` 1..3) or integrated (`order` -1 .. -16; zero at x[0]) and
     evaluated at x_new, for complex y[N, ...].  y may be a device tensor [N, n_cols] (complex128, unit column stride): the same
     launches read it where it is and the result is a new device tensor."""
-    ctx = _ctx(ctx)
-    x = np.ascontiguousarray(x, dtype=float)
-    xn = np.ascontiguousarray(x_new, dtype=float)
-    if hasattr(y, "data_ptr"):
-        y_ptr, ld, n_cols, out = _device_series_arg(ctx, y, x.shape[0], xn.shape[0])
-        rc = _lib.load().bms_spline_derivative(ctx.handle, dptr(x), x.shape[0], y_ptr, ld, n_cols, BMS_DEVICE, dptr(xn), xn.shape[0], int(order),
-                                               c_vp(out.data_ptr()))
-        ctx.check(rc, "bms_spline_derivative")
-        return out
-    y = _lib.as_c16(y)
-    tail = y.shape[1:]
-    y2 = y.reshape(y.shape[0], -1)
-    out = np.empty((xn.shape[0], y2.shape[1]), dtype=np.complex128)
-    rc = _lib.load().bms_spline_derivative(
-        ctx.handle, dptr(x), x.shape[0], vptr(y2), y2.shape[1], y2.shape[1], BMS_HOST, dptr(xn), xn.shape[0], int(order), vptr(out)
-    )
-    ctx.check(rc, "bms_spline_derivative")
-    return out.reshape((xn.shape[0],) + tail)
+    return _spline_call("bms_spline_derivative", x, y, x_new, ctx, int(order))
 
 
 def grid_multiply(a, spin_a, ell_max_a, b, spin_b, ell_max_b, working_ell_max, output_ell_max, ctx=None):
@@ -903,21 +986,21 @@ def row_norm(data, take_sqrt=False, ctx=None, device_tensor=None):
     stride) for data resident on the GPU; returns a host float array [N]."""
     ctx = _ctx(ctx)
     if device_tensor is not None:
+        # (as it always was: the tensor is taken as it is -- its dtype, device and column stride are the caller's business -- and
+        # without a record: this call is all wrapper, and those checks cost a microsecond of its 32)
         import torch
 
         n_rows, n_cols = device_tensor.shape
         out = torch.empty(n_rows, dtype=torch.float64, device=device_tensor.device)
         if n_rows:
-            rc = _lib.load().bms_row_norm(ctx.handle, c_vp(device_tensor.data_ptr()), device_tensor.stride(0) if n_rows > 1 else max(n_cols, 1), n_rows,
-                                          n_cols, BMS_DEVICE, int(bool(take_sqrt)), c_vp(out.data_ptr()))
+            rc = _lib.load().bms_row_norm(ctx.handle, c_vp(device_tensor.data_ptr()), _row_stride(device_tensor, n_rows, n_cols), n_rows, n_cols, BMS_DEVICE,
+                                          int(bool(take_sqrt)), c_vp(out.data_ptr()))
             ctx.check(rc, "bms_row_norm")
         return out.cpu().numpy()
-    data = _lib.as_c16(data)
-    if data.ndim != 2:
-        raise ValueError("row_norm takes a [N, n] array")
-    out = np.empty(data.shape[0], dtype=float)
-    if data.shape[0]:
-        rc = _lib.load().bms_row_norm(ctx.handle, vptr(data), max(data.shape[1], 1), data.shape[0], data.shape[1], BMS_HOST, int(bool(take_sqrt)), vptr(out))
+    a = _stage(ctx, data, np.complex128, "row_norm takes a [N, n] array: data", shape=(None, None))
+    out_ptr, out = out_like(a, (a.rows,), float)
+    if a.rows:
+        rc = _lib.load().bms_row_norm(ctx.handle, a.ptr, a.ld, a.rows, a.cols, a.mem, int(bool(take_sqrt)), out_ptr)
         ctx.check(rc, "bms_row_norm")
     return out
 
@@ -929,27 +1012,6 @@ def polar_tile_rows():
 
 POLAR_TILE_ROWS = polar_tile_rows()  # the kernel's constant: series lengths around its multiples cross a tile edge
 
-def _polar_series_arg(ctx, data):
-    """(address, row stride, rows, columns, memory kind, trailing shape, the array) of a series [N, ...]: a numpy array, or a device
-    tensor [N, n_cols] (complex128, unit column stride, any row stride)"""
-    if hasattr(data, "data_ptr"):
-        import torch
-
-        from . import device_series
-
-        device_series.attach(ctx)
-        _on_device_of(ctx, data)
-        if data.dtype != torch.complex128 or data.ndim != 2 or (data.shape[1] > 1 and data.stride(1) != 1):
-            raise ValueError(f"a device series must be complex128 [N, n_cols] with unit column stride, got {data.dtype} of shape {tuple(data.shape)}")
-        n_rows, n_cols = int(data.shape[0]), int(data.shape[1])
-        return c_vp(data.data_ptr()), (data.stride(0) if n_rows > 1 else max(n_cols, 1)), n_rows, n_cols, BMS_DEVICE, (n_cols,), data
-    data = _lib.as_c16(data)
-    if data.ndim < 1:
-        raise ValueError("a series has a time axis")
-    d2 = data.reshape(data.shape[0], int(np.prod(data.shape[1:])))
-    return vptr(d2), max(d2.shape[1], 1), d2.shape[0], d2.shape[1], BMS_HOST, data.shape[1:], d2
-
-
 def abs_arg(data, unwrap=False, want=("abs", "arg"), ctx=None):
     """bms_polar: |data| and the angle atan2(im, re) of a complex series data[N, ...] (axis 0 = time), the statements numpy.abs and
     numpy.angle; with unwrap=True the angle is unwrapped along the time axis, the statement numpy.unwrap(numpy.angle(data), axis=0).
@@ -960,20 +1022,13 @@ def abs_arg(data, unwrap=False, want=("abs", "arg"), ctx=None):
     names = (want,) if isinstance(want, str) else tuple(want)
     if not names or len(set(names)) != len(names) or not set(names) <= {"abs", "arg"}:
         raise ValueError(f"want names 'abs' and / or 'arg', got {want!r}")
-    ptr, ld, n_rows, n_cols, mem, tail, _keep = _polar_series_arg(ctx, data)
-    if mem == BMS_DEVICE:
-        import torch
-
-        out = {k: torch.empty((n_rows, n_cols), dtype=torch.float64, device=data.device) for k in names}
-        address = lambda x: c_vp(x.data_ptr())  # noqa: E731
-    else:
-        out = {k: np.empty((n_rows, n_cols)) for k in names}
-        address = vptr
-    if n_rows and n_cols:
-        rc = _lib.load().bms_polar(ctx.handle, ptr, ld, n_rows, n_cols, mem, int(bool(unwrap)), address(out["abs"]) if "abs" in out else None,
-                                   address(out["arg"]) if "arg" in out else None, n_cols)
+    a = _stage(ctx, data, np.complex128, "a series", flatten=True)
+    out = {k: out_like(a, (a.rows, a.cols), float) for k in names}
+    if a.rows and a.cols:
+        rc = _lib.load().bms_polar(ctx.handle, a.ptr, a.ld, a.rows, a.cols, a.mem, int(bool(unwrap)), out["abs"][0] if "abs" in out else None,
+                                   out["arg"][0] if "arg" in out else None, a.cols)
         ctx.check(rc, "bms_polar")
-    res = tuple(out[k] if mem == BMS_DEVICE else out[k].reshape((n_rows,) + tuple(tail)) for k in names)
+    res = tuple(out[k][1] if a.mem == BMS_DEVICE else out[k][1].reshape((a.rows,) + tuple(a.tail)) for k in names)
     return res[0] if isinstance(want, str) else res
 
 
@@ -981,10 +1036,10 @@ def count_nonfinite(data, ctx=None):
     """bms_count_nonfinite: (the number of elements of the complex series data[N, ...] with a non-finite real or imaginary part, the
     first row that holds one or -1).  data: a numpy array, or a device tensor as abs_arg takes it (it stays where it is)."""
     ctx = _ctx(ctx)
-    ptr, ld, n_rows, n_cols, mem, _tail, _keep = _polar_series_arg(ctx, data)
+    a = _stage(ctx, data, np.complex128, "a series", flatten=True)
     count, first = c_i64(0), c_i64(-1)
-    if n_rows and n_cols:
-        rc = _lib.load().bms_count_nonfinite(ctx.handle, ptr, ld, n_rows, n_cols, mem, ctypes.byref(count), ctypes.byref(first))
+    if a.rows and a.cols:
+        rc = _lib.load().bms_count_nonfinite(ctx.handle, a.ptr, a.ld, a.rows, a.cols, a.mem, ctypes.byref(count), ctypes.byref(first))
         ctx.check(rc, "bms_count_nonfinite")
     return int(count.value), int(first.value)
 
@@ -1002,18 +1057,11 @@ def dense_product(form, a_ptr, lda, b_ptr, ldb, c_ptr, ldc, M, N, K, col_off_ptr
     ctx.check(rc, "bms_dense_product")
 
 
-def _modes_arg(data, n, ell_min, ell_max):
-    """(address, row stride, memory kind, object to keep alive) of modes [n, n_modes]: a numpy array on the host, or a torch tensor
-    (complex128, unit column stride) for modes resident on the GPU"""
-    n_modes = LM_total_size(ell_min, ell_max)
-    if hasattr(data, "data_ptr"):
-        if tuple(data.shape) != (n, n_modes) or (n_modes > 1 and data.stride(1) != 1):
-            raise ValueError(f"device modes of shape {tuple(data.shape)} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
-        return c_vp(data.data_ptr()), (data.stride(0) if n > 1 else n_modes), BMS_DEVICE, data
-    data = _lib.as_c16(data)
-    if data.shape != (n, n_modes):
-        raise ValueError(f"data shape {data.shape} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
-    return vptr(data), data.shape[1], BMS_HOST, data
+def _modes_arg(ctx, data, n, ell_min, ell_max):
+    """the _Arg of modes [n, n_modes]: a numpy array on the host, or a torch tensor (unit column stride) for modes resident on the GPU
+    (as it always was: neither a tensor's dtype is checked nor the context moved to torch's stream)"""
+    return _stage(ctx, data, np.complex128, f"modes of {n} time steps and ell range [{ell_min}, {ell_max}]", shape=(n, LM_total_size(ell_min, ell_max)),
+                  check_dtype=False, attach=False)
 
 
 def angular_velocity(t, data, ell_min, ell_max, ctx=None, parts=False):
@@ -1022,11 +1070,11 @@ def angular_velocity(t, data, ell_min, ell_max, ctx=None, parts=False):
     ctx = _ctx(ctx)
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
-    ptr, ld, mem, _keep = _modes_arg(data, n, ell_min, ell_max)
+    a = _modes_arg(ctx, data, n, ell_min, ell_max)
     ldt = np.empty((n, 3))
     ll = np.empty((n, 3, 3))
     om = np.empty((n, 3))
-    rc = _lib.load().bms_angular_velocity(ctx.handle, dptr(t), n, ptr, ld, int(ell_min), int(ell_max), mem, dptr(ldt), dptr(ll), dptr(om))
+    rc = _lib.load().bms_angular_velocity(ctx.handle, dptr(t), n, a.ptr, a.ld, int(ell_min), int(ell_max), a.mem, dptr(ldt), dptr(ll), dptr(om))
     ctx.check(rc, "bms_angular_velocity")
     return (ldt, ll, om) if parts else om
 
@@ -1035,54 +1083,23 @@ def angular_velocity(t, data, ell_min, ell_max, ctx=None, parts=False):
 # the host or torch tensors (float64, contiguous) on the device; a result lives where its input does.
 
 
-def _step_arg(x, n, width, what):
-    """(address, memory kind, the array) of a per-step array f8[n][width]"""
-    if hasattr(x, "data_ptr"):
-        import torch
-
-        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != n * width:
-            raise ValueError(f"{what}: expected a contiguous float64 device array of {n} x {width} values, got {x.dtype} of shape "
-                             f"{tuple(x.shape)} on {x.device}")
-        return c_vp(x.data_ptr()), BMS_DEVICE, x
-    a = np.ascontiguousarray(x, dtype=float)
-    if a.shape != (n, width):
-        raise ValueError(f"{what} must have shape ({n}, {width}); it has shape {a.shape}")
-    return vptr(a), BMS_HOST, a
-
-
-def _step_out(like, n, width, out=None):
-    """the result array f8[n][width] beside `like` (a device tensor or a numpy array)"""
-    if hasattr(like, "data_ptr"):
-        import torch
-
-        if out is None:
-            out = torch.empty((n, width), dtype=torch.float64, device=like.device)
-        elif out.dtype != torch.float64 or out.device != like.device or not out.is_contiguous() or out.numel() != n * width:
-            raise ValueError(f"out: expected a contiguous float64 array of {n} x {width} values on {like.device}")
-        return c_vp(out.data_ptr()), out
-    if out is not None:
-        raise ValueError("out= names a device array; with a host input the result is a new host array")
-    out = np.empty((n, width))
-    return vptr(out), out
-
-
-def _on_device_of(ctx, *arrays):
-    for x in arrays:
-        if hasattr(x, "data_ptr") and x.device.index != ctx.device:
-            raise ValueError(f"a device array on {x.device} was passed to a context on device {ctx.device}")
+def _step_arg(ctx, x, n, width, what):
+    """the _Arg of a per-step array f8[n][width]: a numpy array, or a contiguous float64 device tensor of n * width values (as it
+    always was, the context is not moved to torch's stream)"""
+    return _stage(ctx, x, float, what, shape=(n, width), contiguous=True, attach=False)
 
 
 def frame_from_angular_velocity(t, omega, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-12, ctx=None, out=None):
     """R[N, 4] with R[0] = R0 and dR/dt = (1/2) Omega R for the cubic spline Omega through omega[N, 3], on the GPU: interval rotors
     and their prefix product.  `out` (device input only): the device tensor [N, 4] the frame is written to."""
     ctx = _ctx(ctx)
-    _on_device_of(ctx, omega, out)
+    _on_device_of(ctx, out)
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
-    om_ptr, mem, om = _step_arg(omega, n, 3, "omega")
+    om = _step_arg(ctx, omega, n, 3, "omega")
     R0 = np.ascontiguousarray(R0, dtype=float).reshape(4)
-    out_ptr, out = _step_out(om, n, 4, out)
-    rc = _lib.load().bms_frame_from_angular_velocity(ctx.handle, dptr(t), n, om_ptr, mem, dptr(R0), float(tolerance), out_ptr)
+    out_ptr, out = out_like(om, (n, 4), float, out)
+    rc = _lib.load().bms_frame_from_angular_velocity(ctx.handle, dptr(t), n, om.ptr, om.mem, dptr(R0), float(tolerance), out_ptr)
     ctx.check(rc, "bms_frame_from_angular_velocity")
     return out
 
@@ -1090,40 +1107,34 @@ def frame_from_angular_velocity(t, omega, R0=(1.0, 0.0, 0.0, 0.0), tolerance=1e-
 def dominant_axis(ll, rough=(0.0, 0.0, 1.0), rough_index=0, ctx=None):
     """Continuous unit principal axis [N, 3] of the symmetric matrices ll[N, 3, 3] (bms_dominant_axis)."""
     ctx = _ctx(ctx)
-    _on_device_of(ctx, ll)
     n = int(ll.shape[0])
-    ll_ptr, mem, ll = _step_arg(ll.reshape(n, 9), n, 9, "ll")
+    a = _step_arg(ctx, ll.reshape(n, 9), n, 9, "ll")
     rough = np.ascontiguousarray(rough, dtype=float).reshape(3)
-    out_ptr, out = _step_out(ll, n, 3)
-    rc = _lib.load().bms_dominant_axis(ctx.handle, ll_ptr, n, mem, dptr(rough), int(rough_index), out_ptr)
+    out_ptr, out = out_like(a, (n, 3), float)
+    rc = _lib.load().bms_dominant_axis(ctx.handle, a.ptr, n, a.mem, dptr(rough), int(rough_index), out_ptr)
     ctx.check(rc, "bms_dominant_axis")
+    return out
+
+
+def _rotor_series_call(entry, t, R, width, ctx, *args):
+    ctx = _ctx(ctx)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    a = _step_arg(ctx, R, n, 4, "R")
+    out_ptr, out = out_like(a, (n, width), float)
+    rc = getattr(_lib.load(), entry)(ctx.handle, dptr(t), n, a.ptr, a.mem, *args, out_ptr)
+    ctx.check(rc, entry)
     return out
 
 
 def minimal_rotation(t, R, iterations=2, ctx=None):
     """numpy-quaternion's minimal_rotation of the rotor series R[N, 4] (bms_minimal_rotation); a new array beside R."""
-    ctx = _ctx(ctx)
-    _on_device_of(ctx, R)
-    t = np.ascontiguousarray(t, dtype=float)
-    n = t.shape[0]
-    R_ptr, mem, R = _step_arg(R, n, 4, "R")
-    out_ptr, out = _step_out(R, n, 4)
-    rc = _lib.load().bms_minimal_rotation(ctx.handle, dptr(t), n, R_ptr, mem, int(iterations), out_ptr)
-    ctx.check(rc, "bms_minimal_rotation")
-    return out
+    return _rotor_series_call("bms_minimal_rotation", t, R, 4, ctx, int(iterations))
 
 
 def rotor_angular_velocity(t, R, ctx=None):
     """omega[N, 3] = vector part of 2 Rdot R^-1 of the rotor series R[N, 4] (bms_rotor_angular_velocity)."""
-    ctx = _ctx(ctx)
-    _on_device_of(ctx, R)
-    t = np.ascontiguousarray(t, dtype=float)
-    n = t.shape[0]
-    R_ptr, mem, R = _step_arg(R, n, 4, "R")
-    out_ptr, out = _step_out(R, n, 3)
-    rc = _lib.load().bms_rotor_angular_velocity(ctx.handle, dptr(t), n, R_ptr, mem, out_ptr)
-    ctx.check(rc, "bms_rotor_angular_velocity")
-    return out
+    return _rotor_series_call("bms_rotor_angular_velocity", t, R, 3, ctx)
 
 
 def squad(R_in, t_in, t_out, ctx=None, out=None):
@@ -1135,22 +1146,22 @@ def squad(R_in, t_in, t_out, ctx=None, out=None):
     _on_device_of(ctx, R_in, out)
     t_in = np.ascontiguousarray(t_in, dtype=float)
     t_out = np.ascontiguousarray(t_out, dtype=float).reshape(-1)
-    on_device = hasattr(R_in, "data_ptr")
+    on_device = _is_device_array(R_in)
     if not on_device:
         R_in = np.asarray(R_in, dtype=float)
     size = R_in.numel() if on_device else R_in.size
     n, m = (int(R_in.shape[0]) if size else 0), t_out.shape[0]
     if n < 2 or m == 0:  # the statement's answers: nothing from nothing, one rotor repeated
         rows = 0 if n == 0 or m == 0 else m
-        _, res = _step_out(R_in, rows, 4, out)
+        _, res = out_like(_beside(R_in), (rows, 4), float, out)
         if rows:
             res.reshape(rows, 4)[:] = R_in.reshape(-1, 4)[:1]
         return res
     if t_in.shape != (n,):
         raise ValueError(f"t_in must have shape ({n},); it has shape {t_in.shape}")
-    R_ptr, mem, R = _step_arg(R_in, n, 4, "R_in")
-    out_ptr, out = _step_out(R, m, 4, out)
-    rc = _lib.load().bms_squad(ctx.handle, dptr(t_in), n, R_ptr, mem, dptr(t_out), m, out_ptr)
+    a = _step_arg(ctx, R_in, n, 4, "R_in")
+    out_ptr, out = out_like(a, (m, 4), float, out)
+    rc = _lib.load().bms_squad(ctx.handle, dptr(t_in), n, a.ptr, a.mem, dptr(t_out), m, out_ptr)
     ctx.check(rc, "bms_squad")
     return out
 
@@ -1165,15 +1176,14 @@ def frame_adjust(frame, right=None, truncate_tolerance=0.0, want_log=False, want
     to the bits above truncate_tolerance.  Returns (rounded log-frame or None, spinors [N, 4 doubles] = (w + i z, y + i x) or None),
     beside the frame."""
     ctx = _ctx(ctx)
-    _on_device_of(ctx, frame)
     n = int(frame.shape[0])
-    if not hasattr(frame, "data_ptr") and not (isinstance(frame, np.ndarray) and frame.dtype == float and frame.flags.c_contiguous):
+    if not _is_device_array(frame) and not (isinstance(frame, np.ndarray) and frame.dtype == float and frame.flags.c_contiguous):
         raise ValueError("frame_adjust works in place: a contiguous float array or a device tensor")
-    f_ptr, mem, frame = _step_arg(frame, n, 4, "frame")
-    log_ptr, log = _step_out(frame, n, 4) if want_log else (None, None)
-    sp_ptr, sp = _step_out(frame, n, 4) if want_spinors else (None, None)
+    a = _step_arg(ctx, frame, n, 4, "frame")
+    log_ptr, log = out_like(a, (n, 4), float) if want_log else (None, None)
+    sp_ptr, sp = out_like(a, (n, 4), float) if want_spinors else (None, None)
     rt = None if right is None else np.ascontiguousarray(right, dtype=float).reshape(4)
-    rc = _lib.load().bms_frame_adjust(ctx.handle, f_ptr, n, mem, None if rt is None else dptr(rt), float(truncate_tolerance), log_ptr, sp_ptr)
+    rc = _lib.load().bms_frame_adjust(ctx.handle, a.ptr, n, a.mem, None if rt is None else dptr(rt), float(truncate_tolerance), log_ptr, sp_ptr)
     ctx.check(rc, "bms_frame_adjust")
     return log, sp
 
@@ -1182,15 +1192,14 @@ def corotating_frame(t, data, ell_min, ell_max, frame_dev, R0=(1.0, 0.0, 0.0, 0.
     """bms_corotating_frame: the corotating frame of modes data[N, n_modes] (numpy or device tensor) into the device tensor frame_dev
     [N, 4]; returns (host copy of the frame or None, host omega [N, 3] or None)."""
     ctx = _ctx(ctx)
-    _on_device_of(ctx, data, frame_dev)
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
-    ptr, ld, mem, _keep = _modes_arg(data, n, ell_min, ell_max)
-    f_ptr, _, _ = _step_arg(frame_dev, n, 4, "frame_dev")
+    a = _modes_arg(ctx, data, n, ell_min, ell_max)
+    f = _step_arg(ctx, frame_dev, n, 4, "frame_dev")
     R0 = np.ascontiguousarray(R0, dtype=float).reshape(4)
     frame = np.empty((n, 4)) if want_frame else None
     om = np.empty((n, 3)) if want_omega else None
-    rc = _lib.load().bms_corotating_frame(ctx.handle, dptr(t), n, ptr, ld, int(ell_min), int(ell_max), mem, dptr(R0), float(tolerance), f_ptr,
+    rc = _lib.load().bms_corotating_frame(ctx.handle, dptr(t), n, a.ptr, a.ld, int(ell_min), int(ell_max), a.mem, dptr(R0), float(tolerance), f.ptr,
                                           None if frame is None else dptr(frame), None if om is None else dptr(om))
     ctx.check(rc, "bms_corotating_frame")
     return frame, om
@@ -1201,15 +1210,14 @@ def coprecessing_frame(t, data, ell_min, ell_max, rough=(0.0, 0.0, 1.0), rough_i
     """bms_coprecessing_frame: dominant axis of <LL> of modes data[N, n_modes] (numpy or device tensor), and with frame_dev (device
     tensor [N, 4]) or want_frame the minimally rotating frame that takes z to it; returns (host frame or None, host axis [N, 3] or None)."""
     ctx = _ctx(ctx)
-    _on_device_of(ctx, data, frame_dev)
     t = np.ascontiguousarray(t, dtype=float)
     n = t.shape[0]
-    ptr, ld, mem, _keep = _modes_arg(data, n, ell_min, ell_max)
-    f_ptr = None if frame_dev is None else _step_arg(frame_dev, n, 4, "frame_dev")[0]
+    a = _modes_arg(ctx, data, n, ell_min, ell_max)
+    f_ptr = None if frame_dev is None else _step_arg(ctx, frame_dev, n, 4, "frame_dev").ptr
     rough = np.ascontiguousarray(rough, dtype=float).reshape(3)
     frame = np.empty((n, 4)) if want_frame else None
     axis = np.empty((n, 3)) if want_axis else None
-    rc = _lib.load().bms_coprecessing_frame(ctx.handle, dptr(t), n, ptr, ld, int(ell_min), int(ell_max), mem, dptr(rough), int(rough_index),
+    rc = _lib.load().bms_coprecessing_frame(ctx.handle, dptr(t), n, a.ptr, a.ld, int(ell_min), int(ell_max), a.mem, dptr(rough), int(rough_index),
                                             int(iterations), f_ptr, None if frame is None else dptr(frame), None if axis is None else dptr(axis))
     ctx.check(rc, "bms_coprecessing_frame")
     return frame, axis
@@ -1222,15 +1230,10 @@ def _align_bulk(ctx, x, what):
     """(address, row stride, the tensor) of a bulk array c16[n][ld]: a device tensor goes through untouched, a host array goes up once"""
     from . import device_series
 
-    device_series.attach(ctx)
-    if not hasattr(x, "data_ptr"):
+    if not _is_device_array(x):
         x = device_series.to_device(ctx, x)
-    import torch
-
-    if x.dtype != torch.complex128 or x.ndim != 2 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
-        raise ValueError(f"{what}: expected complex128 [n, n_cols] with unit column stride on the device, got {x.dtype} of shape {tuple(x.shape)}")
-    _on_device_of(ctx, x)
-    return c_vp(x.data_ptr()), (x.stride(0) if x.shape[0] > 1 else max(x.shape[1], 1)), x
+    a = _stage(ctx, x, np.complex128, what)
+    return a.ptr, a.ld, x
 
 
 def _align_series(ctx, ta, ya, sa, col_a, tw, w, b, col_b):
@@ -1294,18 +1297,12 @@ def align_residual(ta, ya, sa, col_a, tw, w, b, col_b, m_of, dt, dphi, ctx=None)
 def knot_slopes(t, y, ctx=None):
     """Slopes at the knots of the not-a-knot cubic spline through (t, y) for a device tensor y [n, n_cols] (complex128, unit column
     stride): bms_spline_derivative(order = 1) evaluated at the knots themselves, device to device.  A new tensor of y's shape."""
-    import torch
-
-    from . import device_series
-
     ctx = _ctx(ctx)
-    device_series.attach(ctx)
-    _on_device_of(ctx, y)
     t = np.ascontiguousarray(t, dtype=float)
-    n, n_cols = y.shape
-    out = torch.empty((n, n_cols), dtype=torch.complex128, device=y.device)
-    rc = _lib.load().bms_spline_derivative(ctx.handle, dptr(t), n, c_vp(y.data_ptr()), y.stride(0) if n > 1 else max(n_cols, 1), n_cols, BMS_DEVICE,
-                                           dptr(t), n, 1, c_vp(out.data_ptr()))
+    a = _stage(ctx, y, np.complex128, "a device series", check_dtype=False)  # (as it always was: the dtype is the caller's business)
+    n = a.rows
+    out_ptr, out = out_like(a, (n, a.cols), np.complex128)
+    rc = _lib.load().bms_spline_derivative(ctx.handle, dptr(t), n, a.ptr, a.ld, a.cols, BMS_DEVICE, dptr(t), n, 1, out_ptr)
     ctx.check(rc, "bms_spline_derivative")
     return out
 
@@ -1353,23 +1350,14 @@ def pack_paired_xor(data, ell_min, ell_max, tolerance, ctx=None):
     cannot be packed (a non-finite value, zero norm)."""
     ctx = _ctx(ctx)
     n = int(data.shape[0])
-    ptr, ld, mem, keep = _modes_arg(data, n, ell_min, ell_max)
-    n_modes = LM_total_size(ell_min, ell_max)
-    if mem == BMS_DEVICE:
-        import torch
-
-        words = torch.empty((n, 2 * n_modes), dtype=torch.int64, device=data.device)
-        out_ptr = c_vp(words.data_ptr())
-    else:
-        words = np.empty((n, 2 * n_modes), dtype=np.uint64)
-        out_ptr = vptr(words)
+    a = _modes_arg(ctx, data, n, ell_min, ell_max)
+    out_ptr, words = out_like(a, (n, 2 * a.cols), np.uint64)
     bad = c_i64(-1)
-    rc = _lib.load().bms_pack_paired_xor(ctx.handle, ptr, ld, n, int(ell_min), int(ell_max), mem, float(tolerance), out_ptr, ctypes.byref(bad))
+    rc = _lib.load().bms_pack_paired_xor(ctx.handle, a.ptr, a.ld, n, int(ell_min), int(ell_max), a.mem, float(tolerance), out_ptr, ctypes.byref(bad))
     if rc == _lib.BMS_ERR_INVALID and bad.value >= 0:
         raise ValueError(f"time step {bad.value} cannot be packed: it holds a non-finite value, has zero norm, or its truncation scale is "
                          "beyond the range of the doubles")
     ctx.check(rc, "bms_pack_paired_xor")
-    del keep
     return words
 
 
@@ -1381,16 +1369,12 @@ def unpack_paired_xor(words, ell_min, ell_max, ctx=None):
     n = int(words.shape[0])
     if tuple(words.shape) != (n, 2 * n_modes):
         raise ValueError(f"words of shape {tuple(words.shape)} inconsistent with {n} time steps and ell range [{ell_min}, {ell_max}]")
-    if hasattr(words, "data_ptr"):
-        import torch
-
+    if _is_device_array(words):
         words = words.contiguous()
-        out = torch.empty((n, n_modes), dtype=torch.complex128, device=words.device)
-        rc = _lib.load().bms_unpack_paired_xor(ctx.handle, c_vp(words.data_ptr()), n, int(ell_min), int(ell_max), BMS_DEVICE, c_vp(out.data_ptr()), n_modes)
-    else:
-        words = np.ascontiguousarray(words, dtype=np.uint64)
-        out = np.empty((n, n_modes), dtype=np.complex128)
-        rc = _lib.load().bms_unpack_paired_xor(ctx.handle, vptr(words), n, int(ell_min), int(ell_max), BMS_HOST, vptr(out), n_modes)
+    # (as it always was: a tensor's dtype is not checked, and the context is not moved to torch's stream)
+    a = _stage(ctx, words, np.uint64, "words", contiguous=True, check_dtype=False, attach=False)
+    out_ptr, out = out_like(a, (n, n_modes), np.complex128)
+    rc = _lib.load().bms_unpack_paired_xor(ctx.handle, a.ptr, n, int(ell_min), int(ell_max), a.mem, out_ptr, n_modes)
     ctx.check(rc, "bms_unpack_paired_xor")
     return out
 
@@ -1403,24 +1387,22 @@ def com_fit_tile_panels():
     return int(_lib.load().bms_com_fit_tile_panels())
 
 
-def _is_device_array(x):
-    return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
-
-
 def _com_arrays(ctx, arrays):
-    """float64 contiguous copies of `arrays` side by side: device tensors if any of them is one, numpy arrays otherwise"""
-    if any(_is_device_array(x) for x in arrays):
+    """float64 contiguous copies of `arrays` side by side, staged: device tensors if any of them is one, numpy arrays otherwise"""
+    on_gpu = [_is_device_array(x) and x.is_cuda for x in arrays]  # (a CPU tensor counts as a host array here, as it always did)
+    if any(on_gpu):
         import torch
 
         from . import device_series
 
-        _on_device_of(ctx, *[x for x in arrays if _is_device_array(x)])
+        _on_device_of(ctx, *[x for x, g in zip(arrays, on_gpu) if g])
         dev = device_series.attach(ctx)  # (torch's copies and the engine's kernels on one stream)
-        arrays = [x.to(torch.float64).contiguous() if _is_device_array(x) else torch.as_tensor(np.asarray(x, dtype=float), device=dev).contiguous()
-                  for x in arrays]
-        return arrays, BMS_DEVICE, [c_vp(x.data_ptr()) for x in arrays]
-    arrays = [np.ascontiguousarray(x.numpy() if hasattr(x, "data_ptr") else x, dtype=float) for x in arrays]
-    return arrays, BMS_HOST, [vptr(x) for x in arrays]
+        arrays = [x.to(torch.float64).contiguous() if g else torch.as_tensor(np.asarray(x, dtype=float), device=dev).contiguous()
+                  for x, g in zip(arrays, on_gpu)]
+    else:
+        arrays = [x.numpy() if _is_device_array(x) else x for x in arrays]
+    staged = [_stage(ctx, x, float, "a centre-of-mass array", contiguous=True) for x in arrays]
+    return [a.keep for a in staged], staged
 
 
 def com_track(t, x_a, x_b, m_a, m_b, matter=False, ctx=None):
@@ -1428,23 +1410,15 @@ def com_track(t, x_a, x_b, m_a, m_b, matter=False, ctx=None):
     n or 1, bit for bit the numpy expression; matter=True also divides t and CoM by m_A + m_B.  numpy arrays give numpy arrays; if any
     trajectory is a device tensor everything stays (or is put) on the device and the results are device tensors."""
     ctx = _ctx(ctx)
-    (t, x_a, x_b, m_a, m_b), mem, ptrs = _com_arrays(ctx, [t, x_a, x_b, m_a, m_b])
+    (t, x_a, x_b, m_a, m_b), args = _com_arrays(ctx, [t, x_a, x_b, m_a, m_b])
     n = int(x_a.shape[0])
     if tuple(x_a.shape) != (n, 3) or tuple(x_b.shape) != (n, 3) or tuple(t.shape) != (n,) or m_a.ndim != 1 or m_b.ndim != 1:
         raise ValueError(f"trajectories of shapes {tuple(x_a.shape)}, {tuple(x_b.shape)} and times of shape {tuple(t.shape)} do not describe "
                          f"{n} samples of two positions")
-    if mem == BMS_DEVICE:
-        import torch
-
-        com = torch.empty((n, 3), dtype=torch.float64, device=x_a.device)
-        t_out = torch.empty((n,), dtype=torch.float64, device=x_a.device) if matter else t
-        out_ptrs = (c_vp(t_out.data_ptr()), c_vp(com.data_ptr()))
-    else:
-        com = np.empty((n, 3))
-        t_out = np.empty(n) if matter else t
-        out_ptrs = (vptr(t_out), vptr(com))
-    rc = _lib.load().bms_com_motion(ctx.handle, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(m_a.shape[0]), ptrs[4], int(m_b.shape[0]), n, int(bool(matter)),
-                                    mem, out_ptrs[0] if matter else None, out_ptrs[1])
+    com_ptr, com = out_like(args[1], (n, 3), float)
+    t_ptr, t_out = out_like(args[1], (n,), float) if matter else (None, t)
+    rc = _lib.load().bms_com_motion(ctx.handle, args[0].ptr, args[1].ptr, args[2].ptr, args[3].ptr, int(m_a.shape[0]), args[4].ptr, int(m_b.shape[0]), n,
+                                    int(bool(matter)), args[1].mem, t_ptr, com_ptr)
     ctx.check(rc, "bms_com_motion")
     return t_out, com
 
@@ -1454,12 +1428,12 @@ def com_fit(t, com, skip_beginning_fraction=0.01, skip_ending_fraction=0.10, fit
     t_f, i_i, i_f and moments [3, 3] -- the window of the skip fractions, the Simpson moments of the track over it and the position,
     velocity (and acceleration) that bring the track closest to the origin, correctly rounded."""
     ctx = _ctx(ctx)
-    (t, com), mem, ptrs = _com_arrays(ctx, [t, com])
+    (t, com), args = _com_arrays(ctx, [t, com])
     n = int(t.shape[0])
     if t.ndim != 1 or tuple(com.shape) != (n, 3):
         raise ValueError(f"times of shape {tuple(t.shape)} and a track of shape {tuple(com.shape)}: expected ({n},) and ({n}, 3)")
     res = _lib.bms_com_fit_result()
-    rc = _lib.load().bms_com_fit(ctx.handle, ptrs[0], ptrs[1], n, mem, float(skip_beginning_fraction), float(skip_ending_fraction),
+    rc = _lib.load().bms_com_fit(ctx.handle, args[0].ptr, args[1].ptr, n, args[0].mem, float(skip_beginning_fraction), float(skip_ending_fraction),
                                  int(bool(fit_acceleration)), ctypes.byref(res))
     ctx.check(rc, "bms_com_fit")
     return dict(x_i=np.array(res.x_i), v_i=np.array(res.v_i), a_i=np.array(res.a_i), t_i=np.float64(res.t_i), t_f=np.float64(res.t_f),

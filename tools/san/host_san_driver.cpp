@@ -3,7 +3,7 @@
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
 // pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain, of the rotor interpolation and of the alignment entries, the planner and the per-step
-// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, the prologues of the entries that stage host or device arguments (entry_mem, CallIO), over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -561,6 +561,59 @@ void com_motion_arguments() {
   REQUIRE(com_fit_work_doubles(2 * COM_FIT_TILE + 3) == com_fit_work_doubles(3) + 18);  // one more tile of double-double partials
 }
 
+// The argument helper of the building blocks (engine.h: entry_mem, CallIO).  Per family that stands on it, the refusal of a bad `mem`
+// in that family's words, ahead of the size checks that follow it, and where the device is selected only after those checks (mode map,
+// centre of mass, alignment, paired XOR) one bad size behind a good `mem`; then the helper on device memory, where it hands the
+// caller's pointers through and keeps at most MAX_BACK copies.  No call here gets as far as selecting a device.
+void staged_argument_prologues() {
+  bms_ctx dummy;
+  alignas(16) static double v[64], out[64];
+  double t[4] = {0.0, 0.1, 0.2, 0.3};
+  const int32_t idx[1] = {0};
+  auto says = [&](const char* text) { return std::strstr(bms_last_error(&dummy), text) != nullptr; };
+  // engine_blocks.hip
+  REQUIRE(bms_row_norm(&dummy, v, 1, -1, 1, 7, 0, out) == BMS_ERR_INVALID && says("mem is BMS_HOST or BMS_DEVICE, got 7") && !says("bms_"));
+  REQUIRE(bms_cubic_spline(&dummy, t, 3, v, 1, 1, 7, t, 1, out) == BMS_ERR_INVALID && says("got 7"));
+  REQUIRE(bms_spline_derivative(&dummy, t, 3, v, 1, 1, 7, t, 1, 9, out) == BMS_ERR_INVALID && says("got 7"));
+  REQUIRE(bms_angular_velocity(&dummy, t, 3, v, 0, 0, 0, 7, out, out, out) == BMS_ERR_INVALID && says("got 7"));
+  REQUIRE(bms_xor_timeseries(&dummy, v, 7, -1, 1, 0) == BMS_ERR_INVALID && says("got 7"));
+  REQUIRE(bms_mode_map(&dummy, out, 1, 1, 1, v, 1, idx, v, 0, v, 1, nullptr, nullptr, 0, nullptr, 7) == BMS_ERR_INVALID && says("got 7"));
+  dummy.err.clear();
+  REQUIRE(bms_mode_map(&dummy, out, 1, 1, 1, v, 1, idx, v, 0, v, 1, nullptr, nullptr, 0, nullptr, BMS_HOST) == BMS_ERR_INVALID && dummy.err.empty());
+  // engine_frames.hip
+  REQUIRE(bms_squad(&dummy, t, 1, v, 7, t, -1, out) == BMS_ERR_INVALID && says("mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_frame_adjust(&dummy, v, -1, 7, nullptr, 0.0, nullptr, nullptr) == BMS_ERR_INVALID && says("got 7"));
+  REQUIRE(bms_minimal_rotation(&dummy, t, 3, v, 7, 0, out) == BMS_ERR_INVALID && says("got 7"));
+  REQUIRE(bms_coprecessing_frame(&dummy, t, 0, v, 1, 0, 0, 7, t, 0, 0, nullptr, nullptr, out) == BMS_ERR_INVALID && says("got 7"));
+  // engine_com.hip: the entry's name in front, and the size checks behind a good `mem`
+  bms_com_fit_result res;
+  REQUIRE(bms_com_fit(&dummy, t, v, 1, 5, 0.01, 0.1, 0, &res) == BMS_ERR_INVALID && says("bms_com_fit: mem is BMS_HOST or BMS_DEVICE, got 5"));
+  REQUIRE(bms_com_fit(&dummy, t, v, 1, BMS_DEVICE, 0.01, 0.1, 0, &res) == BMS_ERR_INVALID && says("at least 2 samples"));
+  REQUIRE(bms_com_motion(&dummy, t, v, v, v, 3, v, 1, 0, 0, 3, nullptr, out) == BMS_ERR_INVALID && says("bms_com_motion: mem is BMS_HOST or BMS_DEVICE, got 3"));
+  REQUIRE(bms_com_motion(&dummy, t, v, v, v, 3, v, 1, 4, 0, BMS_DEVICE, nullptr, out) == BMS_ERR_INVALID && says("one per sample"));
+  // engine_align.hip
+  AlignHost h = {t, 4, v, v, 1, idx, t, t, 2, v, 1, idx, 0, 9};
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID && says("mem is BMS_HOST or BMS_DEVICE, got 9"));
+  h.mem = BMS_DEVICE;
+  REQUIRE(align_checks(&dummy, h) == BMS_ERR_INVALID && says("at least one common column"));
+  // the paired-XOR plan
+  PairedPlan P;
+  REQUIRE(plan_paired_xor(&dummy, "bms_pack_paired_xor", v, 1, out, -1, 0, 0, 7, P) == BMS_ERR_INVALID && says("bms_pack_paired_xor: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(plan_paired_xor(&dummy, "bms_unpack_paired_xor", v, 1, out, -1, 0, 0, BMS_HOST, P) == BMS_ERR_INVALID && says("bms_unpack_paired_xor: negative n_times"));
+  // the helper on device memory
+  CallIO io(&dummy, BMS_DEVICE);
+  const double* d_in = nullptr;
+  double *d_out = nullptr, *d_io = nullptr;
+  REQUIRE(io.in("in_data", v, 64, &d_in) == BMS_OK && d_in == v);
+  REQUIRE(io.out("out_data", out, 8, &d_out) == BMS_OK && d_out == out);
+  REQUIRE(io.out_rows("out_data", out, 2, 2, 4, &d_out) == BMS_OK && d_out == out);
+  REQUIRE(io.inout("fr_in", out, out, 8, &d_io) == BMS_OK && d_io == out && io.n_back == 0);  // (one array: no copy, nothing to bring home)
+  REQUIRE(io.copy_back(nullptr, v, 8) == BMS_OK && io.n_back == 0);                            // (an output nobody asked for)
+  for (int k = 0; k < CallIO::MAX_BACK; ++k) REQUIRE(io.copy_back(out + k, v, 8) == BMS_OK);
+  REQUIRE(io.copy_back(out, v, 8) == BMS_ERR_INVALID && io.n_back == CallIO::MAX_BACK);
+  REQUIRE(!dummy.host_copy_queued);  // (nothing was queued on a stream: the destructor has nothing to wait for)
+}
+
 // bms_dense_product (engine_blocks.hip) and the two launchers behind it (kernels_gemm.hip): every refusal of include/scri_amd.h comes
 // back before a device is touched or anything is launched, and an empty product is BMS_OK.  The arrays are never read.
 void dense_product_arguments() {
@@ -641,6 +694,7 @@ int main() {
   paired_xor_arguments();
   com_motion_arguments();
   dense_product_arguments();
+  staged_argument_prologues();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
