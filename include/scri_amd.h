@@ -606,6 +606,35 @@ int bms_com_fit(bms_ctx* ctx, const double* t, const double* com, int64_t n, int
 /* panels (two intervals each) behind one partial sum of the moments (tests place window lengths around it); a size, not a status */
 int64_t bms_com_fit_tile_panels(void);
 
+/* ---- fluxes of energy, momentum, angular momentum and boost (scri/flux.py:182-798) in one pass over the modes ---------------------
+ * bms_poincare_fluxes: energy f8[n] (:206-208), momentum f8[n][3] (:329-340), angular f8[n][3] (:428-439) and boost f8[n][3] (:652-745,
+ * with the signs of its code, not of its docstring) of the strain h and its time derivative hdot, c16[n_times][ld_h] and
+ * c16[n_times][ld_hdot] holding l = ell_min .. ell_max, ell_min >= 2.  h, hdot and the outputs live in `mem`; t is a host f8[n_times].
+ * Any output may be NULL: it is neither computed nor written (at least one is asked for).  h may be NULL when neither `angular` nor
+ * `boost` is asked for, t when `boost` is not.  Every sum <a|M|b> of the reference runs over a banded operator; with the ladder factors
+ * of eth / ethbar folded into three real coefficient sets per (column, neighbour), built in long double and kept per context and l range,
+ * only h and hdot are read, once.  The sum of a time step is taken in an order that depends on nothing but the l range: two calls give
+ * the same bits, a slice of the time steps gives the bits of the whole call, and an output does not depend on which others are asked for.
+ * BMS_ERR_INVALID: a NULL that is needed, ell_max < ell_min, a row stride below the number of modes, negative n_times, a bad mem,
+ * misaligned device arrays; BMS_ERR_UNSUPPORTED: ell_min < 2, an l range whose rows do not fit in LDS.  n_times == 0 writes nothing. */
+int bms_poincare_fluxes(bms_ctx* ctx, const double* t, const void* h, int64_t ld_h, const void* hdot, int64_t ld_hdot, int64_t n_times,
+                        int ell_min, int ell_max, int mem, double* energy, double* momentum, double* angular, double* boost);
+/* out[t] = sum_e op(a[t][rows_e]) values_e b[t][cols_e], op = complex conjugation if conj_a else the identity: the reference's
+ * sparse_expectation_value (scri/flux.py:41-78) for any operator given as triplets.  rows, cols int32[n_el] and values c16[n_el] are
+ * host arrays; a c16[n_times][ld_a], b c16[n_times][ld_b] (n_cols columns used) and out c16[n_times] live in `mem`.  The sum has a fixed
+ * order (element e on lane e mod 64, lane sums in element order, a butterfly over the lanes).  BMS_ERR_INVALID: a NULL argument, a row
+ * stride below n_cols, negative sizes, and an index outside [0, n_cols) -- found on the host before anything is launched. */
+int bms_expectation_values(bms_ctx* ctx, const void* a, int64_t ld_a, int conj_a, const void* b, int64_t ld_b, int64_t n_times, int n_cols,
+                           const int32_t* rows, const int32_t* cols, const void* values, int64_t n_el, int mem, void* out);
+/* how bms_poincare_fluxes runs n_modes columns on the current device: shape[0] time steps per pass of one workgroup, shape[1] workgroups
+ * at most, shape[2] != 0 if the coefficient tables are held in LDS (else they are read through L2).  Returns shape[0], or 0 if the rows of
+ * one time step do not fit in LDS (tests place series lengths around these sizes); sizes, not a status */
+int64_t bms_flux_launch_shape(int n_modes, int64_t shape[3]);
+/* pure host routine: the coefficient tables of l = ell_min .. ell_max as the kernel reads them, image_out f8[30][n_modes]: row 3 k + set
+ * for neighbour k = 3 (dl + 1) + (mu + 1) of a column (l, m) -- the row (l + dl, m + mu) -- and set 0 (chi at s = -2), 1 (the pair
+ * hdot, h), 2 (the pair h, hdot); rows 27, 28: sqrt((l - m)(l + m + 1)), sqrt((l + m)(l - m + 1)); row 29: l. */
+int bms_flux_coefficients(int ell_min, int ell_max, double* image_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ from . import sample_waveforms  # noqa: E402,F401
 from . import extrapolation  # noqa: E402,F401
 from .extrapolation import _Extrapolate, extrapolate_waveforms  # noqa: E402,F401
 from .flux import energy_flux, momentum_flux, angular_momentum_flux, boost_flux, poincare_fluxes  # noqa: E402,F401
+from .flux import swsh_indices_to_matrix_indices, sparse_expectation_value, matrix_expectation_value  # noqa: E402,F401
+from .flux import p_z, p_plusminus, p_plus, p_minus, j_z, j_plusminus, j_plus, j_minus  # noqa: E402,F401
 from .mode_calculations import (  # noqa: E402,F401
     LdtVector, LVector, LLComparisonMatrix, LLMatrix, LLDominantEigenvector, angular_velocity, corotating_frame, inner_product,
 )

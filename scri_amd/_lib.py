@@ -204,6 +204,11 @@ SIGNATURES = {
     "bms_polar": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_i64]),
     "bms_polar_tile_rows": (c_i64, []),
     "bms_count_nonfinite": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "bms_poincare_fluxes": (c_int, [c_vp, c_dp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "bms_expectation_values": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_int, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_int32), c_vp, c_i64, c_int, c_vp]),
+    "bms_flux_launch_shape": (c_i64, [c_int, ctypes.POINTER(c_i64)]),
+    "bms_flux_coefficients": (c_int, [c_int, c_int, c_dp]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@
 //   engine_align.hip     time-and-phase alignment from correlation moments                                   (bms_align_moments, bms_align_residual)
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
+//   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values               (bms_poincare_fluxes, bms_expectation_values)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -218,6 +219,7 @@ struct bms_ctx {
   double* rot_ring_dev = nullptr;
   int rot_ring_next = 0;
   std::map<std::pair<int, int>, RotResPlan> rot_res_plans;  // LDS-resident table images built so far, by (ell_min, ell_max)
+  std::map<std::pair<int, int>, bool> flux_images;          // coefficient images of the fused fluxes on the device, by (ell_min, ell_max)
   int n_cu = 0;
   // analysis tables depend on the grid, the spin and the l range only: kept per tag until a call asks for other ones
   std::map<std::string, std::pair<std::array<int, 6>, AnalysisPlan>> plans;
@@ -746,6 +748,15 @@ BMS_INTERNAL int modes_checks(bms_ctx* c, int ell_min, int ell_max, int64_t ld, 
 // in block "av_out", through blocks "R" and "S": the launches bms_angular_velocity and bms_corotating_frame share (engine_blocks.hip)
 BMS_INTERNAL int angular_velocity_on_device(bms_ctx* c, const double* d_y, int64_t ld, int64_t n, int ell_min, int n_modes, const double* d_x,
                                             const SplineTable* d_tab, int tile, double** d_res);
+// engine_flux.hip: the coefficient image of the fused fluxes (long double, rounded once), the walk over a triplet list, and what the two
+// entries refuse before they select a device
+BMS_INTERNAL void build_flux_image(int ell_min, int ell_max, std::vector<double>& image);
+BMS_INTERNAL int64_t first_bad_triplet(const int32_t* rows, const int32_t* cols, int64_t n_el, int n_cols);
+BMS_INTERNAL int flux_checks(bms_ctx* c, const double* t, const void* h, int64_t ld_h, const void* hdot, int64_t ld_hdot, int64_t n_times,
+                             int ell_min, int ell_max, int mem, const double* energy, const double* momentum, const double* angular,
+                             const double* boost, int* n_modes);
+BMS_INTERNAL int expectation_checks(bms_ctx* c, const void* a, int64_t ld_a, const void* b, int64_t ld_b, int64_t n_times, int n_cols,
+                                    const int32_t* rows, const int32_t* cols, const void* values, int64_t n_el, int mem, const void* out);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

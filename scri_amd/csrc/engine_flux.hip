@@ -1,0 +1,209 @@
+// Fluxes of energy, momentum, angular momentum and boost in one pass over the modes, and the general sparse expectation value
+// (kernels_flux.hip): the coefficient image of an l range, built on the host in long double and kept per context, and the two entries
+// behind scri_amd/flux.py
+// (engine.h: the split of the engine by entry family; include/scri_amd.h: the C ABI)
+#include "engine.h"
+
+namespace {
+
+// <l, m; 1, mu | J, m + mu> (Condon-Shortley), the closed forms for coupling with j = 1; zero outside the triangle and the m ranges
+long double cg_one(int l, int m, int mu, int J) {
+  const int M = m + mu;
+  if (l < 0 || J < 0 || std::abs(J - l) > 1 || std::abs(m) > l || std::abs(M) > J || std::abs(mu) > 1) return 0.0L;
+  const long double L = l, Md = M;
+  if (J == l + 1) {
+    if (mu == 1) return sqrtl((L + Md) * (L + Md + 1) / ((2 * L + 1) * (2 * L + 2)));
+    if (mu == 0) return sqrtl((L - Md + 1) * (L + Md + 1) / ((2 * L + 1) * (L + 1)));
+    return sqrtl((L - Md) * (L - Md + 1) / ((2 * L + 1) * (2 * L + 2)));
+  }
+  if (J == l) {
+    if (l == 0) return 0.0L;
+    if (mu == 1) return -sqrtl((L + Md) * (L - Md + 1) / (2 * L * (L + 1)));
+    if (mu == 0) return Md / sqrtl(L * (L + 1));
+    return sqrtl((L - Md) * (L + Md + 1) / (2 * L * (L + 1)));
+  }
+  if (mu == 1) return sqrtl((L - Md) * (L - Md + 1) / (2 * L * (2 * L + 1)));
+  if (mu == 0) return -sqrtl((L - Md) * (L + Md) / (L * (2 * L + 1)));
+  return sqrtl((L + Md + 1) * (L + Md) / (2 * L * (2 * L + 1)));
+}
+
+// <s, lp, m + mu| chi_mu |s, l, m>, chi_0 = cos(theta), chi_+-1 = sin(theta) e^{+-i phi} (the reference's p_z, p_plus, p_minus,
+// scri/flux.py:213-300; the factors of pi of its two prefactors cancel)
+long double chi_element(int s, int lp, int l, int m, int mu) {
+  const long double ratio = (2.0L * l + 1) / (2.0L * lp + 1), spin = cg_one(l, -s, 0, lp);
+  if (mu == 0) return sqrtl(ratio) * cg_one(l, m, 0, lp) * spin;
+  return -mu * sqrtl(2 * ratio) * cg_one(l, m, mu, lp) * spin;
+}
+// <lp, m + mu| (eth chi)_mu |l, m> between spin -1 and spin -2 (raise = true, scri/flux.py:480-500, 526-560) and
+// <lp, m + mu| (ethbar chi)_mu |l, m> between spin -2 and spin -1 (:501-521, 566-598), as the reference's generators give them
+long double ladder_chi_element(bool raise, int lp, int l, int m, int mu) {
+  const long double ratio = (2.0L * l + 1) / (2.0L * lp + 1), spin = raise ? cg_one(l, 2, -1, lp) : cg_one(l, 1, 1, lp);
+  if (mu == 0) return sqrtl(2 * ratio) * cg_one(l, m, 0, lp) * spin;
+  return -mu * 2 * sqrtl(ratio) * cg_one(l, m, mu, lp) * spin;
+}
+
+}  // namespace
+
+// The coefficient image of l = ell_min .. ell_max (layout: kernels_flux.hip), every entry computed in long double and rounded once.
+// eth and ethbar of a spin -2 field multiply its mode l by E_l = sqrt((l + 2)(l - 1)) and Eb_l = -sqrt((l - 2)(l + 3))
+// (Newman-Penrose convention, scri/waveform_modes.py:478-572).  Signs of the eth chi / ethbar chi terms as scri/flux.py:704-707, 740-741.
+BMS_INTERNAL void build_flux_image(int ell_min, int ell_max, std::vector<double>& image) {
+  const int n = LM_total_size(ell_min, ell_max);
+  image.assign((size_t)flux_image_doubles(n), 0.0);
+  auto E = [](int l) { return sqrtl((long double)(l + 2) * (l - 1)); };
+  auto Eb = [](int l) { return -sqrtl((long double)(l - 2) * (l + 3)); };
+  for (int l = ell_min; l <= ell_max; ++l)
+    for (int m = -l; m <= l; ++m) {
+      const int c = LM_index(l, m, ell_min);
+      for (int dl = -1; dl <= 1; ++dl)
+        for (int mu = -1; mu <= 1; ++mu) {
+          const int lp = l + dl, k = 3 * (dl + 1) + (mu + 1);
+          if (lp < ell_min || lp > ell_max || std::abs(m + mu) > lp) continue;
+          const long double chi2 = chi_element(-2, lp, l, m, mu);
+          const long double bracket = (Eb(lp) * chi_element(-3, lp, l, m, mu) * Eb(l) - E(lp) * chi_element(-1, lp, l, m, mu) * E(l) + 6 * chi2) / 8;
+          image[(size_t)(3 * k + 0) * n + c] = (double)chi2;
+          image[(size_t)(3 * k + 1) * n + c] = (double)(bracket - E(lp) * ladder_chi_element(true, lp, l, m, mu) / 4);
+          image[(size_t)(3 * k + 2) * n + c] = (double)(bracket + ladder_chi_element(false, lp, l, m, mu) * E(l) / 4);
+        }
+      image[(size_t)27 * n + c] = (double)sqrtl((long double)(l - m) * (l + m + 1));
+      image[(size_t)28 * n + c] = (double)sqrtl((long double)(l + m) * (l - m + 1));
+      image[(size_t)29 * n + c] = (double)l;
+    }
+}
+
+// the first triplet with an index outside [0, n_cols): -1 if there is none
+BMS_INTERNAL int64_t first_bad_triplet(const int32_t* rows, const int32_t* cols, int64_t n_el, int n_cols) {
+  for (int64_t e = 0; e < n_el; ++e)
+    if (rows[e] < 0 || rows[e] >= n_cols || cols[e] < 0 || cols[e] >= n_cols) return e;
+  return -1;
+}
+
+// what bms_poincare_fluxes refuses before it selects a device; *n_modes on success
+BMS_INTERNAL int flux_checks(bms_ctx* c, const double* t, const void* h, int64_t ld_h, const void* hdot, int64_t ld_hdot, int64_t n_times,
+                             int ell_min, int ell_max, int mem, const double* energy, const double* momentum, const double* angular,
+                             const double* boost, int* n_modes) {
+  if (!hdot) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: NULL hdot");
+  if (!energy && !momentum && !angular && !boost) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: every output is NULL");
+  if ((angular || boost) && !h) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: the angular-momentum and boost fluxes need h, which is NULL");
+  if (boost && !t) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: the boost flux needs the times, which are NULL");
+  if (n_times < 0) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: negative n_times");
+  if (ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: bad ell range [%d, %d]", ell_min, ell_max);
+  if (ell_min < 2) return fail(c, BMS_ERR_UNSUPPORTED, "bms_poincare_fluxes: ell_min = %d: the fused fluxes take spin -2 modes from ell_min >= 2", ell_min);
+  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "bms_poincare_fluxes: ell_max = %d is beyond %d", ell_max, MAX_ELL);
+  *n_modes = LM_total_size(ell_min, ell_max);
+  if (ld_hdot < *n_modes || (h && ld_h < *n_modes)) return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: row stride smaller than the number of modes (%d)", *n_modes);
+  if (mem == BMS_DEVICE && ((((uintptr_t)h | (uintptr_t)hdot) & 15) || (((uintptr_t)energy | (uintptr_t)momentum | (uintptr_t)angular | (uintptr_t)boost) & 7)))
+    return fail(c, BMS_ERR_INVALID, "bms_poincare_fluxes: device arrays must be aligned to their elements");
+  return BMS_OK;
+}
+
+// the image of (ell_min, ell_max) on the device, built once per context and range (as the rotation's resident tables are)
+static int ensure_flux_image(bms_ctx* c, int ell_min, int ell_max, const double** d_image) {
+  char name[64];
+  snprintf(name, sizeof name, "flux_image_%d_%d", ell_min, ell_max);
+  const int n = LM_total_size(ell_min, ell_max);
+  double* d = nullptr;
+  if (int rc = dev_buf_t(c, name, (size_t)flux_image_doubles(n), &d)) return rc;
+  *d_image = d;
+  if (c->flux_images.count({ell_min, ell_max})) return BMS_OK;
+  std::vector<double> image;
+  build_flux_image(ell_min, ell_max, image);
+  HIP_TRY(c, hipMemcpyAsync(d, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vector goes out of scope
+  c->flux_images[{ell_min, ell_max}] = true;
+  return BMS_OK;
+}
+
+// (sizes, not statuses) how the fused kernel would run n_modes columns on the current device: shape[0] time steps per pass of one
+// workgroup (returned as well), shape[1] workgroups at most, shape[2] != 0 if the coefficient image is held in LDS; returns 0 if the range is not supported
+extern "C" int64_t bms_flux_launch_shape(int n_modes, int64_t shape[3]) {
+  FluxShape S;
+  if (!shape || !flux_launch_shape(n_modes, &S)) return 0;
+  shape[0] = S.waves, shape[1] = S.groups, shape[2] = S.tables_in_lds ? 1 : 0;
+  return S.waves;
+}
+
+// pure host routine: the coefficient image the fused kernel reads, [30][n_modes] doubles (kernels_flux.hip states the layout)
+extern "C" int bms_flux_coefficients(int ell_min, int ell_max, double* image_out) try {
+  if (!image_out || ell_min < 2 || ell_max < ell_min || ell_max > MAX_ELL) return BMS_ERR_INVALID;
+  std::vector<double> image;
+  build_flux_image(ell_min, ell_max, image);
+  std::memcpy(image_out, image.data(), sizeof(double) * image.size());
+  return BMS_OK;
+} BMS_CATCH(nullptr)
+
+extern "C" int bms_poincare_fluxes(bms_ctx* c, const double* t, const void* h, int64_t ld_h, const void* hdot, int64_t ld_hdot, int64_t n_times,
+                                   int ell_min, int ell_max, int mem, double* energy, double* momentum, double* angular, double* boost) try {
+  if (!c) return BMS_ERR_INVALID;
+  if (int rc0 = entry_mem(c, mem, "bms_poincare_fluxes", false)) return rc0;  // (the argument checks come before the device is selected)
+  int rc, n_modes = 0;
+  if ((rc = flux_checks(c, t, h, ld_h, hdot, ld_hdot, n_times, ell_min, ell_max, mem, energy, momentum, angular, boost, &n_modes))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  FluxShape S;
+  if (!flux_launch_shape(n_modes, &S))
+    return fail(c, BMS_ERR_UNSUPPORTED, "bms_poincare_fluxes: %d modes (ell = %d .. %d): one time step's rows of h and hdot do not fit in LDS", n_modes, ell_min, ell_max);
+  const double* d_image;
+  if ((rc = ensure_flux_image(c, ell_min, ell_max, &d_image))) return rc;
+  const bool with_h = angular || boost;
+  CallIO io(c, mem);
+  const double *d_t = nullptr, *d_h = nullptr, *d_n;
+  if ((rc = io.in("in_data", hdot, ((size_t)(n_times - 1) * ld_hdot + n_modes) * 16, &d_n))) return rc;
+  if (with_h && (rc = io.in("in_aux0", h, ((size_t)(n_times - 1) * ld_h + n_modes) * 16, &d_h))) return rc;
+  if (boost) {  // (the times are a host array whatever `mem` is, as everywhere in this interface)
+    void* vp;
+    if ((rc = upload(c, "times", t, 8 * (size_t)n_times, &vp))) return rc;
+    d_t = (const double*)vp;
+  }
+  double *d_e, *d_p, *d_j, *d_b;
+  if ((rc = io.out("flux_e", energy, (size_t)n_times, &d_e))) return rc;
+  if ((rc = io.out("flux_p", momentum, (size_t)3 * n_times, &d_p))) return rc;
+  if ((rc = io.out("flux_j", angular, (size_t)3 * n_times, &d_j))) return rc;
+  if ((rc = io.out("flux_b", boost, (size_t)3 * n_times, &d_b))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_poincare_fluxes(c->stream, d_t, d_h, ld_h, d_n, ld_hdot, n_times, ell_min, ell_max, d_image, d_e, d_p, d_j, d_b));
+  return io.finish();
+} BMS_CATCH(c)
+
+// what bms_expectation_values refuses before it selects a device
+BMS_INTERNAL int expectation_checks(bms_ctx* c, const void* a, int64_t ld_a, const void* b, int64_t ld_b, int64_t n_times, int n_cols,
+                                    const int32_t* rows, const int32_t* cols, const void* values, int64_t n_el, int mem, const void* out) {
+  if (!a || !b || !out || (n_el > 0 && (!rows || !cols || !values))) return fail(c, BMS_ERR_INVALID, "bms_expectation_values: NULL argument");
+  if (n_times < 0 || n_el < 0 || n_cols < 1) return fail(c, BMS_ERR_INVALID, "bms_expectation_values: bad sizes");
+  if (ld_a < n_cols || ld_b < n_cols) return fail(c, BMS_ERR_INVALID, "bms_expectation_values: row stride smaller than the number of columns (%d)", n_cols);
+  const int64_t bad = first_bad_triplet(rows, cols, n_el, n_cols);
+  if (bad >= 0)
+    return fail(c, BMS_ERR_INVALID, "bms_expectation_values: element %lld couples row %d and column %d, outside [0, %d)", (long long)bad, (int)rows[bad],
+                (int)cols[bad], n_cols);
+  if (mem == BMS_DEVICE && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15))
+    return fail(c, BMS_ERR_INVALID, "bms_expectation_values: device arrays must be aligned to their elements");
+  return BMS_OK;
+}
+
+extern "C" int bms_expectation_values(bms_ctx* c, const void* a, int64_t ld_a, int conj_a, const void* b, int64_t ld_b, int64_t n_times, int n_cols,
+                                      const int32_t* rows, const int32_t* cols, const void* values, int64_t n_el, int mem, void* out) try {
+  if (!c) return BMS_ERR_INVALID;
+  if (int rc0 = entry_mem(c, mem, "bms_expectation_values", false)) return rc0;
+  int rc;
+  if ((rc = expectation_checks(c, a, ld_a, b, ld_b, n_times, n_cols, rows, cols, values, n_el, mem, out))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n_cols > expectation_max_cols())
+    return fail(c, BMS_ERR_UNSUPPORTED, "bms_expectation_values: %d columns: one time step's row pair does not fit in LDS (at most %d)", n_cols, expectation_max_cols());
+  CallIO io(c, mem);
+  void *d_rows, *d_cols, *d_vals;
+  const size_t ne = (size_t)std::max<int64_t>(n_el, 1);
+  if ((rc = dev_buf(c, "ev_rows", 4 * ne, &d_rows)) || (rc = dev_buf(c, "ev_cols", 4 * ne, &d_cols)) || (rc = dev_buf(c, "ev_values", 16 * ne, &d_vals))) return rc;
+  if (n_el > 0) {
+    if ((rc = upload(c, "ev_rows", rows, 4 * (size_t)n_el, &d_rows))) return rc;
+    if ((rc = upload(c, "ev_cols", cols, 4 * (size_t)n_el, &d_cols))) return rc;
+    if ((rc = upload(c, "ev_values", values, 16 * (size_t)n_el, &d_vals))) return rc;
+  }
+  const double *d_a, *d_b;
+  if ((rc = io.in("in_data", a, ((size_t)(n_times - 1) * ld_a + n_cols) * 16, &d_a))) return rc;
+  if ((rc = io.in("in_aux0", b, ((size_t)(n_times - 1) * ld_b + n_cols) * 16, &d_b))) return rc;
+  double* d_out;
+  if ((rc = io.out("ev_out", out, (size_t)2 * n_times, &d_out))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_expectation_values(c->stream, d_a, ld_a, conj_a != 0, d_b, ld_b, n_times, n_cols, (const int*)d_rows, (const int*)d_cols,
+                                                        (const double*)d_vals, n_el, d_out));
+  return io.finish();
+} BMS_CATCH(c)

@@ -458,6 +458,27 @@ hipError_t launch_polar(hipStream_t stream, const void* in, long long ld, long l
 // acc[0] += elements with a non-finite part, acc[1] = min(acc[1], first row holding one); acc preset to (0, all ones)
 hipError_t launch_count_nonfinite(hipStream_t stream, const void* in, long long ld, long long n_rows, int n_cols, unsigned long long* acc);
 
+// ---- fluxes of energy, momentum, angular momentum and boost in one pass over the modes (kernels_flux.hip; scri/flux.py:182-798)
+// How the launcher runs a range of n_modes columns: one wave per time step, `waves` steps per pass of a workgroup, at most `groups`
+// persistent workgroups; tables_in_lds: the coefficient image sits in LDS beside the rows, else it is read through L2.
+struct FluxShape {
+  int waves, groups;
+  bool tables_in_lds;
+  size_t lds_bytes;
+};
+int flux_image_doubles(int n_modes);                 // doubles of the coefficient image (engine_flux.hip builds it)
+bool flux_launch_shape(int n_modes, FluxShape* S);  // false: not even one wave's row pair fits in LDS
+// energy f8[n], momentum / angular / boost f8[n][3] (any may be null; h may be null without angular and boost, t without boost) of
+// h, hdot c16[n][ld] holding l = ell_min .. ell_max, ell_min >= 2
+hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const double* h, long long ld_h, const double* hdot, long long ld_hdot,
+                                  long long n_times, int ell_min, int ell_max, const double* image, double* energy, double* momentum,
+                                  double* angular, double* boost);
+// out c16[n] = sum_e op(a[t][rows_e]) values_e b[t][cols_e] for triplets on the device, indices inside [0, n_cols) (the entry checks them)
+int expectation_max_cols();
+hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,
+                                     long long n_times, int n_cols, const int* rows, const int* cols, const double* values, long long n_el,
+                                     double* out);
+
 // centre-of-mass track and drift fit of the horizon trajectories (scri/SpEC/com_motion.py), kernels_com.hip
 constexpr int COM_FIT_TILE = 256;  // panels (two intervals each) per partial of the moment sums: one per thread of a workgroup
 constexpr int COM_FIT_OUT = 24;    // doubles of the fit's result block (com_fit_kernel)

@@ -1,0 +1,260 @@
+// Fluxes of energy, momentum, angular momentum and boost (scri/flux.py:182-798) of modes resident in HBM, in one pass over the modes.
+//
+// Every operator of scri/flux.py is banded: a column (l, m) couples only to the rows (l + dl, m + mu), dl, mu in {-1, 0, 1}, and with the
+// ladder factors of eth / ethbar folded into the coefficients only h and hdot = N are read.  Per (column, neighbour) three REAL
+// coefficients remain (engine_flux.hip builds them in long double):
+//     P   chi at s = -2                                    momentum flux <N|chi|N>, and the boost term -(u/2) <N|chi|N>: formed once
+//     B1  (1/8)[ethbar' chi_-3 ethbar - eth' chi_-1 eth + 6 chi_-2] - (1/4) eth' (eth chi)       the pair (N, h)
+//     B2  (1/8)[...the same bracket...]                            + (1/4) (ethbar chi) eth      the pair (h, N)
+// and the angular-momentum operators need lambda_+- = sqrt((l -+ m)(l +- m + 1)) and m.  The image of one l range: 27 n + 2 n + n doubles,
+//     image[(3 k + set) n + c]   k = 3 (dl + 1) + (mu + 1), set = 0 (P), 1 (B1), 2 (B2), column c      (lanes read consecutive doubles)
+//     image[27 n + c], image[28 n + c]   lambda_+, lambda_-;      image[29 n + c]   l of the column
+// A persistent workgroup copies the image into LDS ONCE (while it fits beside the rows: FluxShape::tables_in_lds, else it is read through
+// L2) and then walks time steps, one wave per step: the two rows of the step go to LDS by 16-byte loads of consecutive lanes (coalesced
+// for any n_modes and ld), lane j sums the columns j, j + 64, ... in that order, and the sixteen partial sums are added across the wave by
+// a butterfly.  Nothing in that order depends on the launch geometry, so a step's result does not depend on the steps around it, on the
+// number of waves or workgroups, or on which outputs were asked for.  No contraction: every multiply-add is spelled out.
+#include "wigner.h"
+#include "kernels.h"
+
+namespace bms {
+
+namespace {
+
+constexpr int FLUX_IMAGE_PER_MODE = 30;  // doubles of the image per column
+constexpr int FLUX_MAX_WAVES = 8;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <bool WITH_H, bool TAB_LDS>
+__global__ __launch_bounds__(64 * FLUX_MAX_WAVES) void flux_kernel(const double* __restrict__ t, const double* __restrict__ H, long long ld_h,
+                                                                   const double* __restrict__ N, long long ld_n, long long n_times, int ell_min,
+                                                                   int ell_max, int n, const double* __restrict__ image, double* __restrict__ e_out,
+                                                                   double* __restrict__ p_out, double* __restrict__ j_out, double* __restrict__ b_out) {
+#pragma clang fp contract(off)
+  extern __shared__ double2 flux_lds[];  // [waves][rows][n] rows of modes, then the image
+  constexpr int ROWS = WITH_H ? 2 : 1;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double2* nrow = flux_lds + (size_t)wave * ROWS * n;
+  double2* hrow = nrow + (WITH_H ? n : 0);
+  double* ltab = reinterpret_cast<double*>(flux_lds + (size_t)waves * ROWS * n);
+  if (TAB_LDS)
+    for (int i = threadIdx.x; i < FLUX_IMAGE_PER_MODE * n; i += blockDim.x) ltab[i] = image[i];
+  auto tab = [&](int i) { return TAB_LDS ? ltab[i] : image[i]; };
+  const long long pass_steps = (long long)gridDim.x * waves, passes = (n_times + pass_steps - 1) / pass_steps;
+  const int base = ell_min * ell_min;
+  __syncthreads();
+  for (long long pass = 0; pass < passes; ++pass) {  // (every wave takes every barrier: the trip count is the workgroup's)
+    const long long step = pass * pass_steps + (long long)blockIdx.x * waves + wave;
+    const bool live = step < n_times;
+    if (live)
+      for (int i = lane; i < n; i += 64) {
+        nrow[i] = *reinterpret_cast<const double2*>(N + (step * ld_n + i) * 2);
+        if (WITH_H) hrow[i] = *reinterpret_cast<const double2*>(H + (step * ld_h + i) * 2);
+      }
+    __syncthreads();
+    if (live) {
+      // + and - components as (re, im), z as re: P = <N|chi|N>, B = <N|B1|h> + <h|B2|N>, J = <N|J|h>
+      double e = 0, P[5] = {0, 0, 0, 0, 0}, B[5] = {0, 0, 0, 0, 0}, J[5] = {0, 0, 0, 0, 0};
+      for (int i = lane; i < n; i += 64) {
+        const int l = (int)tab(29 * n + i), m = i + base - l * (l + 1);
+        const double2 nc = nrow[i];
+        const double2 hc = WITH_H ? hrow[i] : double2{0.0, 0.0};
+        e = fma(nc.x, nc.x, e);
+        e = fma(nc.y, nc.y, e);
+#pragma unroll
+        for (int dl = -1; dl <= 1; ++dl) {
+          const int lp = l + dl;
+          if (lp < ell_min || lp > ell_max) continue;
+          const int shift = dl == 0 ? 0 : (dl > 0 ? 2 * l + 2 : -2 * l);
+#pragma unroll
+          for (int mu = -1; mu <= 1; ++mu) {
+            if (m + mu < -lp || m + mu > lp) continue;
+            const int r = i + shift + mu, k = 3 * (dl + 1) + (mu + 1);
+            const int o = mu == 1 ? 0 : (mu == -1 ? 2 : 4);  // where the component's (re, im) live
+            const double2 nr = nrow[r];
+            const double cp = tab((3 * k + 0) * n + i);
+            // conj(nr) nc
+            const double qr = fma(nr.x, nc.x, nr.y * nc.y), qi = fma(nr.x, nc.y, -(nr.y * nc.x));
+            P[o] = fma(cp, qr, P[o]);
+            if (mu != 0) P[o + 1] = fma(cp, qi, P[o + 1]);
+            if (WITH_H) {
+              const double2 hr = hrow[r];
+              const double c1 = tab((3 * k + 1) * n + i), c2 = tab((3 * k + 2) * n + i);
+              const double ar = fma(nr.x, hc.x, nr.y * hc.y), ai = fma(nr.x, hc.y, -(nr.y * hc.x));  // conj(nr) hc
+              const double br = fma(hr.x, nc.x, hr.y * nc.y), bi = fma(hr.x, nc.y, -(hr.y * nc.x));  // conj(hr) nc
+              B[o] = fma(c1, ar, B[o]);
+              B[o] = fma(c2, br, B[o]);
+              if (mu != 0) {
+                B[o + 1] = fma(c1, ai, B[o + 1]);
+                B[o + 1] = fma(c2, bi, B[o + 1]);
+              }
+              if (dl == 0) {  // <l, m + mu| J |l, m> = i lambda: i (ar + i ai) = -ai + i ar
+                const double lam = mu == 0 ? (double)m : tab((mu == 1 ? 27 : 28) * n + i);
+                J[o] = fma(-lam, ai, J[o]);
+                if (mu != 0) J[o + 1] = fma(lam, ar, J[o + 1]);
+              }
+            }
+          }
+        }
+      }
+      e = wave_sum(e);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        P[q] = wave_sum(P[q]);
+        if (WITH_H) B[q] = wave_sum(B[q]), J[q] = wave_sum(J[q]);
+      }
+      if (lane == 0) {
+        const double e_scale = 16.0 * M_PI;
+        if (e_out) e_out[step] = e / e_scale;
+        if (p_out) {
+          p_out[3 * step] = 0.5 * (P[0] + P[2]) / e_scale;
+          p_out[3 * step + 1] = 0.5 * (P[1] - P[3]) / e_scale;
+          p_out[3 * step + 2] = P[4] / e_scale;
+        }
+        if (WITH_H && j_out) {
+          j_out[3 * step] = 0.5 * (J[0] + J[2]) / -e_scale;
+          j_out[3 * step + 1] = 0.5 * (J[1] - J[3]) / -e_scale;
+          j_out[3 * step + 2] = J[4] / -e_scale;
+        }
+        if (WITH_H && b_out) {
+          const double half_u = 0.5 * t[step], b_scale = -32.0 * M_PI;
+          double T[5];
+#pragma unroll
+          for (int q = 0; q < 5; ++q) T[q] = fma(-half_u, P[q], B[q]);
+          b_out[3 * step] = 0.5 * (T[0] + T[2]) / b_scale;
+          b_out[3 * step + 1] = 0.5 * (T[1] - T[3]) / b_scale;
+          b_out[3 * step + 2] = T[4] / b_scale;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// out[t] = sum_e op(a[t][rows_e]) values_e b[t][cols_e]: one wave per step, its row pair in LDS, element e on lane e mod 64, lane sums in
+// element order, then the butterfly
+__global__ __launch_bounds__(256) void expectation_kernel(const double* __restrict__ A, long long ld_a, int conj_a, const double* __restrict__ Bm,
+                                                          long long ld_b, long long n_times, int n_cols, const int* __restrict__ rows,
+                                                          const int* __restrict__ cols, const double2* __restrict__ values, long long n_el,
+                                                          double* __restrict__ out) {
+#pragma clang fp contract(off)
+  extern __shared__ double2 exp_lds[];  // [waves][2][n_cols]
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double2* a = exp_lds + (size_t)wave * 2 * n_cols;
+  double2* b = a + n_cols;
+  const long long pass_steps = (long long)gridDim.x * waves, passes = (n_times + pass_steps - 1) / pass_steps;
+  for (long long pass = 0; pass < passes; ++pass) {
+    const long long step = pass * pass_steps + (long long)blockIdx.x * waves + wave;
+    const bool live = step < n_times;
+    if (live)
+      for (int i = lane; i < n_cols; i += 64) {
+        a[i] = *reinterpret_cast<const double2*>(A + (step * ld_a + i) * 2);
+        b[i] = *reinterpret_cast<const double2*>(Bm + (step * ld_b + i) * 2);
+      }
+    __syncthreads();
+    if (live) {
+      double sr = 0, si = 0;
+      for (long long el = lane; el < n_el; el += 64) {
+        const double2 x = a[rows[el]], y = b[cols[el]], v = values[el];
+        const double xi = conj_a ? -x.y : x.y;
+        const double pr = fma(x.x, y.x, -(xi * y.y)), pi = fma(x.x, y.y, xi * y.x);  // x y
+        sr = fma(pr, v.x, sr);
+        sr = fma(-pi, v.y, sr);
+        si = fma(pr, v.y, si);
+        si = fma(pi, v.x, si);
+      }
+      sr = wave_sum(sr);
+      si = wave_sum(si);
+      if (lane == 0) out[2 * step] = sr, out[2 * step + 1] = si;
+    }
+    __syncthreads();
+  }
+}
+
+int compute_units() {
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  (void)hipGetLastError();
+  return cus;
+}
+
+}  // namespace
+
+int flux_image_doubles(int n_modes) { return FLUX_IMAGE_PER_MODE * n_modes; }
+
+// 8, 4, 2 or 1 waves with the image in LDS while both fit; beyond that the image stays in global memory and the waves' rows have the LDS
+bool flux_launch_shape(int n_modes, FluxShape* S) {
+  if (n_modes < 1) return false;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const size_t room = (size_t)lds_per_workgroup(dev), row_pair = (size_t)32 * n_modes, image = (size_t)8 * flux_image_doubles(n_modes);
+  FluxShape s{};
+  for (int w = FLUX_MAX_WAVES; w >= 1 && !s.waves; w >>= 1)
+    if (w * row_pair + image <= room) s.waves = w, s.tables_in_lds = true, s.lds_bytes = w * row_pair + image;
+  for (int w = FLUX_MAX_WAVES; w >= 1 && !s.waves; w >>= 1)
+    if (w * row_pair <= room) s.waves = w, s.tables_in_lds = false, s.lds_bytes = w * row_pair;
+  if (!s.waves) return false;
+  // as many workgroups as the device holds at once: by LDS, and by its 32 waves per compute unit
+  const long long per_cu = std::max<long long>(1, std::min<long long>((long long)(room / s.lds_bytes), 32 / s.waves));
+  s.groups = (int)std::min<long long>(per_cu * compute_units(), 1 << 20);
+  *S = s;
+  return true;
+}
+
+hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const double* h, long long ld_h, const double* hdot, long long ld_hdot,
+                                  long long n_times, int ell_min, int ell_max, const double* image, double* energy, double* momentum,
+                                  double* angular, double* boost) {
+  if (n_times <= 0) return hipSuccess;
+  const int n = (ell_max + 1) * (ell_max + 1) - ell_min * ell_min;
+  const bool with_h = angular || boost;
+  FluxShape S;
+  if (!hdot || !image || (with_h && !h) || (boost && !t) || !flux_launch_shape(n, &S)) return hipErrorInvalidValue;
+  const long long groups = std::min<long long>(S.groups, (n_times + S.waves - 1) / S.waves);
+  // (the shape is that of two rows per wave; a launch without h leaves the second row's LDS unused)
+  auto go = [&](auto kernel) -> hipError_t {
+    if (S.lds_bytes > 64 * 1024) {
+      hipError_t e = allow_dynamic_lds((const void*)kernel);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * S.waves), S.lds_bytes, stream, t, h, ld_h, hdot, ld_hdot, n_times, ell_min, ell_max,
+                       n, image, energy, momentum, angular, boost);
+    return hipGetLastError();
+  };
+  if (with_h) return S.tables_in_lds ? go(flux_kernel<true, true>) : go(flux_kernel<true, false>);
+  return S.tables_in_lds ? go(flux_kernel<false, true>) : go(flux_kernel<false, false>);
+}
+
+int expectation_max_cols() {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  return (int)((size_t)lds_per_workgroup(dev) / 32);
+}
+
+hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,
+                                     long long n_times, int n_cols, const int* rows, const int* cols, const double* values, long long n_el,
+                                     double* out) {
+  if (n_times <= 0) return hipSuccess;
+  if (n_cols < 1 || n_cols > expectation_max_cols()) return hipErrorInvalidValue;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const size_t room = (size_t)lds_per_workgroup(dev);
+  int waves = 4;
+  while (waves > 1 && (size_t)waves * 32 * n_cols > room) waves >>= 1;
+  const size_t lds = (size_t)waves * 32 * n_cols;
+  if (lds > 64 * 1024) {
+    hipError_t e = allow_dynamic_lds((const void*)expectation_kernel);
+    if (e != hipSuccess) return e;
+  }
+  const long long groups = std::min<long long>((n_times + waves - 1) / waves, 8LL * compute_units());
+  hipLaunchKernelGGL(expectation_kernel, dim3((unsigned)groups), dim3(64 * waves), lds, stream, a, ld_a, conj_a, b, ld_b, n_times, n_cols, rows, cols,
+                     reinterpret_cast<const double2*>(values), n_el, out);
+  return hipGetLastError();
+}
+
+}  // namespace bms

@@ -1044,6 +1044,81 @@ def count_nonfinite(data, ctx=None):
     return int(count.value), int(first.value)
 
 
+FLUX_NAMES = ("energy", "momentum", "angular", "boost")
+
+
+def flux_launch_shape(n_modes):
+    """(time steps per pass of one workgroup, workgroups at most, whether the coefficient tables sit in LDS) of the fused flux kernel
+    for n_modes columns on the current device (bms_flux_launch_shape); None if the range is not supported"""
+    shape = (c_i64 * 3)()
+    if not _lib.load().bms_flux_launch_shape(int(n_modes), shape):
+        return None
+    return int(shape[0]), int(shape[1]), bool(shape[2])
+
+
+def flux_coefficients(ell_min, ell_max):
+    """the coefficient tables of the fused flux kernel, f8[30, n_modes] (bms_flux_coefficients: a host routine, no device needed)"""
+    out = np.empty((30, LM_total_size(ell_min, ell_max)))
+    rc = _lib.load().bms_flux_coefficients(int(ell_min), int(ell_max), dptr(out))
+    if rc != 0:
+        raise ValueError(f"bms_flux_coefficients: bad ell range [{ell_min}, {ell_max}] (status {rc})")
+    return out
+
+
+def poincare_fluxes(t, h, hdot, ell_min, ell_max, want=FLUX_NAMES, ctx=None):
+    """bms_poincare_fluxes: the fluxes named in `want` -- "energy" [N], "momentum", "angular", "boost" [N, 3] -- of the strain h[N, n_modes]
+    and its time derivative hdot, l = ell_min .. ell_max, ell_min >= 2, in one launch.  h and hdot are numpy arrays (numpy arrays out) or
+    device tensors (complex128, unit column stride, any row stride: float64 device tensors out); h may be None when neither "angular" nor
+    "boost" is wanted.  Returns the results in the order of `want` (a tuple); one name as a string returns that array alone."""
+    ctx = _ctx(ctx)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or len(set(names)) != len(names) or not set(names) <= set(FLUX_NAMES):
+        raise ValueError(f"want names {', '.join(repr(k) for k in FLUX_NAMES)}, got {want!r}")
+    n_modes = LM_total_size(ell_min, ell_max)
+    N = _stage(ctx, hdot, np.complex128, "hdot", shape=(None, n_modes))
+    with_h = "angular" in names or "boost" in names
+    if with_h and h is None:
+        raise ValueError("the angular-momentum and boost fluxes need h")
+    H = _stage(ctx, h, np.complex128, "h", shape=(N.rows, n_modes)) if with_h else None
+    if H is not None and H.mem != N.mem:
+        raise ValueError("h and hdot must live in the same memory")
+    t = np.ascontiguousarray(t, dtype=float) if "boost" in names else None
+    if t is not None and t.shape != (N.rows,):
+        raise ValueError(f"{N.rows} time steps of modes on {t.shape} times")
+    out = {k: out_like(N, (N.rows,) if k == "energy" else (N.rows, 3), float) for k in names}
+    if N.rows:
+        ptr = lambda k: out[k][0] if k in out else None  # noqa: E731
+        rc = _lib.load().bms_poincare_fluxes(ctx.handle, dptr(t) if t is not None else None, H.ptr if H is not None else None,
+                                             H.ld if H is not None else 0, N.ptr, N.ld, N.rows, int(ell_min), int(ell_max), N.mem,
+                                             ptr("energy"), ptr("momentum"), ptr("angular"), ptr("boost"))
+        ctx.check(rc, "bms_poincare_fluxes")
+    res = tuple(out[k][1] for k in names)
+    return res[0] if isinstance(want, str) else res
+
+
+def expectation_values(a, rows, cols, values, b, conj_a=False, ctx=None):
+    """bms_expectation_values: out[t] = sum_e op(a[t, rows[e]]) values[e] b[t, cols[e]], op = conjugation with conj_a, for any triplets
+    (the reference's sparse_expectation_value).  a, b: numpy arrays [N, n] (a numpy array out) or device tensors (complex128, unit column
+    stride: a device tensor out); rows, cols, values: host arrays of one length."""
+    ctx = _ctx(ctx)
+    A = _stage(ctx, a, np.complex128, "a", shape=(None, None))
+    B = _stage(ctx, b, np.complex128, "b", shape=(A.rows, A.cols))
+    if A.mem != B.mem:
+        raise ValueError("a and b must live in the same memory")
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    values = np.ascontiguousarray(values, dtype=np.complex128)
+    if rows.ndim != 1 or cols.shape != rows.shape or values.shape != rows.shape:
+        raise ValueError("rows, cols and values must be one-dimensional and of one length")
+    out_ptr, out = out_like(A, (A.rows,), np.complex128)
+    if A.rows:
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        rc = _lib.load().bms_expectation_values(ctx.handle, A.ptr, A.ld, int(bool(conj_a)), B.ptr, B.ld, A.rows, A.cols, rows.ctypes.data_as(i32),
+                                                cols.ctypes.data_as(i32), vptr(values), rows.shape[0], A.mem, out_ptr)
+        ctx.check(rc, "bms_expectation_values")
+    return out
+
+
 PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
 
 

@@ -3,7 +3,7 @@
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
 // pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain, of the rotor interpolation and of the alignment entries, the planner and the per-step
-// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, the prologues of the entries that stage host or device arguments (entry_mem, CallIO), over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, the coefficient tables of the fused fluxes and the walk over a list of triplets, the prologues of the entries that stage host or device arguments (entry_mem, CallIO), over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -14,6 +14,7 @@
 #include "../../scri_amd/csrc/engine_align.hip"
 #include "../../scri_amd/csrc/engine_sample.hip"
 #include "../../scri_amd/csrc/engine_com.hip"
+#include "../../scri_amd/csrc/engine_flux.hip"
 
 #include <cstdio>
 #include <random>
@@ -672,6 +673,70 @@ void dense_product_arguments() {
   REQUIRE(launch_zgemm3m(nullptr, a, 36, b, 256, c, 140, M, 0, 18, nullptr, nullptr) == hipSuccess);
 }
 
+// The fused fluxes (engine_flux.hip): the coefficient image of four l ranges -- every neighbour outside the range is zero, the image of
+// sin(theta) e^{+i phi} is the transpose of that of sin(theta) e^{-i phi} and cos(theta)'s is symmetric (real matrices of adjoint
+// operators) -- the walk over a triplet list with an index out of range, and what the two entries refuse before they select a device.
+void flux_tables_and_triplets() {
+  const int ranges[][2] = {{2, 2}, {2, 3}, {3, 5}, {2, 16}};
+  for (const auto& lr : ranges) {
+    const int ell_min = lr[0], ell_max = lr[1], n = LM_total_size(ell_min, ell_max);
+    std::vector<double> image;
+    build_flux_image(ell_min, ell_max, image);
+    REQUIRE((int)image.size() == flux_image_doubles(n) && (int)image.size() == 30 * n);
+    for (int l = ell_min; l <= ell_max; ++l)
+      for (int m = -l; m <= l; ++m) {
+        const int c = LM_index(l, m, ell_min);
+        REQUIRE(image[(size_t)29 * n + c] == l);
+        REQUIRE(image[(size_t)27 * n + c] == std::sqrt((double)((l - m) * (l + m + 1))) && image[(size_t)28 * n + c] == std::sqrt((double)((l + m) * (l - m + 1))));
+        for (int dl = -1; dl <= 1; ++dl)
+          for (int mu = -1; mu <= 1; ++mu) {
+            const int lp = l + dl, k = 3 * (dl + 1) + (mu + 1);
+            const bool inside = lp >= ell_min && lp <= ell_max && std::abs(m + mu) <= lp;
+            for (int set = 0; set < 3; ++set) REQUIRE(std::isfinite(image[(size_t)(3 * k + set) * n + c]) && (inside || image[(size_t)(3 * k + set) * n + c] == 0.0));
+            if (!inside) continue;
+            const int r = LM_index(lp, m + mu, ell_min), back = 3 * (-dl + 1) + (-mu + 1);
+            REQUIRE(r >= 0 && r < n);
+            REQUIRE(std::fabs(image[(size_t)(3 * k) * n + c] - image[(size_t)(3 * back) * n + r]) <= 4e-16);
+          }
+      }
+  }
+  const int32_t rows[5] = {0, 3, 4, 2, 1}, cols[5] = {4, 0, 1, 5, 2}, low[3] = {0, -1, 2};
+  REQUIRE(first_bad_triplet(rows, cols, 5, 6) == -1 && first_bad_triplet(rows, cols, 5, 5) == 3 && first_bad_triplet(rows, cols, 3, 5) == -1);
+  REQUIRE(first_bad_triplet(low, cols, 3, 6) == 1 && first_bad_triplet(rows, low, 3, 6) == 1 && first_bad_triplet(rows, cols, 0, 1) == -1);
+  bms_ctx dummy;
+  alignas(16) static double v[64], out[64];
+  double t[4] = {0.0, 0.1, 0.2, 0.3};
+  auto says = [&](const char* text) { return std::strstr(bms_last_error(&dummy), text) != nullptr; };
+  REQUIRE(expectation_checks(&dummy, v, 6, v, 6, 2, 6, rows, cols, v, 5, BMS_HOST, out) == BMS_OK);
+  REQUIRE(expectation_checks(&dummy, v, 6, v, 6, 2, 5, rows, cols, v, 5, BMS_HOST, out) == BMS_ERR_INVALID && says("element 3 couples row 2 and column 5, outside [0, 5)"));
+  REQUIRE(expectation_checks(&dummy, v, 5, v, 6, 2, 6, rows, cols, v, 5, BMS_HOST, out) == BMS_ERR_INVALID && says("row stride"));
+  REQUIRE(expectation_checks(&dummy, nullptr, 6, v, 6, 2, 6, rows, cols, v, 5, BMS_HOST, out) == BMS_ERR_INVALID && says("NULL"));
+  REQUIRE(expectation_checks(&dummy, v, 6, v, 6, 2, 6, rows, cols, v, 5, BMS_DEVICE, (char*)out + 8) == BMS_ERR_INVALID && says("aligned"));
+  REQUIRE(bms_expectation_values(&dummy, v, 6, 1, v, 6, 2, 6, rows, cols, v, 5, 7, out) == BMS_ERR_INVALID && says("bms_expectation_values: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_expectation_values(&dummy, v, 6, 1, v, 6, 2, 5, rows, cols, v, 5, BMS_HOST, out) == BMS_ERR_INVALID && says("outside [0, 5)"));
+  REQUIRE(bms_expectation_values(&dummy, v, 6, 1, v, 6, 0, 6, rows, cols, v, 5, BMS_HOST, out) == BMS_OK);
+  REQUIRE(bms_expectation_values(nullptr, v, 6, 1, v, 6, 2, 6, rows, cols, v, 5, BMS_HOST, out) == BMS_ERR_INVALID);
+  int nm = 0;
+  REQUIRE(flux_checks(&dummy, t, v, 5, v, 5, 4, 2, 2, BMS_HOST, out, out, out, out, &nm) == BMS_OK && nm == 5);
+  REQUIRE(flux_checks(&dummy, t, v, 5, nullptr, 5, 4, 2, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("NULL hdot"));
+  REQUIRE(flux_checks(&dummy, t, nullptr, 5, v, 5, 4, 2, 2, BMS_HOST, out, out, nullptr, nullptr, &nm) == BMS_OK);
+  REQUIRE(flux_checks(&dummy, t, nullptr, 5, v, 5, 4, 2, 2, BMS_HOST, out, out, out, nullptr, &nm) == BMS_ERR_INVALID && says("need h"));
+  REQUIRE(flux_checks(&dummy, nullptr, v, 5, v, 5, 4, 2, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("needs the times"));
+  REQUIRE(flux_checks(&dummy, t, v, 5, v, 5, 4, 2, 2, BMS_HOST, nullptr, nullptr, nullptr, nullptr, &nm) == BMS_ERR_INVALID);
+  REQUIRE(flux_checks(&dummy, t, v, 4, v, 5, 4, 2, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("row stride"));
+  REQUIRE(flux_checks(&dummy, t, v, 5, v, 5, 4, 1, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_UNSUPPORTED && says("ell_min = 1"));
+  REQUIRE(flux_checks(&dummy, t, v, 5, v, 5, 4, 3, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID);
+  REQUIRE(flux_checks(&dummy, t, v, 1 << 30, v, 1 << 30, 4, 2, MAX_ELL + 1, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(flux_checks(&dummy, t, v, 5, v, 5, -1, 2, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID);
+  REQUIRE(flux_checks(&dummy, t, v + 1, 5, v, 5, 4, 2, 2, BMS_DEVICE, out, out, out, out, &nm) == BMS_ERR_INVALID && says("aligned"));
+  REQUIRE(bms_poincare_fluxes(&dummy, t, v, 5, v, 5, 4, 2, 2, 7, out, out, out, out) == BMS_ERR_INVALID && says("bms_poincare_fluxes: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_poincare_fluxes(&dummy, t, v, 5, v, 5, 0, 2, 2, BMS_HOST, out, out, out, out) == BMS_OK);
+  REQUIRE(bms_poincare_fluxes(nullptr, t, v, 5, v, 5, 4, 2, 2, BMS_HOST, out, out, out, out) == BMS_ERR_INVALID);
+  std::vector<double> image((size_t)30 * 5);
+  REQUIRE(bms_flux_coefficients(2, 2, image.data()) == BMS_OK && image[(size_t)29 * 5] == 2.0);
+  REQUIRE(bms_flux_coefficients(1, 2, image.data()) == BMS_ERR_INVALID && bms_flux_coefficients(2, 2, nullptr) == BMS_ERR_INVALID);
+}
+
 }  // namespace
 
 int main() {
@@ -695,6 +760,7 @@ int main() {
   com_motion_arguments();
   dense_product_arguments();
   staged_argument_prologues();
+  flux_tables_and_triplets();
   slab_allocator();
   std::printf("host sanitizer run: %d checks, clean\n", g_checks);
   return 0;
