@@ -635,6 +635,25 @@ int64_t bms_flux_launch_shape(int n_modes, int64_t shape[3]);
  * hdot, h), 2 (the pair h, hdot); rows 27, 28: sqrt((l - m)(l + m + 1)), sqrt((l + m)(l - m + 1)); row 29: l. */
 int bms_flux_coefficients(int ell_min, int ell_max, double* image_out);
 
+/* ---- brackets of two waveforms (scri/mode_calculations.py:60-89, 106-180; scri/waveform_modes.py:574-656) in one pass over the modes --
+ * For f = a and g = b on the common range l = ell_min .. ell_max, per time step and in the (+, -, z) basis:
+ *   inner  c16[n]     sum conj(f[l,m]) g[l,m]                       (the integrand of WaveformModes.inner_product)
+ *   l_out  c16[n][3]  sum conj(f[l,m']) <l,m'|L_a|l,m> g[l,m],      a = +, -, z
+ *   ll_out c16[n][9]  sum conj(f[l,m']) <l,m'|L_a L_b|l,m> g[l,m],  ab = pp, pm, mp, mm, pz, zp, mz, zm, zz
+ * with the reference's terms, clips and coefficients (products of sqrt((l -+ m)(l +- m + 1)) and m, formed on the device).
+ * a c16[n_times][ld_a] holds l from ell_min_a on, b c16[n_times][ld_b] from ell_min_b on: the common range is read where it lies in
+ * each row.  a, b and the outputs live in `mem`; a and b may be one array.  Any output may be NULL: it is neither computed nor written
+ * (at least one is asked for).  The sum of a time step is taken in an order that depends on nothing but the common range: a slice of the
+ * time steps gives the bits of the whole call, host memory those of device memory, and an output does not depend on which others are
+ * asked for.  BMS_ERR_INVALID: a NULL that is needed, ell_max < ell_min, ell_min below ell_min_a or ell_min_b, a row stride that ends
+ * before the column (ell_max, ell_max), negative n_times, a bad mem, device arrays not aligned to 16 bytes; BMS_ERR_UNSUPPORTED: a common
+ * range whose row does not fit in LDS.  n_times == 0 writes nothing. */
+int bms_pair_brackets(bms_ctx* ctx, const void* a, int64_t ld_a, int ell_min_a, const void* b, int64_t ld_b, int ell_min_b, int64_t n_times,
+                      int ell_min, int ell_max, int mem, void* inner, void* l_out, void* ll_out);
+/* how bms_pair_brackets runs n_modes columns on the current device: shape[0] time steps per pass of one workgroup, shape[1] workgroups at
+ * most, shape[2] = 0 (the kernel reads no tables).  Returns shape[0], or 0 if a row does not fit in LDS; sizes, not a status */
+int64_t bms_pair_launch_shape(int n_modes, int64_t shape[3]);
+
 #ifdef __cplusplus
 }
 #endif

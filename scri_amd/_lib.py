@@ -209,6 +209,8 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_int32), c_vp, c_i64, c_int, c_vp]),
     "bms_flux_launch_shape": (c_i64, [c_int, ctypes.POINTER(c_i64)]),
     "bms_flux_coefficients": (c_int, [c_int, c_int, c_dp]),
+    "bms_pair_brackets": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "bms_pair_launch_shape": (c_i64, [c_int, ctypes.POINTER(c_i64)]),
 }
 
 _lib = None

@@ -12,7 +12,7 @@
 //   engine_align.hip     time-and-phase alignment from correlation moments                                   (bms_align_moments, bms_align_residual)
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
-//   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values               (bms_poincare_fluxes, bms_expectation_values)
+//   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -757,6 +757,9 @@ BMS_INTERNAL int flux_checks(bms_ctx* c, const double* t, const void* h, int64_t
                              const double* boost, int* n_modes);
 BMS_INTERNAL int expectation_checks(bms_ctx* c, const void* a, int64_t ld_a, const void* b, int64_t ld_b, int64_t n_times, int n_cols,
                                     const int32_t* rows, const int32_t* cols, const void* values, int64_t n_el, int mem, const void* out);
+BMS_INTERNAL int pair_checks(bms_ctx* c, const void* a, int64_t ld_a, int ell_min_a, const void* b, int64_t ld_b, int ell_min_b, int64_t n_times,
+                             int ell_min, int ell_max, int mem, const void* inner, const void* l_out, const void* ll_out, int* n_modes,
+                             int64_t* off_a, int64_t* off_b);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

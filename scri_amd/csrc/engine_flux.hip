@@ -1,6 +1,6 @@
 // Fluxes of energy, momentum, angular momentum and boost in one pass over the modes, and the general sparse expectation value
 // (kernels_flux.hip): the coefficient image of an l range, built on the host in long double and kept per context, and the two entries
-// behind scri_amd/flux.py
+// behind scri_amd/flux.py; the brackets of two waveforms <f|g>, <f|L_a|g>, <f|L_a L_b|g> in one pass (bms_pair_brackets)
 // (engine.h: the split of the engine by entry family; include/scri_amd.h: the C ABI)
 #include "engine.h"
 
@@ -205,5 +205,62 @@ extern "C" int bms_expectation_values(bms_ctx* c, const void* a, int64_t ld_a, i
   if ((rc = io.out("ev_out", out, (size_t)2 * n_times, &d_out))) return rc;
   TIMED(c, BMS_TAG_POINTWISE, launch_expectation_values(c->stream, d_a, ld_a, conj_a != 0, d_b, ld_b, n_times, n_cols, (const int*)d_rows, (const int*)d_cols,
                                                         (const double*)d_vals, n_el, d_out));
+  return io.finish();
+} BMS_CATCH(c)
+
+// what bms_pair_brackets refuses before it selects a device; on success *n_modes of the common range and the columns at which it starts
+// in the rows of a and b
+BMS_INTERNAL int pair_checks(bms_ctx* c, const void* a, int64_t ld_a, int ell_min_a, const void* b, int64_t ld_b, int ell_min_b, int64_t n_times,
+                             int ell_min, int ell_max, int mem, const void* inner, const void* l_out, const void* ll_out, int* n_modes,
+                             int64_t* off_a, int64_t* off_b) {
+  if (!a || !b) return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: NULL waveform");
+  if (!inner && !l_out && !ll_out) return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: every output is NULL");
+  if (n_times < 0) return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: negative n_times");
+  if (ell_max < ell_min) return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: bad ell range [%d, %d]", ell_min, ell_max);
+  if (ell_min_a < 0 || ell_min_b < 0 || ell_min < ell_min_a || ell_min < ell_min_b)
+    return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: the common range starts at ell = %d, below a row's first ell (%d, %d)", ell_min, ell_min_a, ell_min_b);
+  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "bms_pair_brackets: ell_max = %d is beyond %d", ell_max, MAX_ELL);
+  *n_modes = LM_total_size(ell_min, ell_max);
+  *off_a = (int64_t)ell_min * ell_min - (int64_t)ell_min_a * ell_min_a;
+  *off_b = (int64_t)ell_min * ell_min - (int64_t)ell_min_b * ell_min_b;
+  if (ld_a < *off_a + *n_modes || ld_b < *off_b + *n_modes)
+    return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: row stride smaller than the columns up to ell_max (%lld, %lld)", (long long)(*off_a + *n_modes),
+                (long long)(*off_b + *n_modes));
+  if (mem == BMS_DEVICE && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)inner | (uintptr_t)l_out | (uintptr_t)ll_out) & 15))
+    return fail(c, BMS_ERR_INVALID, "bms_pair_brackets: device arrays must be aligned to their elements");
+  return BMS_OK;
+}
+
+// (sizes, not statuses) how the bracket kernel would run n_modes columns on the current device: shape[0] time steps per pass of one
+// workgroup (returned as well), shape[1] workgroups at most, shape[2] = 0 (it reads no tables); returns 0 if a row does not fit in LDS
+extern "C" int64_t bms_pair_launch_shape(int n_modes, int64_t shape[3]) {
+  FluxShape S;
+  if (!shape || !pair_launch_shape(n_modes, &S)) return 0;
+  shape[0] = S.waves, shape[1] = S.groups, shape[2] = 0;
+  return S.waves;
+}
+
+extern "C" int bms_pair_brackets(bms_ctx* c, const void* a, int64_t ld_a, int ell_min_a, const void* b, int64_t ld_b, int ell_min_b, int64_t n_times,
+                                 int ell_min, int ell_max, int mem, void* inner, void* l_out, void* ll_out) try {
+  if (!c) return BMS_ERR_INVALID;
+  if (int rc0 = entry_mem(c, mem, "bms_pair_brackets", false)) return rc0;  // (the argument checks come before the device is selected)
+  int rc, n_modes = 0;
+  int64_t off_a = 0, off_b = 0;
+  if ((rc = pair_checks(c, a, ld_a, ell_min_a, b, ld_b, ell_min_b, n_times, ell_min, ell_max, mem, inner, l_out, ll_out, &n_modes, &off_a, &off_b))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  FluxShape S;
+  if (!pair_launch_shape(n_modes, &S))
+    return fail(c, BMS_ERR_UNSUPPORTED, "bms_pair_brackets: %d modes (ell = %d .. %d): one time step's row does not fit in LDS", n_modes, ell_min, ell_max);
+  CallIO io(c, mem);
+  // (host rows go up whole, from their first column to the last of the common range: the kernel reads the range where it lies)
+  const double *d_a, *d_b;
+  if ((rc = io.in("in_data", a, ((size_t)(n_times - 1) * ld_a + off_a + n_modes) * 16, &d_a))) return rc;
+  if ((rc = io.in("in_aux0", b, ((size_t)(n_times - 1) * ld_b + off_b + n_modes) * 16, &d_b))) return rc;
+  double *d_i, *d_l, *d_ll;
+  if ((rc = io.out("pair_i", inner, (size_t)2 * n_times, &d_i))) return rc;
+  if ((rc = io.out("pair_l", l_out, (size_t)6 * n_times, &d_l))) return rc;
+  if ((rc = io.out("pair_ll", ll_out, (size_t)18 * n_times, &d_ll))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_pair_brackets(c->stream, d_a + 2 * off_a, ld_a, d_b + 2 * off_b, ld_b, n_times, ell_min, ell_max, d_i, d_l, d_ll));
   return io.finish();
 } BMS_CATCH(c)

@@ -473,6 +473,12 @@ bool flux_launch_shape(int n_modes, FluxShape* S);  // false: not even one wave'
 hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const double* h, long long ld_h, const double* hdot, long long ld_hdot,
                                   long long n_times, int ell_min, int ell_max, const double* image, double* energy, double* momentum,
                                   double* angular, double* boost);
+// brackets of two waveforms (scri/mode_calculations.py:60-180): inner c16[n] = sum conj(f) g, l_out c16[n][3] = <f|L_a|g>, a = +, -, z,
+// ll_out c16[n][9] = <f|L_a L_b|g>, ab = pp, pm, mp, mm, pz, zp, mz, zm, zz (any may be null, not all) of f c16[n][ld_f], g c16[n][ld_g],
+// both pointing AT the column (ell_min, -ell_min) of rows that may hold more on either side.  One row of f per wave in LDS, no tables.
+bool pair_launch_shape(int n_modes, FluxShape* S);  // false: a row does not fit in LDS (tables_in_lds is always false)
+hipError_t launch_pair_brackets(hipStream_t stream, const double* f, long long ld_f, const double* g, long long ld_g, long long n_times,
+                                int ell_min, int ell_max, double* inner, double* l_out, double* ll_out);
 // out c16[n] = sum_e op(a[t][rows_e]) values_e b[t][cols_e] for triplets on the device, indices inside [0, n_cols) (the entry checks them)
 int expectation_max_cols();
 hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,

@@ -14,6 +14,7 @@
 // for any n_modes and ld), lane j sums the columns j, j + 64, ... in that order, and the sixteen partial sums are added across the wave by
 // a butterfly.  Nothing in that order depends on the launch geometry, so a step's result does not depend on the steps around it, on the
 // number of waves or workgroups, or on which outputs were asked for.  No contraction: every multiply-add is spelled out.
+// The brackets of two waveforms (pair_kernel below: <f|g>, <f|L_a|g>, <f|L_a L_b|g>) share that frame, the wave sum and the LDS-room rule.
 #include "wigner.h"
 #include "kernels.h"
 
@@ -176,6 +177,106 @@ __global__ __launch_bounds__(256) void expectation_kernel(const double* __restri
   }
 }
 
+// Brackets of two waveforms f, g (scri/mode_calculations.py:60-89, 106-180) per time step, in the (+, -, z) basis:
+//     I = sum conj(f_i) g_i;   <L_a> = sum conj(f_{i'}) <l, m'| L_a |l, m> g_i;   <L_a L_b> likewise
+// With q_k = conj(f[i + k]) g[i], k = -2 .. 2 (inside the l block of column i = (l, m)) and lp = sqrt((l - m)(l + m + 1)),
+// lm = sqrt((l + m)(l - m + 1)), the thirteen brackets are real multiples of the five products:
+//     q_0:  I 1, z m, zz m^2, pm lm^2 = (l + m)(l - m + 1) (m - 1 >= -l), mp lp^2 = (l - m)(l + m + 1) (m + 1 <= l)
+//     q_+1: p lp, pz lp m, zp (m + 1) lp (m + 1 <= l);        q_-1: m lm, mz lm m, zm (m - 1) lm (m - 1 >= -l)
+//     q_+2: pp sqrt((l - m - 1)(l + m + 2)) lp (m + 2 <= l);   q_-2: mm sqrt((l + m - 1)(l - m + 2)) lm (m - 2 >= -l)
+// Geometry and order as the flux kernel's: one wave per step, the row of f in LDS (its neighbours are read), g at its own column straight
+// from memory, lane j sums the columns j, j + 64, ... in that order, a butterfly closes.  GROUPS: bit 0 I, bit 1 <L>, bit 2 <LL>; an
+// accumulator's chain of operations is the same in every instantiation.
+template <int GROUPS>
+__global__ __launch_bounds__(64 * FLUX_MAX_WAVES) void pair_kernel(const double* __restrict__ F, long long ld_f, const double* __restrict__ G,
+                                                                   long long ld_g, long long n_times, int ell_min, int n,
+                                                                   double* __restrict__ inner, double* __restrict__ l_out,
+                                                                   double* __restrict__ ll_out) {
+#pragma clang fp contract(off)
+  extern __shared__ double2 pair_lds[];  // [waves][n] rows of f
+  constexpr bool W_I = GROUPS & 1, W_L = GROUPS & 2, W_LL = GROUPS & 4;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double2* frow = pair_lds + (size_t)wave * n;
+  const long long pass_steps = (long long)gridDim.x * waves, passes = (n_times + pass_steps - 1) / pass_steps;
+  const int base = ell_min * ell_min;
+  for (long long pass = 0; pass < passes; ++pass) {  // (every wave takes every barrier: the trip count is the workgroup's)
+    const long long step = pass * pass_steps + (long long)blockIdx.x * waves + wave;
+    const bool live = step < n_times;
+    if (live)
+      for (int i = lane; i < n; i += 64) frow[i] = *reinterpret_cast<const double2*>(F + (step * ld_f + i) * 2);
+    __syncthreads();
+    if (live) {
+      double I[2] = {0, 0}, L[6] = {0, 0, 0, 0, 0, 0}, LL[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      auto add = [](double* acc, double c, double qr, double qi) { acc[0] = fma(c, qr, acc[0]), acc[1] = fma(c, qi, acc[1]); };
+      int l = ell_min;
+      for (int i = lane; i < n; i += 64) {
+        while (i + base >= (l + 1) * (l + 1)) ++l;
+        const int m = i + base - l * (l + 1);
+        const double2 g = *reinterpret_cast<const double2*>(G + (step * ld_g + i) * 2);
+        auto q = [&](int k, double& qr, double& qi) {  // conj(f[i + k]) g[i]
+          const double2 f = frow[i + k];
+          qr = fma(f.x, g.x, f.y * g.y), qi = fma(f.x, g.y, -(f.y * g.x));
+        };
+        const double md = (double)m;
+        double qr, qi;
+        q(0, qr, qi);
+        if (W_I) add(I, 1.0, qr, qi);
+        if (W_L) add(L + 4, md, qr, qi);
+        if (W_LL) {
+          add(LL + 16, md * md, qr, qi);
+          if (m - 1 >= -l) add(LL + 2, (double)((l + m) * (l - m + 1)), qr, qi);
+          if (m + 1 <= l) add(LL + 4, (double)((l - m) * (l + m + 1)), qr, qi);
+        }
+        if ((W_L || W_LL) && m + 1 <= l) {
+          const double lp = sqrt((double)((l - m) * (l + m + 1)));
+          q(1, qr, qi);
+          if (W_L) add(L + 0, lp, qr, qi);
+          if (W_LL) {
+            add(LL + 8, lp * md, qr, qi);
+            add(LL + 10, (md + 1.0) * lp, qr, qi);
+            if (m + 2 <= l) {
+              q(2, qr, qi);
+              add(LL + 0, sqrt((double)((l - m - 1) * (l + m + 2))) * lp, qr, qi);
+            }
+          }
+        }
+        if ((W_L || W_LL) && m - 1 >= -l) {
+          const double lm = sqrt((double)((l + m) * (l - m + 1)));
+          q(-1, qr, qi);
+          if (W_L) add(L + 2, lm, qr, qi);
+          if (W_LL) {
+            add(LL + 12, lm * md, qr, qi);
+            add(LL + 14, (md - 1.0) * lm, qr, qi);
+            if (m - 2 >= -l) {
+              q(-2, qr, qi);
+              add(LL + 6, sqrt((double)((l + m - 1) * (l - m + 2))) * lm, qr, qi);
+            }
+          }
+        }
+      }
+      if (W_I) {
+        I[0] = wave_sum(I[0]), I[1] = wave_sum(I[1]);
+        if (lane == 0 && inner) inner[2 * step] = I[0], inner[2 * step + 1] = I[1];
+      }
+      if (W_L) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) L[k] = wave_sum(L[k]);
+        if (lane == 0 && l_out)
+#pragma unroll
+          for (int k = 0; k < 6; ++k) l_out[6 * step + k] = L[k];
+      }
+      if (W_LL) {
+#pragma unroll
+        for (int k = 0; k < 18; ++k) LL[k] = wave_sum(LL[k]);
+        if (lane == 0 && ll_out)
+#pragma unroll
+          for (int k = 0; k < 18; ++k) ll_out[18 * step + k] = LL[k];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 int compute_units() {
   int dev = 0, cus = 0;
   (void)hipGetDevice(&dev);
@@ -188,24 +289,31 @@ int compute_units() {
 
 int flux_image_doubles(int n_modes) { return FLUX_IMAGE_PER_MODE * n_modes; }
 
-// 8, 4, 2 or 1 waves with the image in LDS while both fit; beyond that the image stays in global memory and the waves' rows have the LDS
-bool flux_launch_shape(int n_modes, FluxShape* S) {
-  if (n_modes < 1) return false;
+// THE LDS-room rule of the one-wave-per-step kernels: the most waves (8, 4, 2 or 1) whose rows of `row_bytes` each fit in LDS beside
+// `table_bytes`, and as many workgroups as the device holds at once: by LDS, and by its 32 waves per compute unit.  false: not one fits
+static bool fit_waves(size_t row_bytes, size_t table_bytes, FluxShape* S) {
   int dev = 0;
   (void)hipGetDevice(&dev);
-  const size_t room = (size_t)lds_per_workgroup(dev), row_pair = (size_t)32 * n_modes, image = (size_t)8 * flux_image_doubles(n_modes);
+  const size_t room = (size_t)lds_per_workgroup(dev);
   FluxShape s{};
   for (int w = FLUX_MAX_WAVES; w >= 1 && !s.waves; w >>= 1)
-    if (w * row_pair + image <= room) s.waves = w, s.tables_in_lds = true, s.lds_bytes = w * row_pair + image;
-  for (int w = FLUX_MAX_WAVES; w >= 1 && !s.waves; w >>= 1)
-    if (w * row_pair <= room) s.waves = w, s.tables_in_lds = false, s.lds_bytes = w * row_pair;
+    if (w * row_bytes + table_bytes <= room) s.waves = w, s.tables_in_lds = table_bytes > 0, s.lds_bytes = w * row_bytes + table_bytes;
   if (!s.waves) return false;
-  // as many workgroups as the device holds at once: by LDS, and by its 32 waves per compute unit
   const long long per_cu = std::max<long long>(1, std::min<long long>((long long)(room / s.lds_bytes), 32 / s.waves));
   s.groups = (int)std::min<long long>(per_cu * compute_units(), 1 << 20);
   *S = s;
   return true;
 }
+
+// the image in LDS while it fits beside the rows; beyond that it stays in global memory and the waves' rows have the LDS
+bool flux_launch_shape(int n_modes, FluxShape* S) {
+  if (n_modes < 1) return false;
+  const size_t row_pair = (size_t)32 * n_modes, image = (size_t)8 * flux_image_doubles(n_modes);
+  return fit_waves(row_pair, image, S) || fit_waves(row_pair, 0, S);
+}
+
+// one row of f per wave; no tables
+bool pair_launch_shape(int n_modes, FluxShape* S) { return n_modes >= 1 && fit_waves((size_t)16 * n_modes, 0, S); }
 
 hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const double* h, long long ld_h, const double* hdot, long long ld_hdot,
                                   long long n_times, int ell_min, int ell_max, const double* image, double* energy, double* momentum,
@@ -228,6 +336,35 @@ hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const dou
   };
   if (with_h) return S.tables_in_lds ? go(flux_kernel<true, true>) : go(flux_kernel<true, false>);
   return S.tables_in_lds ? go(flux_kernel<false, true>) : go(flux_kernel<false, false>);
+}
+
+// inner c16[n], l_out c16[n][3] (+, -, z), ll_out c16[n][9] (pp, pm, mp, mm, pz, zp, mz, zm, zz), any may be null, of the rows f, g
+// c16[n][ld] that START at column (ell_min, -ell_min) and hold n_modes columns of the common range
+hipError_t launch_pair_brackets(hipStream_t stream, const double* f, long long ld_f, const double* g, long long ld_g, long long n_times,
+                                int ell_min, int ell_max, double* inner, double* l_out, double* ll_out) {
+  if (n_times <= 0) return hipSuccess;
+  const int n = (ell_max + 1) * (ell_max + 1) - ell_min * ell_min;
+  FluxShape S;
+  if (!f || !g || (!inner && !l_out && !ll_out) || !pair_launch_shape(n, &S)) return hipErrorInvalidValue;
+  const long long groups = std::min<long long>(S.groups, (n_times + S.waves - 1) / S.waves);
+  auto go = [&](auto kernel) -> hipError_t {
+    if (S.lds_bytes > 64 * 1024) {
+      hipError_t e = allow_dynamic_lds((const void*)kernel);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * S.waves), S.lds_bytes, stream, f, ld_f, g, ld_g, n_times, ell_min, n, inner, l_out,
+                       ll_out);
+    return hipGetLastError();
+  };
+  switch ((inner ? 1 : 0) | (l_out ? 2 : 0) | (ll_out ? 4 : 0)) {
+    case 1: return go(pair_kernel<1>);
+    case 2: return go(pair_kernel<2>);
+    case 3: return go(pair_kernel<3>);
+    case 4: return go(pair_kernel<4>);
+    case 5: return go(pair_kernel<5>);
+    case 6: return go(pair_kernel<6>);
+    default: return go(pair_kernel<7>);
+  }
 }
 
 int expectation_max_cols() {

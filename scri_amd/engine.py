@@ -1119,6 +1119,50 @@ def expectation_values(a, rows, cols, values, b, conj_a=False, ctx=None):
     return out
 
 
+PAIR_NAMES = ("inner", "L", "LL")
+_PAIR_WIDTH = {"inner": None, "L": 3, "LL": 9}
+
+
+def pair_launch_shape(n_modes):
+    """(time steps per pass of one workgroup, workgroups at most) of the bracket kernel for n_modes columns on the current device
+    (bms_pair_launch_shape); None if a row does not fit in LDS"""
+    shape = (c_i64 * 3)()
+    if not _lib.load().bms_pair_launch_shape(int(n_modes), shape):
+        return None
+    return int(shape[0]), int(shape[1])
+
+
+def pair_brackets(a, b, ell_min, ell_max, ell_min_a=None, ell_min_b=None, want=PAIR_NAMES, ctx=None):
+    """bms_pair_brackets: the brackets named in `want` of the modes a and b on the common range l = ell_min .. ell_max, per time step and
+    in the (+, -, z) basis, in one launch -- "inner" [N]: sum conj(a) b; "L" [N, 3]: <a|L_a|b>, a = +, -, z; "LL" [N, 9]: <a|L_a L_b|b>,
+    ab = pp, pm, mp, mm, pz, zp, mz, zm, zz.  a and b are numpy arrays (numpy arrays out) or device tensors (complex128, unit column
+    stride, any row stride: device tensors out), both in the same memory; their rows start at l = ell_min_a and ell_min_b (default:
+    ell_min) and may go on beyond ell_max: the common range is read where it lies.  Returns the results in the order of `want` (a
+    tuple); one name as a string returns that array alone."""
+    ctx = _ctx(ctx)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or len(set(names)) != len(names) or not set(names) <= set(PAIR_NAMES):
+        raise ValueError(f"want names {', '.join(repr(k) for k in PAIR_NAMES)}, got {want!r}")
+    ell_min_a = ell_min if ell_min_a is None else ell_min_a
+    ell_min_b = ell_min if ell_min_b is None else ell_min_b
+    A = _stage(ctx, a, np.complex128, "a", shape=(None, None))
+    B = _stage(ctx, b, np.complex128, "b", shape=(A.rows, None))
+    if A.mem != B.mem:
+        raise ValueError("a and b must live in the same memory")
+    if 0 <= ell_min_a <= ell_min <= ell_max and 0 <= ell_min_b <= ell_min:  # (any other range: the entry refuses it)
+        for x, first, name in ((A, ell_min_a, "a"), (B, ell_min_b, "b")):
+            if x.cols < (ell_max + 1) ** 2 - first**2:
+                raise ValueError(f"{name} has {x.cols} columns: rows from l = {first} to {ell_max} hold {(ell_max + 1) ** 2 - first**2}")
+    out = {k: out_like(A, (A.rows,) if _PAIR_WIDTH[k] is None else (A.rows, _PAIR_WIDTH[k]), np.complex128) for k in names}
+    if A.rows:
+        ptr = lambda k: out[k][0] if k in out else None  # noqa: E731
+        rc = _lib.load().bms_pair_brackets(ctx.handle, A.ptr, A.ld, int(ell_min_a), B.ptr, B.ld, int(ell_min_b), A.rows, int(ell_min), int(ell_max),
+                                           A.mem, ptr("inner"), ptr("L"), ptr("LL"))
+        ctx.check(rc, "bms_pair_brackets")
+    res = tuple(out[k][1] for k in names)
+    return res[0] if isinstance(want, str) else res
+
+
 PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
 
 

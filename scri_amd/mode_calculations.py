@@ -9,7 +9,8 @@ LLDominantEigenvector (:316-399) is bms_coprecessing_frame without the frame: a 
 choice that makes the axis continuous as a scan of sign maps.
 
 The modes of a device-resident waveform are read where they are: only per-step quantities (vectors, 3 x 3 matrices, rotors) come
-to the host.
+to the host.  That holds for the two-waveform forms LVector and LLComparisonMatrix too (:60-180): with a device-resident waveform on
+either side they are one bms_pair_brackets launch over both rows; two host-resident waveforms keep the composition of ladder operators.
 """
 import numpy as np
 
@@ -154,22 +155,63 @@ def _braket(W1, W2):
     return np.einsum("ij, ij -> i", np.conjugate(W1.data), W2.data)
 
 
-def LVector(W1, W2):
-    r"""<L>^a = \sum \bar f^{l,m'} <l,m'|L_a|l,m> g^{l,m} for two waveforms with the same modes; complex [n_times, 3], mode frame"""
-    Lp, Lm, Lz = (_braket(W1, _ladder_applied(W2, w)) for w in "+-z")
-    return np.stack([0.5 * (Lp + Lm), -0.5j * (Lp - Lm), Lz], axis=1)
+def _is_resident(W):
+    return getattr(W, "is_device_resident", False) and len(W._data_shape()) == 2
 
 
-def LLComparisonMatrix(W1, W2):
-    r"""<LL>^{ab} = \sum \bar f^{l,m'} <l,m'|L_a L_b|l,m> g^{l,m}; complex [n_times, 3, 3].
+def _either_resident(W1, W2):
+    return _is_resident(W1) or _is_resident(W2)
 
-    As in the reference (scri/mode_calculations.py:187), the <L_y L_z> term is added to the (y, y) element and the (y, z) element
-    stays zero -- a slip of an index there, kept so that the numbers are the reference's."""
+
+def pair_brackets(W1, W2, want, ell_min=None, ell_max=None):
+    """The brackets `want` (engine.PAIR_NAMES) of two waveforms of which at least one is device resident, on l = ell_min .. ell_max
+    (default: the range of W1, which W2 then shares), in one bms_pair_brackets launch: device tensors.  The range is read where it lies in
+    either row; a host-resident partner is uploaded for the call and stays host resident; nobody's `data` is read."""
+    from . import device_series
+
+    resident = [W for W in (W1, W2) if _is_resident(W)]
+    if len(resident) == 2 and W1._ctx is not W2._ctx:
+        raise ValueError("the two device-resident waveforms live on different contexts")
+    ctx = resident[0]._ctx
+    if ell_min is None:
+        if (W1.ell_min, W1.ell_max) != (W2.ell_min, W2.ell_max):
+            raise ValueError(f"the waveforms hold different modes: l = {W1.ell_min} .. {W1.ell_max} and {W2.ell_min} .. {W2.ell_max}")
+        ell_min, ell_max = W1.ell_min, W1.ell_max
+    if W1.n_times != W2.n_times:
+        raise ValueError(f"the waveforms hold {W1.n_times} and {W2.n_times} time steps")
+    a, b = (W._dev if _is_resident(W) else device_series.to_device(ctx, np.ascontiguousarray(W.data, dtype=complex)) for W in (W1, W2))
+    return engine.pair_brackets(a, b, ell_min, ell_max, W1.ell_min, W2.ell_min, want=want, ctx=ctx)
+
+
+def _plus_minus_z(W1, W2, which):
+    """the brackets "L" [n, 3] or "LL" [n, 9] in the (+, -, z) basis on the host: one launch with a device-resident waveform, else the
+    composition of ladder operators on host data"""
+    if _either_resident(W1, W2):
+        return pair_brackets(W1, W2, which).cpu().numpy()
+    if which == "L":
+        return np.stack([_braket(W1, _ladder_applied(W2, w)) for w in "+-z"], axis=1)
     T = {}
     for b in "+-z":
         right = _ladder_applied(W2, b)
         for a in "+-z":
             T[a + b] = _braket(W1, _ladder_applied(right, a))
+    return np.stack([T[k] for k in ("++", "+-", "-+", "--", "+z", "z+", "-z", "z-", "zz")], axis=1)
+
+
+def LVector(W1, W2):
+    r"""<L>^a = \sum \bar f^{l,m'} <l,m'|L_a|l,m> g^{l,m} for two waveforms with the same modes; complex [n_times, 3], mode frame.
+    Device-resident waveforms are read in HBM (bms_pair_brackets) and stay resident."""
+    Lp, Lm, Lz = _plus_minus_z(W1, W2, "L").T
+    return np.stack([0.5 * (Lp + Lm), -0.5j * (Lp - Lm), Lz], axis=1)
+
+
+def LLComparisonMatrix(W1, W2):
+    r"""<LL>^{ab} = \sum \bar f^{l,m'} <l,m'|L_a L_b|l,m> g^{l,m}; complex [n_times, 3, 3].  Device-resident waveforms are read in HBM
+    (bms_pair_brackets) and stay resident.
+
+    As in the reference (scri/mode_calculations.py:187), the <L_y L_z> term is added to the (y, y) element and the (y, z) element
+    stays zero -- a slip of an index there, kept so that the numbers are the reference's."""
+    T = dict(zip(("++", "+-", "-+", "--", "+z", "z+", "-z", "z-", "zz"), _plus_minus_z(W1, W2, "LL").T))
     LL = np.empty((W1.n_times, 3, 3), dtype=complex)
     LL[:, 0, 0] = (T["++"] + T["+-"] + T["-+"] + T["--"]) / 4
     LL[:, 0, 1] = -1j * (T["++"] - T["+-"] + T["-+"] - T["--"]) / 4

@@ -240,8 +240,12 @@ class ModeOperators:
     def inner_product(self, b, t1=None, t2=None, allow_LM_differ=False, allow_times_differ=False):
         """The all-angles inner product <self, b>: integral over [t1, t2] of sum_lm conj(self_lm) b_lm (cubic-spline quadrature
         of the samples, as quaternion.calculus.spline_definite_integral does)."""
+        from . import mode_calculations
+
         if self.spin_weight != b.spin_weight:
             raise ValueError("Spin weights must match in inner_product")
+        if mode_calculations._either_resident(self, b):
+            return self._inner_product_in_hbm(b, t1, t2, allow_LM_differ, allow_times_differ)
         A, B = self, b
         if (self.ell_min != b.ell_min) or (self.ell_max != b.ell_max):
             if not allow_LM_differ:
@@ -260,6 +264,32 @@ class ModeOperators:
         t2 = times[-1] if t2 is None else t2
         integrand = np.sum(np.conjugate(A.data) * B.data, axis=1)
         ends = engine.spline_derivative(times, integrand[:, np.newaxis], np.array([t1, t2], dtype=float), order=-1, ctx=self._ctx)
+        return complex(ends[1, 0] - ends[0, 0])
+
+    def _inner_product_in_hbm(self, b, t1, t2, allow_LM_differ, allow_times_differ):
+        """inner_product with a device-resident waveform on either side (the checks, their texts and their order are those above): the
+        common l range is read where it lies in both rows (bms_pair_brackets), times that differ go through the resident interpolate,
+        the integrand stays in HBM for the spline quadrature, and two complex numbers come to the host.  Nobody changes residence."""
+        from . import mode_calculations
+
+        ell_min, ell_max = self.ell_min, self.ell_max
+        if (self.ell_min != b.ell_min) or (self.ell_max != b.ell_max):
+            if not allow_LM_differ:
+                raise ValueError("ell_min and ell_max must match in inner_product (use allow_LM_differ=True to override)")
+            ell_min, ell_max = max(self.ell_min, b.ell_min), min(self.ell_max, b.ell_max)
+            if ell_min > ell_max:
+                raise ValueError("Intersection of (ell,m) modes is empty.  Assuming this is not desired.")
+        A, B, times = self, b, self.t
+        if not np.array_equal(self.t, b.t):
+            if not allow_times_differ:
+                raise ValueError("Time samples must match in inner_product (use allow_times_differ=True to override)")
+            times = time_intersection(self.t, b.t)
+            A, B = A.interpolate(times), B.interpolate(times)
+        t1 = times[0] if t1 is None else t1
+        t2 = times[-1] if t2 is None else t2
+        integrand = mode_calculations.pair_brackets(A, B, "inner", ell_min, ell_max)
+        ctx = next(W._ctx for W in (A, B) if mode_calculations._is_resident(W))
+        ends = engine.spline_derivative(times, integrand[:, None], np.array([t1, t2], dtype=float), order=-1, ctx=ctx).cpu().numpy()
         return complex(ends[1, 0] - ends[0, 0])
 
     # ------------------------------------------------------------------ what the object says about itself (waveform_base.py:425-516)

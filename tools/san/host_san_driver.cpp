@@ -735,6 +735,22 @@ void flux_tables_and_triplets() {
   std::vector<double> image((size_t)30 * 5);
   REQUIRE(bms_flux_coefficients(2, 2, image.data()) == BMS_OK && image[(size_t)29 * 5] == 2.0);
   REQUIRE(bms_flux_coefficients(1, 2, image.data()) == BMS_ERR_INVALID && bms_flux_coefficients(2, 2, nullptr) == BMS_ERR_INVALID);
+  // the brackets of a pair: the common range l = 2..3 (12 columns) inside rows that start at l = 2 and at l = 0
+  int64_t off_a = -1, off_b = -1;
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 16, 0, 2, 2, 3, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_OK && nm == 12 && off_a == 0 && off_b == 4);
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 15, 0, 2, 2, 3, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("row stride"));
+  REQUIRE(pair_checks(&dummy, v, 11, 2, v, 16, 0, 2, 2, 3, BMS_HOST, out, nullptr, nullptr, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("row stride"));
+  REQUIRE(pair_checks(&dummy, nullptr, 12, 2, v, 16, 0, 2, 2, 3, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("NULL waveform"));
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 16, 0, 2, 2, 3, BMS_HOST, nullptr, nullptr, nullptr, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("every output"));
+  REQUIRE(pair_checks(&dummy, v, 12, 3, v, 16, 0, 2, 2, 3, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("below a row's first ell"));
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 16, -1, 2, 2, 3, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID);
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 16, 0, 2, 3, 2, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("bad ell range [3, 2]"));
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 16, 0, -1, 2, 3, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("negative n_times"));
+  REQUIRE(pair_checks(&dummy, v, 1 << 30, 2, v, 1 << 30, 0, 2, 2, MAX_ELL + 1, BMS_HOST, out, out, out, &nm, &off_a, &off_b) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(pair_checks(&dummy, v, 12, 2, v, 16, 0, 2, 2, 3, BMS_DEVICE, out, out + 1, out, &nm, &off_a, &off_b) == BMS_ERR_INVALID && says("aligned"));
+  REQUIRE(bms_pair_brackets(&dummy, v, 12, 2, v, 16, 0, 2, 2, 3, 7, out, out, out) == BMS_ERR_INVALID && says("bms_pair_brackets: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_pair_brackets(&dummy, v, 12, 2, v, 16, 0, 0, 2, 3, BMS_HOST, out, out, out) == BMS_OK);
+  REQUIRE(bms_pair_brackets(nullptr, v, 12, 2, v, 16, 0, 2, 2, 3, BMS_HOST, out, out, out) == BMS_ERR_INVALID);
 }
 
 }  // namespace
