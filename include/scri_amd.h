@@ -654,6 +654,32 @@ int bms_pair_brackets(bms_ctx* ctx, const void* a, int64_t ld_a, int ell_min_a, 
  * most, shape[2] = 0 (the kernel reads no tables).  Returns shape[0], or 0 if a row does not fit in LDS; sizes, not a status */
 int64_t bms_pair_launch_shape(int n_modes, int64_t shape[3]);
 
+/* ---- Bondi charges of AsymptoticBondiData rows (scri/asymptotic_bondi_data/bms_charges.py:14-200) in one pass over the modes ---------
+ * four_momentum f8[n][4] (:79-88), angular f8[n][3] (:91-106), boost f8[n][3] (:163-182) and com f8[n][3] (:185-200) of psi1, psi2, sigma
+ * and sigma_dot = d sigma / dt, rows c16[n_times][ld] stored from l = 0 as AsymptoticBondiData stores them ((ell_max + 1)^2 columns of
+ * sigma and sigma_dot are read, the first four of psi1 and psi2).  The fields and the outputs live in `mem`; t is a host f8[n_times].
+ * Any output may be NULL: it is neither computed nor written (at least one is asked for).  sigma_dot and psi2 may be NULL when neither
+ * `four_momentum` nor `boost` is asked for, psi1 when `four_momentum` alone is, t when `boost` is not.  The l <= 1 modes of the products
+ * sigma sigma-bar-dot, sigma eth sigma-bar and sigma sigma-bar are sums over the columns of sigma and their nine neighbours with three
+ * real coefficient sets, built in long double and kept per context and ell_max; nothing is synthesised on a grid.  The sum of a time step
+ * is taken in an order that depends on nothing but ell_max: two calls give the same bits, a slice of the time steps gives the bits of the
+ * whole call, row strides change no bit, and an output does not depend on which others are asked for.
+ * BMS_ERR_INVALID: a NULL that is needed, a row stride below the columns read, negative n_times or ell_max, a bad mem, misaligned device
+ * arrays; BMS_ERR_UNSUPPORTED: ell_max < 2 (no shear), rows that do not fit in LDS.  All of it is found on the host before anything is
+ * launched.  n_times == 0 writes nothing. */
+int bms_bondi_charges(bms_ctx* ctx, const double* t, const void* psi1, int64_t ld_psi1, const void* psi2, int64_t ld_psi2, const void* sigma,
+                      int64_t ld_sigma, const void* sigma_dot, int64_t ld_sigma_dot, int64_t n_times, int ell_max, int mem,
+                      double* four_momentum, double* angular, double* boost, double* com);
+/* how bms_bondi_charges runs n_modes = (ell_max + 1)^2 columns on the current device, as bms_flux_launch_shape: shape[0] time steps per
+ * pass of one workgroup (returned as well, 0 if the rows of one time step do not fit in LDS), shape[1] workgroups at most, shape[2] != 0
+ * if the coefficient tables are held in LDS (they are while that costs no wave; else they are read through L2); sizes, not a status */
+int64_t bms_charge_launch_shape(int n_modes, int64_t shape[3]);
+/* pure host routine: the coefficient tables of l = 0 .. ell_max (ell_max >= 2) as the kernel reads them, image_out f8[20][(ell_max + 1)^2]:
+ * row 2 k + set for the neighbour k = 3 (dl + 1) + (mu + 1) of a column (l, m) of sigma -- the column (l + dl, m + mu) of sigma or
+ * sigma_dot, which contributes to the mode M = -mu -- and set 0 (A1: spins (2, -2) -> L = 1), 1 (B: spins (2, -1) -> L = 1 with the GHP
+ * factor of eth on sigma-bar); row 18: A0 (spins (2, -2) -> L = 0, the column itself); row 19: l. */
+int bms_charge_coefficients(int ell_max, double* image_out);
+
 #ifdef __cplusplus
 }
 #endif

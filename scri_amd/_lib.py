@@ -211,6 +211,9 @@ SIGNATURES = {
     "bms_flux_coefficients": (c_int, [c_int, c_int, c_dp]),
     "bms_pair_brackets": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "bms_pair_launch_shape": (c_i64, [c_int, ctypes.POINTER(c_i64)]),
+    "bms_bondi_charges": (c_int, [c_vp, c_dp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "bms_charge_launch_shape": (c_i64, [c_int, ctypes.POINTER(c_i64)]),
+    "bms_charge_coefficients": (c_int, [c_int, c_dp]),
 }
 
 _lib = None

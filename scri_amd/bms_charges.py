@@ -2,6 +2,10 @@
 transformation path.  Products of fields run on the GPU (ModesTimeSeries.multiply ->
 bms_grid_multiply on a grid that is exact for l_a + l_b), time derivatives through bms_spline_derivative; what is left
 here is the bookkeeping of the formulas.  The functions are grafted onto AsymptoticBondiData as methods.
+
+The Bondi charges P, J, N, G need the l <= 1 modes of their aspects only.  Of a device-resident object with ell_max >= 2 they come from
+ONE launch over the modes (bondi_charges -> bms_bondi_charges) after one spline derivative of sigma in HBM: no grid is built.  Host-resident
+objects, the full-band mass_aspect, the supermomenta and CWWY_angular_momentum keep the route through the products.
 """
 from math import sqrt
 
@@ -52,6 +56,34 @@ def _minkowski_norm_squared(P):
     return P[..., 0] ** 2 - np.einsum("...i,...i->...", P[..., 1:], P[..., 1:])
 
 
+def _one_pass(self):
+    """whether the charges of this object come from the one-pass kernel: fields in HBM and a shear to read"""
+    return getattr(self, "is_device_resident", False) and self.ell_max >= 2
+
+
+_CHARGES = ("four_momentum", "angular", "boost", "com")
+
+
+def _charges_on_device(self, want):
+    """the charges named in `want` (engine.CHARGE_NAMES) of a device-resident object as host arrays, in one launch; sigma is
+    differentiated (once, in HBM) only where the four-momentum or the boost charge is wanted"""
+    from . import engine
+
+    raw = self._raw_dev  # psi0 .. psi4, sigma
+    with_dot = "four_momentum" in want or "boost" in want
+    sigma_dot = engine.spline_derivative(self.t, raw[5], self.t, 1, ctx=self._ctx) if with_dot else None
+    out = engine.bondi_charges(self.t, raw[1], raw[2] if with_dot else None, raw[5], sigma_dot, self.ell_max, want=tuple(want), ctx=self._ctx)
+    return tuple(o.cpu().numpy() for o in out)
+
+
+def bondi_charges(self):
+    """(P [N, 4], J [N, 3], N [N, 3], G [N, 3]): bondi_four_momentum, bondi_angular_momentum, bondi_boost_charge and bondi_CoM_charge
+    together; of a device-resident object one derivative of sigma and one launch"""
+    if _one_pass(self):
+        return _charges_on_device(self, _CHARGES)
+    return self.bondi_four_momentum(), self.bondi_angular_momentum(), self.bondi_boost_charge(), self.bondi_CoM_charge()
+
+
 def bondi_rest_mass(self):
     """Rest mass of the Bondi four-momentum (bms_charges.py:72-76)"""
     return np.sqrt(_minkowski_norm_squared(self.bondi_four_momentum()))
@@ -75,6 +107,8 @@ def _dipole_product(a, b):
 
 def bondi_four_momentum(self):
     """l < 2 part of the mass aspect as a four-vector (bms_charges.py:79-88)"""
+    if _one_pass(self):
+        return _charges_on_device(self, ("four_momentum",))[0]
     return _four_vector(self.mass_aspect(_DIPOLE))
 
 
@@ -85,6 +119,8 @@ def _psi1_sigma_term(self, ell_max):
 
 def bondi_angular_momentum(self):
     """Total Bondi angular momentum vector from i (psi1 + sigma eth sigma-bar)  (bms_charges.py:91-106)"""
+    if _one_pass(self):
+        return _charges_on_device(self, ("angular",))[0]
     return _three_vector(1j * _psi1_sigma_term(self, _DIPOLE))
 
 
@@ -97,19 +133,26 @@ def _com_aspect(self):
 def bondi_boost_charge(self):
     """N = G - t P as an aspect: - [psi1 + sigma eth sigma-bar + (1/2) eth(sigma sigma-bar) - t eth Re{psi2 + sigma d_t sigma-bar}]
     (bms_charges.py:163-182)"""
+    if _one_pass(self):
+        return _charges_on_device(self, ("boost",))[0]
     energy_density = (self.psi2.truncate_ell(_DIPOLE) + _dipole_product(self.sigma, self.sigma.bar.dot)).real
     return _three_vector(_com_aspect(self) + self.t[:, np.newaxis] * energy_density.eth_GHP)
 
 
 def bondi_CoM_charge(self):
     """G = N + t P = - [psi1 + sigma eth sigma-bar + (1/2) eth(sigma sigma-bar)]  (bms_charges.py:185-200)"""
+    if _one_pass(self):
+        return _charges_on_device(self, ("com",))[0]
     return _three_vector(_com_aspect(self))
 
 
 def bondi_dimensionless_spin(self):
     """Dimensionless Bondi spin vector chi = [gamma (J + v x N) - (gamma - 1) (J . v^) v^] / M^2 with v = p / E
     (bms_charges.py:139-160), as one expression on (P, J, N)."""
-    P, J, N = self.bondi_four_momentum(), self.bondi_angular_momentum(), self.bondi_boost_charge()
+    if _one_pass(self):
+        P, J, N = _charges_on_device(self, ("four_momentum", "angular", "boost"))
+    else:
+        P, J, N = self.bondi_four_momentum(), self.bondi_angular_momentum(), self.bondi_boost_charge()
     velocity = P[:, 1:] / P[:, :1]
     speed = np.sqrt(np.einsum("ti,ti->t", velocity, velocity))[:, np.newaxis]
     direction = np.divide(velocity, speed, out=velocity.copy(), where=speed != 0)  # (a vanishing velocity has no direction: kept)
@@ -164,6 +207,6 @@ def supermomentum(self, supermomentum_def, **kwargs):
 
 
 METHODS = (
-    mass_aspect, bondi_rest_mass, bondi_four_momentum, bondi_angular_momentum, bondi_boost_charge, bondi_CoM_charge,
+    mass_aspect, bondi_charges, bondi_rest_mass, bondi_four_momentum, bondi_angular_momentum, bondi_boost_charge, bondi_CoM_charge,
     bondi_dimensionless_spin, CWWY_angular_momentum, supermomentum,
 )

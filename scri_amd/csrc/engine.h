@@ -12,7 +12,7 @@
 //   engine_align.hip     time-and-phase alignment from correlation moments                                   (bms_align_moments, bms_align_residual)
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
-//   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets)
+//   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair, Bondi charges (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets, bms_bondi_charges)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -220,6 +220,7 @@ struct bms_ctx {
   int rot_ring_next = 0;
   std::map<std::pair<int, int>, RotResPlan> rot_res_plans;  // LDS-resident table images built so far, by (ell_min, ell_max)
   std::map<std::pair<int, int>, bool> flux_images;          // coefficient images of the fused fluxes on the device, by (ell_min, ell_max)
+  std::map<int, bool> charge_images;                        // coefficient images of the Bondi charges on the device, by ell_max
   int n_cu = 0;
   // analysis tables depend on the grid, the spin and the l range only: kept per tag until a call asks for other ones
   std::map<std::string, std::pair<std::array<int, 6>, AnalysisPlan>> plans;
@@ -760,6 +761,10 @@ BMS_INTERNAL int expectation_checks(bms_ctx* c, const void* a, int64_t ld_a, con
 BMS_INTERNAL int pair_checks(bms_ctx* c, const void* a, int64_t ld_a, int ell_min_a, const void* b, int64_t ld_b, int ell_min_b, int64_t n_times,
                              int ell_min, int ell_max, int mem, const void* inner, const void* l_out, const void* ll_out, int* n_modes,
                              int64_t* off_a, int64_t* off_b);
+BMS_INTERNAL void build_charge_image(int ell_max, std::vector<double>& image);
+BMS_INTERNAL int charge_checks(bms_ctx* c, const double* t, const void* psi1, int64_t ld_psi1, const void* psi2, int64_t ld_psi2, const void* sigma,
+                               int64_t ld_sigma, const void* sigma_dot, int64_t ld_sigma_dot, int64_t n_times, int ell_max, int mem,
+                               const double* four_momentum, const double* angular, const double* boost, const double* com, int* n_modes);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

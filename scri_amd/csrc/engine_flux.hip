@@ -1,6 +1,7 @@
 // Fluxes of energy, momentum, angular momentum and boost in one pass over the modes, and the general sparse expectation value
 // (kernels_flux.hip): the coefficient image of an l range, built on the host in long double and kept per context, and the two entries
-// behind scri_amd/flux.py; the brackets of two waveforms <f|g>, <f|L_a|g>, <f|L_a L_b|g> in one pass (bms_pair_brackets)
+// behind scri_amd/flux.py; the brackets of two waveforms <f|g>, <f|L_a|g>, <f|L_a L_b|g> in one pass (bms_pair_brackets); the Bondi
+// charges P, J, N, G of AsymptoticBondiData rows in one pass (bms_bondi_charges) with a coefficient image of their own
 // (engine.h: the split of the engine by entry family; include/scri_amd.h: the C ABI)
 #include "engine.h"
 
@@ -40,6 +41,29 @@ long double ladder_chi_element(bool raise, int lp, int l, int m, int mu) {
   const long double ratio = (2.0L * l + 1) / (2.0L * lp + 1), spin = raise ? cg_one(l, 2, -1, lp) : cg_one(l, 1, 1, lp);
   if (mu == 0) return sqrtl(2 * ratio) * cg_one(l, m, 0, lp) * spin;
   return -mu * 2 * sqrtl(ratio) * cg_one(l, m, mu, lp) * spin;
+}
+
+
+// (l1 l2 L; m1 m2 m3) for L = 0, 1, from the couplings with j = 1 above:
+//     (l1 l2 1; m1 m2 m3) = (-1)^(l1 + l2 + 1) (l1 1 l2; m1 m3 m2),   (j1 j2 j3; m1 m2 m3) = (-1)^(j1 - j2 - m3) <j1 m1; j2 m2|j3, -m3> / sqrt(2 j3 + 1)
+long double w3j_low(int l1, int l2, int L, int m1, int m2, int m3) {
+  if (m1 + m2 + m3 != 0 || std::abs(m1) > l1 || std::abs(m2) > l2 || std::abs(m3) > L || std::abs(l1 - l2) > L) return 0.0L;
+  if (L == 0) return (((l1 - m1) & 1) ? -1.0L : 1.0L) / sqrtl(2.0L * l1 + 1);
+  const long double sign = ((l1 + l2 + 1 + l1 - 1 - m2) & 1) ? -1.0L : 1.0L;
+  return sign * cg_one(l1, m1, m3, l2) / sqrtl(2.0L * l2 + 1);
+}
+
+// C of sum C sigma_{l1 m1} conj(x_{l2, m1 + mu}), l2 = l1 + dl, for the mode (L, M = -mu) of sigma times a spin s2 field built from
+// bar(x)_{l2 m2} = (-1)^m2 conj(x_{l2, -m2}), m2 = M - m1:  s2 = -2: sigma x-bar;  s2 = -1: sigma eth x-bar, with the GHP ladder factor
+// sqrt((l2 + 2)(l2 - 1) / 2) of eth on the spin -2 field folded in.  Zero where the neighbour does not exist or either l is below 2.
+long double charge_coefficient(int L, int s2, int l1, int m1, int dl, int mu) {
+  const int l2 = l1 + dl, M = -mu, m2 = M - m1, S = 2 + s2;
+  if (l1 < 2 || l2 < 2 || std::abs(m1) > l1 || std::abs(m2) > l2 || std::abs(M) > L || std::abs(dl) > L) return 0.0L;
+  const long double pi = 3.14159265358979323846264338327950288L;
+  long double c = sqrtl((2.0L * l1 + 1) * (2.0L * l2 + 1) * (2.0L * L + 1) / (4 * pi)) * w3j_low(l1, l2, L, m1, m2, -M) * w3j_low(l1, l2, L, -2, -s2, S);
+  if ((M + S + m2) & 1) c = -c;
+  if (s2 == -1) c *= sqrtl((long double)(l2 + 2) * (l2 - 1) / 2);
+  return c;
 }
 
 }  // namespace
@@ -262,5 +286,123 @@ extern "C" int bms_pair_brackets(bms_ctx* c, const void* a, int64_t ld_a, int el
   if ((rc = io.out("pair_l", l_out, (size_t)6 * n_times, &d_l))) return rc;
   if ((rc = io.out("pair_ll", ll_out, (size_t)18 * n_times, &d_ll))) return rc;
   TIMED(c, BMS_TAG_POINTWISE, launch_pair_brackets(c->stream, d_a + 2 * off_a, ld_a, d_b + 2 * off_b, ld_b, n_times, ell_min, ell_max, d_i, d_l, d_ll));
+  return io.finish();
+} BMS_CATCH(c)
+
+// ---- Bondi charges (scri/asymptotic_bondi_data/bms_charges.py:14-200) of rows stored from l = 0 -------------------------------------
+// The coefficient image of l = 0 .. ell_max (layout: kernels_flux.hip, charge_kernel), every entry computed in long double and rounded once
+BMS_INTERNAL void build_charge_image(int ell_max, std::vector<double>& image) {
+  const int n = LM_total_size(0, ell_max);
+  image.assign((size_t)charge_image_doubles(n), 0.0);
+  for (int l = 0; l <= ell_max; ++l)
+    for (int m = -l; m <= l; ++m) {
+      const int c = LM_index(l, m, 0);
+      for (int dl = -1; dl <= 1; ++dl)
+        for (int mu = -1; mu <= 1; ++mu) {
+          const int k = 3 * (dl + 1) + (mu + 1);
+          if (l + dl > ell_max) continue;
+          image[(size_t)(2 * k + 0) * n + c] = (double)charge_coefficient(1, -2, l, m, dl, mu);
+          image[(size_t)(2 * k + 1) * n + c] = (double)charge_coefficient(1, -1, l, m, dl, mu);
+        }
+      image[(size_t)18 * n + c] = (double)charge_coefficient(0, -2, l, m, 0, 0);
+      image[(size_t)19 * n + c] = (double)l;
+    }
+}
+
+// what bms_bondi_charges refuses before it selects a device; *n_modes on success
+BMS_INTERNAL int charge_checks(bms_ctx* c, const double* t, const void* psi1, int64_t ld_psi1, const void* psi2, int64_t ld_psi2, const void* sigma,
+                               int64_t ld_sigma, const void* sigma_dot, int64_t ld_sigma_dot, int64_t n_times, int ell_max, int mem,
+                               const double* four_momentum, const double* angular, const double* boost, const double* com, int* n_modes) {
+  if (!four_momentum && !angular && !boost && !com) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: every output is NULL");
+  if (!sigma) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: NULL sigma");
+  if ((four_momentum || boost) && !sigma_dot)
+    return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: the four-momentum and the boost charge need sigma_dot, which is NULL");
+  if ((four_momentum || boost) && !psi2) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: the four-momentum and the boost charge need psi2, which is NULL");
+  if ((angular || boost || com) && !psi1)
+    return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: the angular momentum, the boost charge and the centre-of-mass charge need psi1, which is NULL");
+  if (boost && !t) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: the boost charge needs the times, which are NULL");
+  if (n_times < 0) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: negative n_times");
+  if (ell_max < 0) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: negative ell_max");
+  if (ell_max < 2) return fail(c, BMS_ERR_UNSUPPORTED, "bms_bondi_charges: ell_max = %d: the shear starts at ell = 2", ell_max);
+  if (ell_max > MAX_ELL) return fail(c, BMS_ERR_UNSUPPORTED, "bms_bondi_charges: ell_max = %d is beyond %d", ell_max, MAX_ELL);
+  *n_modes = LM_total_size(0, ell_max);
+  if (ld_sigma < *n_modes || (sigma_dot && ld_sigma_dot < *n_modes))
+    return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: row stride smaller than the number of modes (%d)", *n_modes);
+  if ((psi1 && ld_psi1 < 4) || (psi2 && ld_psi2 < 4)) return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: row stride of psi1 or psi2 smaller than its four columns read");
+  if (mem == BMS_DEVICE && ((((uintptr_t)psi1 | (uintptr_t)psi2 | (uintptr_t)sigma | (uintptr_t)sigma_dot) & 15) ||
+                            (((uintptr_t)four_momentum | (uintptr_t)angular | (uintptr_t)boost | (uintptr_t)com) & 7)))
+    return fail(c, BMS_ERR_INVALID, "bms_bondi_charges: device arrays must be aligned to their elements");
+  return BMS_OK;
+}
+
+// the image of ell_max on the device, built once per context and ell_max (as the fluxes' is)
+static int ensure_charge_image(bms_ctx* c, int ell_max, const double** d_image) {
+  char name[64];
+  snprintf(name, sizeof name, "charge_image_%d", ell_max);
+  const int n = LM_total_size(0, ell_max);
+  double* d = nullptr;
+  if (int rc = dev_buf_t(c, name, (size_t)charge_image_doubles(n), &d)) return rc;
+  *d_image = d;
+  if (c->charge_images.count(ell_max)) return BMS_OK;
+  std::vector<double> image;
+  build_charge_image(ell_max, image);
+  HIP_TRY(c, hipMemcpyAsync(d, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vector goes out of scope
+  c->charge_images[ell_max] = true;
+  return BMS_OK;
+}
+
+// (sizes, not statuses) as bms_flux_launch_shape, for the charge kernel and n_modes = (ell_max + 1)^2 columns
+extern "C" int64_t bms_charge_launch_shape(int n_modes, int64_t shape[3]) {
+  FluxShape S;
+  if (!shape || !charge_launch_shape(n_modes, &S)) return 0;
+  shape[0] = S.waves, shape[1] = S.groups, shape[2] = S.tables_in_lds ? 1 : 0;
+  return S.waves;
+}
+
+// pure host routine: the coefficient image the charge kernel reads, [20][(ell_max + 1)^2] doubles (kernels_flux.hip states the layout)
+extern "C" int bms_charge_coefficients(int ell_max, double* image_out) try {
+  if (!image_out || ell_max < 2 || ell_max > MAX_ELL) return BMS_ERR_INVALID;
+  std::vector<double> image;
+  build_charge_image(ell_max, image);
+  std::memcpy(image_out, image.data(), sizeof(double) * image.size());
+  return BMS_OK;
+} BMS_CATCH(nullptr)
+
+extern "C" int bms_bondi_charges(bms_ctx* c, const double* t, const void* psi1, int64_t ld_psi1, const void* psi2, int64_t ld_psi2, const void* sigma,
+                                 int64_t ld_sigma, const void* sigma_dot, int64_t ld_sigma_dot, int64_t n_times, int ell_max, int mem,
+                                 double* four_momentum, double* angular, double* boost, double* com) try {
+  if (!c) return BMS_ERR_INVALID;
+  if (int rc0 = entry_mem(c, mem, "bms_bondi_charges", false)) return rc0;  // (the argument checks come before the device is selected)
+  int rc, n_modes = 0;
+  if ((rc = charge_checks(c, t, psi1, ld_psi1, psi2, ld_psi2, sigma, ld_sigma, sigma_dot, ld_sigma_dot, n_times, ell_max, mem, four_momentum, angular, boost,
+                          com, &n_modes)))
+    return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  FluxShape S;
+  if (!charge_launch_shape(n_modes, &S))
+    return fail(c, BMS_ERR_UNSUPPORTED, "bms_bondi_charges: %d modes (ell_max = %d): one time step's rows of sigma and sigma_dot do not fit in LDS", n_modes, ell_max);
+  const double* d_image;
+  if ((rc = ensure_charge_image(c, ell_max, &d_image))) return rc;
+  const bool with_dot = four_momentum || boost, with_psi1 = angular || boost || com;
+  CallIO io(c, mem);
+  const double *d_t = nullptr, *d_p1 = nullptr, *d_p2 = nullptr, *d_s, *d_sd = nullptr;
+  if ((rc = io.in("in_data", sigma, ((size_t)(n_times - 1) * ld_sigma + n_modes) * 16, &d_s))) return rc;
+  if (with_dot && (rc = io.in("in_aux0", sigma_dot, ((size_t)(n_times - 1) * ld_sigma_dot + n_modes) * 16, &d_sd))) return rc;
+  if (with_psi1 && (rc = io.in("in_aux1", psi1, ((size_t)(n_times - 1) * ld_psi1 + 4) * 16, &d_p1))) return rc;
+  if (with_dot && (rc = io.in("in_aux2", psi2, ((size_t)(n_times - 1) * ld_psi2 + 4) * 16, &d_p2))) return rc;
+  if (boost) {  // (the times are a host array whatever `mem` is, as everywhere in this interface)
+    void* vp;
+    if ((rc = upload(c, "times", t, 8 * (size_t)n_times, &vp))) return rc;
+    d_t = (const double*)vp;
+  }
+  double *d_p, *d_j, *d_n, *d_g;
+  if ((rc = io.out("charge_p", four_momentum, (size_t)4 * n_times, &d_p))) return rc;
+  if ((rc = io.out("charge_j", angular, (size_t)3 * n_times, &d_j))) return rc;
+  if ((rc = io.out("charge_n", boost, (size_t)3 * n_times, &d_n))) return rc;
+  if ((rc = io.out("charge_g", com, (size_t)3 * n_times, &d_g))) return rc;
+  TIMED(c, BMS_TAG_POINTWISE, launch_bondi_charges(c->stream, d_t, d_p1, ld_psi1, d_p2, ld_psi2, d_s, ld_sigma, d_sd, ld_sigma_dot, n_times, ell_max, d_image,
+                                                   d_p, d_j, d_n, d_g));
   return io.finish();
 } BMS_CATCH(c)

@@ -479,6 +479,14 @@ hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const dou
 bool pair_launch_shape(int n_modes, FluxShape* S);  // false: a row does not fit in LDS (tables_in_lds is always false)
 hipError_t launch_pair_brackets(hipStream_t stream, const double* f, long long ld_f, const double* g, long long ld_g, long long n_times,
                                 int ell_min, int ell_max, double* inner, double* l_out, double* ll_out);
+// Bondi charges (scri/asymptotic_bondi_data/bms_charges.py:14-200): four_momentum f8[n][4], angular / boost / com f8[n][3] (any may be
+// null, not all) of sigma, sigma_dot c16[n][ld] holding l = 0 .. ell_max and the first four columns of psi1, psi2 c16[n][ld].  sigma_dot
+// and psi2 may be null without four_momentum and boost, psi1 with four_momentum alone, t without boost.
+int charge_image_doubles(int n_modes);                 // doubles of the coefficient image (engine_flux.hip builds it)
+bool charge_launch_shape(int n_modes, FluxShape* S);  // false: not even one wave's row pair fits in LDS
+hipError_t launch_bondi_charges(hipStream_t stream, const double* t, const double* psi1, long long ld_psi1, const double* psi2, long long ld_psi2,
+                                const double* sigma, long long ld_sigma, const double* sigma_dot, long long ld_sigma_dot, long long n_times,
+                                int ell_max, const double* image, double* four_momentum, double* angular, double* boost, double* com);
 // out c16[n] = sum_e op(a[t][rows_e]) values_e b[t][cols_e] for triplets on the device, indices inside [0, n_cols) (the entry checks them)
 int expectation_max_cols();
 hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,

@@ -14,7 +14,8 @@
 // for any n_modes and ld), lane j sums the columns j, j + 64, ... in that order, and the sixteen partial sums are added across the wave by
 // a butterfly.  Nothing in that order depends on the launch geometry, so a step's result does not depend on the steps around it, on the
 // number of waves or workgroups, or on which outputs were asked for.  No contraction: every multiply-add is spelled out.
-// The brackets of two waveforms (pair_kernel below: <f|g>, <f|L_a|g>, <f|L_a L_b|g>) share that frame, the wave sum and the LDS-room rule.
+// The brackets of two waveforms (pair_kernel below: <f|g>, <f|L_a|g>, <f|L_a L_b|g>) and the Bondi charges (charge_kernel) share that
+// frame, the wave sum and the LDS-room rule.
 #include "wigner.h"
 #include "kernels.h"
 
@@ -24,6 +25,7 @@ namespace {
 
 constexpr int FLUX_IMAGE_PER_MODE = 30;  // doubles of the image per column
 constexpr int FLUX_MAX_WAVES = 8;
+constexpr int CHARGE_IMAGE_PER_MODE = 20;  // doubles of the charges' image per column
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -277,6 +279,137 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES) void pair_kernel(const double*
   }
 }
 
+// Bondi charges (scri/asymptotic_bondi_data/bms_charges.py:14-200) of AsymptoticBondiData rows (l from 0) per time step.  The l <= 1 modes
+// of a product sigma b, b built from sigma-bar or its time derivative, are  sum C sigma[i] conj(x[r])  over the columns i = (l, m) of sigma
+// and the neighbours r = (l + dl, m + mu) of x = sigma or sigma_dot, mode M = -mu, with real C (engine_flux.hip builds them in long double):
+//     A0  spins (2, -2) -> L = 0, diagonal             with x = sigma_dot: the energy
+//     A1  spins (2, -2) -> L = 1                       with x = sigma_dot: the momentum;  with x = sigma: (1/2) eth(sigma sigma-bar)
+//     B   spins (2, -1) -> L = 1, eth's factor folded  with x = sigma: sigma eth sigma-bar
+// The image of l = 0 .. ell_max: 18 n + n + n doubles,
+//     image[(2 k + set) n + c]   k = 3 (dl + 1) + (mu + 1), set = 0 (A1), 1 (B), column c;    image[18 n + c]  A0;    image[19 n + c]  l
+// From the sums E0 (A0), E (A1, sigma_dot), S (A1, sigma), Bc (B) and the l <= 1 entries of psi1 and psi2 (read by one lane, added after
+// the wave sum), with vec(a) = (Re(a_-1 - a_1) / sqrt 6, Im(a_-1 + a_1) / sqrt 6, Re a_0 / sqrt 3) / sqrt(4 pi):
+//     P = -(Re(psi2_00 + E0) / sqrt(4 pi), vec(psi2 + E)),  J = vec(i (psi1 + Bc)),  G = vec(g), g = -(psi1 + Bc + S / 2),  N = vec(g + t (psi2 + E))
+// (the real part of a function changes nothing in vec; eth_GHP of a spin-0 l = 1 mode is a factor of 1).  Geometry and order as the flux
+// kernel's.  WITH_DOT: sigma_dot and psi2 are read (P or N wanted); an accumulator's chain of operations is the same in both instantiations.
+template <bool WITH_DOT, bool TAB_LDS>
+__global__ __launch_bounds__(64 * FLUX_MAX_WAVES) void charge_kernel(const double* __restrict__ t, const double* __restrict__ psi1, long long ld_1,
+                                                                     const double* __restrict__ psi2, long long ld_2, const double* __restrict__ Sg,
+                                                                     long long ld_s, const double* __restrict__ Sd, long long ld_d, long long n_times,
+                                                                     int ell_max, int n, const double* __restrict__ image, double* __restrict__ p_out,
+                                                                     double* __restrict__ j_out, double* __restrict__ n_out, double* __restrict__ g_out) {
+#pragma clang fp contract(off)
+  extern __shared__ double2 charge_lds[];  // [waves][rows][n] rows of modes, then the image
+  constexpr int ROWS = WITH_DOT ? 2 : 1;
+  const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double2* srow = charge_lds + (size_t)wave * ROWS * n;
+  double2* drow = srow + (WITH_DOT ? n : 0);
+  double* ltab = reinterpret_cast<double*>(charge_lds + (size_t)waves * ROWS * n);
+  if (TAB_LDS)
+    for (int i = threadIdx.x; i < CHARGE_IMAGE_PER_MODE * n; i += blockDim.x) ltab[i] = image[i];
+  auto tab = [&](int i) { return TAB_LDS ? ltab[i] : image[i]; };
+  const long long pass_steps = (long long)gridDim.x * waves, passes = (n_times + pass_steps - 1) / pass_steps;
+  __syncthreads();
+  for (long long pass = 0; pass < passes; ++pass) {  // (every wave takes every barrier: the trip count is the workgroup's)
+    const long long step = pass * pass_steps + (long long)blockIdx.x * waves + wave;
+    const bool live = step < n_times;
+    if (live)
+      for (int i = lane; i < n; i += 64) {
+        srow[i] = *reinterpret_cast<const double2*>(Sg + (step * ld_s + i) * 2);
+        if (WITH_DOT) drow[i] = *reinterpret_cast<const double2*>(Sd + (step * ld_d + i) * 2);
+      }
+    __syncthreads();
+    if (live) {
+      // modes M = -1, +1 as (re, im) at 0, 2 and M = 0 at 4 (mu = +1, -1, 0): E, S need no imaginary part of M = 0
+      double e0 = 0, E[5] = {0, 0, 0, 0, 0}, S[5] = {0, 0, 0, 0, 0}, Bc[6] = {0, 0, 0, 0, 0, 0};
+      for (int i = lane; i < n; i += 64) {
+        const int l = (int)tab(19 * n + i), m = i - l * (l + 1);
+        if (l < 2) continue;
+        const double2 sc = srow[i];
+        if (WITH_DOT) {
+          const double2 dc = drow[i];
+          e0 = fma(tab(18 * n + i), fma(sc.x, dc.x, sc.y * dc.y), e0);  // Re(sigma conj(sigma_dot))
+        }
+#pragma unroll
+        for (int dl = -1; dl <= 1; ++dl) {
+          const int lp = l + dl;
+          if (lp < 2 || lp > ell_max) continue;
+          const int shift = dl == 0 ? 0 : (dl > 0 ? 2 * l + 2 : -2 * l);
+#pragma unroll
+          for (int mu = -1; mu <= 1; ++mu) {
+            if (m + mu < -lp || m + mu > lp) continue;
+            const int r = i + shift + mu, k = 3 * (dl + 1) + (mu + 1);
+            const int o = mu == 1 ? 0 : (mu == -1 ? 2 : 4);  // where the mode's (re, im) live
+            const double ca = tab((2 * k + 0) * n + i), cb = tab((2 * k + 1) * n + i);
+            const double2 xs = srow[r];
+            // sc conj(xs)
+            const double qr = fma(sc.x, xs.x, sc.y * xs.y), qi = fma(sc.y, xs.x, -(sc.x * xs.y));
+            Bc[o] = fma(cb, qr, Bc[o]);
+            Bc[o + 1] = fma(cb, qi, Bc[o + 1]);
+            S[o] = fma(ca, qr, S[o]);
+            if (mu != 0) S[o + 1] = fma(ca, qi, S[o + 1]);
+            if (WITH_DOT) {
+              const double2 xd = drow[r];
+              const double dr = fma(sc.x, xd.x, sc.y * xd.y), di = fma(sc.y, xd.x, -(sc.x * xd.y));  // sc conj(xd)
+              E[o] = fma(ca, dr, E[o]);
+              if (mu != 0) E[o + 1] = fma(ca, di, E[o + 1]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 6; ++q) Bc[q] = wave_sum(Bc[q]);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        S[q] = wave_sum(S[q]);
+        if (WITH_DOT) E[q] = wave_sum(E[q]);
+      }
+      if (WITH_DOT) e0 = wave_sum(e0);
+      if (lane == 0) {
+        const double r4 = 3.5449077018110320546, r12 = 6.1399602476789309309, r24 = 8.6832150546992119124;  // sqrt(4 pi), sqrt(12 pi), sqrt(24 pi)
+        double a[5] = {0, 0, 0, 0, 0};  // psi2 + E, the modes (1, -1), (1, 1), (1, 0) as above
+        if (WITH_DOT) {
+          const double* p2 = psi2 + step * ld_2 * 2;
+          a[0] = p2[2] + E[0], a[1] = p2[3] + E[1], a[2] = p2[6] + E[2], a[3] = p2[7] + E[3], a[4] = p2[4] + E[4];
+          if (p_out) {
+            p_out[4 * step] = -(p2[0] + e0) / r4;
+            p_out[4 * step + 1] = -(a[0] - a[2]) / r24;
+            p_out[4 * step + 2] = -(a[1] + a[3]) / r24;
+            p_out[4 * step + 3] = -a[4] / r12;
+          }
+        }
+        if (j_out || n_out || g_out) {
+          const double* p1 = psi1 + step * ld_1 * 2;
+          const double c[6] = {p1[2] + Bc[0], p1[3] + Bc[1], p1[6] + Bc[2], p1[7] + Bc[3], p1[4] + Bc[4], p1[5] + Bc[5]};  // psi1 + sigma eth sigma-bar
+          if (j_out) {  // i c
+            j_out[3 * step] = (c[3] - c[1]) / r24;
+            j_out[3 * step + 1] = (c[0] + c[2]) / r24;
+            j_out[3 * step + 2] = -c[5] / r12;
+          }
+          double g[5];
+#pragma unroll
+          for (int q = 0; q < 5; ++q) g[q] = -fma(0.5, S[q], c[q]);
+          if (g_out) {
+            g_out[3 * step] = (g[0] - g[2]) / r24;
+            g_out[3 * step + 1] = (g[1] + g[3]) / r24;
+            g_out[3 * step + 2] = g[4] / r12;
+          }
+          if (WITH_DOT && n_out) {
+            const double u = t[step];
+            double b[5];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) b[q] = fma(u, a[q], g[q]);
+            n_out[3 * step] = (b[0] - b[2]) / r24;
+            n_out[3 * step + 1] = (b[1] + b[3]) / r24;
+            n_out[3 * step + 2] = b[4] / r12;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 int compute_units() {
   int dev = 0, cus = 0;
   (void)hipGetDevice(&dev);
@@ -288,6 +421,7 @@ int compute_units() {
 }  // namespace
 
 int flux_image_doubles(int n_modes) { return FLUX_IMAGE_PER_MODE * n_modes; }
+int charge_image_doubles(int n_modes) { return CHARGE_IMAGE_PER_MODE * n_modes; }
 
 // THE LDS-room rule of the one-wave-per-step kernels: the most waves (8, 4, 2 or 1) whose rows of `row_bytes` each fit in LDS beside
 // `table_bytes`, and as many workgroups as the device holds at once: by LDS, and by its 32 waves per compute unit.  false: not one fits
@@ -314,6 +448,17 @@ bool flux_launch_shape(int n_modes, FluxShape* S) {
 
 // one row of f per wave; no tables
 bool pair_launch_shape(int n_modes, FluxShape* S) { return n_modes >= 1 && fit_waves((size_t)16 * n_modes, 0, S); }
+
+// rows of sigma and sigma_dot per wave.  The image goes into LDS only where that costs no wave: a workgroup of fewer waves hides less of
+// the latency of its row loads than the table reads through L2 cost (from (ell_max + 1)^2 = 394 columns on with 160 KB)
+bool charge_launch_shape(int n_modes, FluxShape* S) {
+  if (n_modes < 1) return false;
+  const size_t row_pair = (size_t)32 * n_modes, image = (size_t)8 * charge_image_doubles(n_modes);
+  FluxShape rows_only;
+  if (!fit_waves(row_pair, 0, &rows_only)) return false;
+  if (!fit_waves(row_pair, image, S) || S->waves < rows_only.waves) *S = rows_only;
+  return true;
+}
 
 hipError_t launch_poincare_fluxes(hipStream_t stream, const double* t, const double* h, long long ld_h, const double* hdot, long long ld_hdot,
                                   long long n_times, int ell_min, int ell_max, const double* image, double* energy, double* momentum,
@@ -365,6 +510,31 @@ hipError_t launch_pair_brackets(hipStream_t stream, const double* f, long long l
     case 6: return go(pair_kernel<6>);
     default: return go(pair_kernel<7>);
   }
+}
+
+hipError_t launch_bondi_charges(hipStream_t stream, const double* t, const double* psi1, long long ld_psi1, const double* psi2, long long ld_psi2,
+                                const double* sigma, long long ld_sigma, const double* sigma_dot, long long ld_sigma_dot, long long n_times,
+                                int ell_max, const double* image, double* four_momentum, double* angular, double* boost, double* com) {
+  if (n_times <= 0) return hipSuccess;
+  const int n = (ell_max + 1) * (ell_max + 1);
+  const bool with_dot = four_momentum || boost, with_psi1 = angular || boost || com;
+  FluxShape S;
+  if (ell_max < 2 || !sigma || !image || (!with_dot && !with_psi1) || (with_dot && (!sigma_dot || !psi2)) || (with_psi1 && !psi1) || (boost && !t) ||
+      !charge_launch_shape(n, &S))
+    return hipErrorInvalidValue;
+  const long long groups = std::min<long long>(S.groups, (n_times + S.waves - 1) / S.waves);
+  // (the shape is that of two rows per wave; a launch without sigma_dot leaves the second row's LDS unused)
+  auto go = [&](auto kernel) -> hipError_t {
+    if (S.lds_bytes > 64 * 1024) {
+      hipError_t e = allow_dynamic_lds((const void*)kernel);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * S.waves), S.lds_bytes, stream, t, psi1, ld_psi1, psi2, ld_psi2, sigma, ld_sigma, sigma_dot,
+                       ld_sigma_dot, n_times, ell_max, n, image, four_momentum, angular, boost, com);
+    return hipGetLastError();
+  };
+  if (with_dot) return S.tables_in_lds ? go(charge_kernel<true, true>) : go(charge_kernel<true, false>);
+  return S.tables_in_lds ? go(charge_kernel<false, true>) : go(charge_kernel<false, false>);
 }
 
 int expectation_max_cols() {

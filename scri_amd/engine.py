@@ -1163,6 +1163,65 @@ def pair_brackets(a, b, ell_min, ell_max, ell_min_a=None, ell_min_b=None, want=P
     return res[0] if isinstance(want, str) else res
 
 
+CHARGE_NAMES = ("four_momentum", "angular", "boost", "com")
+
+
+def charge_launch_shape(n_modes):
+    """(time steps per pass of one workgroup, workgroups at most, whether the coefficient tables sit in LDS) of the Bondi-charge kernel for
+    n_modes = (ell_max + 1)^2 columns on the current device (bms_charge_launch_shape); None if the rows do not fit in LDS"""
+    shape = (c_i64 * 3)()
+    if not _lib.load().bms_charge_launch_shape(int(n_modes), shape):
+        return None
+    return int(shape[0]), int(shape[1]), bool(shape[2])
+
+
+def charge_coefficients(ell_max):
+    """the coefficient tables of the Bondi-charge kernel, f8[20, (ell_max + 1)^2] (bms_charge_coefficients: a host routine, no device needed)"""
+    if ell_max < 2:
+        raise ValueError(f"bms_charge_coefficients: ell_max = {ell_max} is below 2")
+    out = np.empty((20, (int(ell_max) + 1) ** 2))
+    rc = _lib.load().bms_charge_coefficients(int(ell_max), dptr(out))
+    if rc != 0:
+        raise ValueError(f"bms_charge_coefficients: bad ell_max = {ell_max} (status {rc})")
+    return out
+
+
+def bondi_charges(t, psi1, psi2, sigma, sigma_dot, ell_max, want=CHARGE_NAMES, ctx=None):
+    """bms_bondi_charges: the charges named in `want` -- "four_momentum" [N, 4], "angular", "boost", "com" [N, 3] -- of the fields psi1,
+    psi2, sigma and sigma_dot = d sigma / dt, each [N, (ell_max + 1)^2] from l = 0 as AsymptoticBondiData stores them, in one launch.  The
+    fields are numpy arrays (numpy arrays out) or device tensors (complex128, unit column stride, any row stride: float64 device tensors
+    out), all in one memory.  sigma_dot and psi2 may be None when neither "four_momentum" nor "boost" is wanted, psi1 when "four_momentum"
+    alone is, t when "boost" is not.  Returns the results in the order of `want` (a tuple); one name as a string returns that array alone."""
+    ctx = _ctx(ctx)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or len(set(names)) != len(names) or not set(names) <= set(CHARGE_NAMES):
+        raise ValueError(f"want names {', '.join(repr(k) for k in CHARGE_NAMES)}, got {want!r}")
+    n_modes = (int(ell_max) + 1) ** 2
+    S = _stage(ctx, sigma, np.complex128, "sigma", shape=(None, n_modes))
+    with_dot = "four_momentum" in names or "boost" in names
+    with_psi1 = names != ("four_momentum",)
+    needed = (("sigma_dot", sigma_dot, with_dot), ("psi2", psi2, with_dot), ("psi1", psi1, with_psi1))
+    for name, x, need in needed:
+        if need and x is None:
+            raise ValueError(f"the charges asked for ({', '.join(names)}) need {name}")
+    staged = {name: _stage(ctx, x, np.complex128, name, shape=(S.rows, n_modes)) if need else None for name, x, need in needed}
+    if any(x is not None and x.mem != S.mem for x in staged.values()):
+        raise ValueError("psi1, psi2, sigma and sigma_dot must live in the same memory")
+    t = np.ascontiguousarray(t, dtype=float) if "boost" in names else None
+    if t is not None and t.shape != (S.rows,):
+        raise ValueError(f"{S.rows} time steps of modes on {t.shape} times")
+    out = {k: out_like(S, (S.rows, 4 if k == "four_momentum" else 3), float) for k in names}
+    if S.rows:
+        ptr = lambda k: out[k][0] if k in out else None  # noqa: E731
+        arg = lambda x: (x.ptr, x.ld) if x is not None else (None, 0)  # noqa: E731
+        rc = _lib.load().bms_bondi_charges(ctx.handle, dptr(t) if t is not None else None, *arg(staged["psi1"]), *arg(staged["psi2"]), S.ptr, S.ld,
+                                           *arg(staged["sigma_dot"]), S.rows, int(ell_max), S.mem, ptr("four_momentum"), ptr("angular"),
+                                           ptr("boost"), ptr("com"))
+        ctx.check(rc, "bms_bondi_charges")
+    res = tuple(out[k][1] for k in names)
+    return res[0] if isinstance(want, str) else res
+
+
 PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
 
 

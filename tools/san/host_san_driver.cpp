@@ -751,6 +751,28 @@ void flux_tables_and_triplets() {
   REQUIRE(bms_pair_brackets(&dummy, v, 12, 2, v, 16, 0, 2, 2, 3, 7, out, out, out) == BMS_ERR_INVALID && says("bms_pair_brackets: mem is BMS_HOST or BMS_DEVICE, got 7"));
   REQUIRE(bms_pair_brackets(&dummy, v, 12, 2, v, 16, 0, 0, 2, 3, BMS_HOST, out, out, out) == BMS_OK);
   REQUIRE(bms_pair_brackets(nullptr, v, 12, 2, v, 16, 0, 2, 2, 3, BMS_HOST, out, out, out) == BMS_ERR_INVALID);
+  // the Bondi charges: rows from l = 0 to 2 (9 columns), four columns of psi1 and psi2
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 9, v, 9, 4, 2, BMS_HOST, out, out, out, out, &nm) == BMS_OK && nm == 9);
+  REQUIRE(charge_checks(&dummy, nullptr, v, 4, nullptr, 0, v, 9, nullptr, 0, 4, 2, BMS_HOST, nullptr, out, nullptr, out, &nm) == BMS_OK);
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 9, v, 9, 4, 2, BMS_HOST, nullptr, nullptr, nullptr, nullptr, &nm) == BMS_ERR_INVALID && says("every output"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, nullptr, 9, v, 9, 4, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("NULL sigma"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 9, nullptr, 9, 4, 2, BMS_HOST, out, nullptr, nullptr, nullptr, &nm) == BMS_ERR_INVALID && says("need sigma_dot"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, nullptr, 9, v, 9, v, 9, 4, 2, BMS_HOST, nullptr, nullptr, out, nullptr, &nm) == BMS_ERR_INVALID && says("need psi2"));
+  REQUIRE(charge_checks(&dummy, t, nullptr, 9, v, 9, v, 9, v, 9, 4, 2, BMS_HOST, nullptr, out, nullptr, nullptr, &nm) == BMS_ERR_INVALID && says("need psi1"));
+  REQUIRE(charge_checks(&dummy, nullptr, v, 9, v, 9, v, 9, v, 9, 4, 2, BMS_HOST, nullptr, nullptr, out, nullptr, &nm) == BMS_ERR_INVALID && says("needs the times"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 8, v, 9, 4, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("row stride"));
+  REQUIRE(charge_checks(&dummy, t, v, 3, v, 9, v, 9, v, 9, 4, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("four columns"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 9, v, 9, -1, 2, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID && says("negative n_times"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 9, v, 9, 4, 1, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_UNSUPPORTED && says("ell_max = 1"));
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 9, v, 9, 4, -1, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_INVALID);
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v, 1 << 30, v, 1 << 30, 4, MAX_ELL + 1, BMS_HOST, out, out, out, out, &nm) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(charge_checks(&dummy, t, v, 9, v, 9, v + 1, 9, v, 9, 4, 2, BMS_DEVICE, out, out, out, out, &nm) == BMS_ERR_INVALID && says("aligned"));
+  REQUIRE(bms_bondi_charges(&dummy, t, v, 9, v, 9, v, 9, v, 9, 4, 2, 7, out, out, out, out) == BMS_ERR_INVALID && says("bms_bondi_charges: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_bondi_charges(&dummy, t, v, 9, v, 9, v, 9, v, 9, 0, 2, BMS_HOST, out, out, out, out) == BMS_OK);
+  REQUIRE(bms_bondi_charges(nullptr, t, v, 9, v, 9, v, 9, v, 9, 4, 2, BMS_HOST, out, out, out, out) == BMS_ERR_INVALID);
+  std::vector<double> charge_image((size_t)20 * 16);
+  REQUIRE(bms_charge_coefficients(3, charge_image.data()) == BMS_OK && charge_image[(size_t)19 * 16 + 15] == 3.0 && charge_image[(size_t)18 * 16 + 3] == 0.0);
+  REQUIRE(bms_charge_coefficients(1, charge_image.data()) == BMS_ERR_INVALID && bms_charge_coefficients(3, nullptr) == BMS_ERR_INVALID);
 }
 
 }  // namespace
