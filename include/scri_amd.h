@@ -680,6 +680,43 @@ int64_t bms_charge_launch_shape(int n_modes, int64_t shape[3]);
  * factor of eth on sigma-bar); row 18: A0 (spins (2, -2) -> L = 0, the column itself); row 19: l. */
 int bms_charge_coefficients(int ell_max, double* image_out);
 
+/* ---- Products of two spin-weighted functions on Gauss-Legendre rows: no grid ----------------------------------------------------------
+ * out c16[n_times][ld_out] = the modes l = 0 .. ell_max_out of op(a) op(b), for rows a c16[n_times][ld_a] and b c16[n_times][ld_b] stored
+ * from l = 0 ((ell_max + 1)^2 columns of each are read).  spin_* is the spin of the STORED row; with conj_* != 0 the operand is its bar,
+ * bar(x)_lm = (-1)^(s + m) conj(x_{l, -m}), of spin -spin_*, applied as the row is loaded.  The output has the sum S of the effective spins
+ * and (ell_max_out + 1)^2 columns; those with l < |S| are exact zeros, and input columns with l < |s| are never read.  a and b may be the
+ * same array.  The product is taken as theta sums of both operands on n = floor((ell_max_a + ell_max_b + ell_max_out) / 2) + 1 Gauss-Legendre
+ * nodes in cos(theta), a convolution in m and a quadrature: exact for the truncated product (the integrand has degree <= ell_max_a +
+ * ell_max_b + ell_max_out), with no phi grid.  The nodes and the tables of sYlm(theta_j, 0) are built on the host in long double and kept
+ * per context and (spin, ell_max, n).  Every sum is taken in a fixed order (l, then m1, then j ascending) that depends on nothing but the
+ * sizes and the spins: two calls give the same bits, a slice of the time steps gives the bits of the whole call, row strides and the kind
+ * of memory change no bit.
+ * BMS_ERR_INVALID: a NULL, a row stride below the columns read or written, negative sizes, ell_max_out > ell_max_a + ell_max_b, a bad mem,
+ * misaligned device arrays; BMS_ERR_UNSUPPORTED: an effective |spin| or |S| above 4, an ell_max beyond the library's, a time step whose
+ * rows and panels do not fit in LDS.  All of it is found on the host before anything is launched.  n_times == 0 writes nothing. */
+int bms_mode_product(bms_ctx* ctx, const void* a, int64_t ld_a, int spin_a, int ell_max_a, int conj_a, const void* b, int64_t ld_b, int spin_b,
+                     int ell_max_b, int conj_b, int64_t n_times, int ell_max_out, int mem, void* out, int64_t ld_out);
+/* mass aspect and supermomenta (scri/asymptotic_bondi_data/bms_charges.py:14-47, 203-286) of psi2, sigma and sigma_dot = d sigma / dt, rows
+ * from l = 0 ((ell_max + 1)^2 columns of sigma and sigma_dot and (ell_max_out + 1)^2 of psi2 are read), 2 <= ell_max, ell_max_out <= ell_max:
+ * the product body of bms_mode_product on sigma and bar(sigma_dot), and as the row is stored, mode by mode,
+ *   bondi_sachs = psi2 + sigma sigma-bar-dot,   moreschi = bondi_sachs + eth^2 sigma-bar,   geroch = bondi_sachs + (eth^2 sigma-bar -
+ *   ethbar^2 sigma) / 2,   geroch_winicour = bondi_sachs - ethbar^2 sigma,   mass_aspect = -(bondi_sachs + bar bondi_sachs) / 2
+ * (GHP: eth^2 sigma-bar = bar(sigma) sqrt((l + 2)(l + 1) l (l - 1)) / 2, ethbar^2 sigma = sigma times the same factor).  Each output is
+ * c16[n_times][ld_out] with (ell_max_out + 1)^2 columns written; any may be NULL, not all; an output does not depend on which others are
+ * asked for.  integrated != 0: the four supermomenta are written as -bar(Psi) / (2 sqrt(pi)); the mass aspect is never altered.
+ * Refusals and bit guarantees as bms_mode_product; ell_max < 2 is BMS_ERR_UNSUPPORTED, ell_max_out > ell_max BMS_ERR_INVALID. */
+int bms_supermomenta(bms_ctx* ctx, const void* psi2, int64_t ld_psi2, const void* sigma, int64_t ld_sigma, const void* sigma_dot,
+                     int64_t ld_sigma_dot, int64_t n_times, int ell_max, int ell_max_out, int mem, int integrated, void* bondi_sachs,
+                     void* moreschi, void* geroch, void* geroch_winicour, void* mass_aspect, int64_t ld_out);
+/* how the product kernel runs on the current device: shape[0] time steps per pass of one workgroup (returned as well, 0 if the rows and
+ * panels of one time step do not fit in LDS), shape[1] workgroups at most, shape[2] != 0 if the tables are held in LDS (they are read
+ * through L2); sizes, not a status */
+int64_t bms_product_launch_shape(int ell_max_a, int ell_max_b, int ell_max_out, int64_t shape[3]);
+/* pure host routine: the n_nodes Gauss-Legendre nodes cos_theta f8[n_nodes] (theta ascending) and weights f8[n_nodes], and the table
+ * f8[n_nodes][(ell_max + 1)^2] of sYlm(theta_j, 0) for spin s = `spin` (|spin| <= 4; zero for l < |s|) as the kernel reads it -- the
+ * output spin's table is this one times 2 pi w_j, formed in long double before the one rounding */
+int bms_product_tables(int spin, int ell_max, int n_nodes, double* cos_theta, double* weights, double* table);
+
 #ifdef __cplusplus
 }
 #endif

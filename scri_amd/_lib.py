@@ -214,6 +214,10 @@ SIGNATURES = {
     "bms_bondi_charges": (c_int, [c_vp, c_dp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "bms_charge_launch_shape": (c_i64, [c_int, ctypes.POINTER(c_i64)]),
     "bms_charge_coefficients": (c_int, [c_int, c_dp]),
+    "bms_mode_product": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int, c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64]),
+    "bms_supermomenta": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "bms_product_launch_shape": (c_i64, [c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
+    "bms_product_tables": (c_int, [c_int, c_int, c_int, c_dp, c_dp, c_dp]),
 }
 
 _lib = None

@@ -4,8 +4,13 @@ bms_grid_multiply on a grid that is exact for l_a + l_b), time derivatives throu
 here is the bookkeeping of the formulas.  The functions are grafted onto AsymptoticBondiData as methods.
 
 The Bondi charges P, J, N, G need the l <= 1 modes of their aspects only.  Of a device-resident object with ell_max >= 2 they come from
-ONE launch over the modes (bondi_charges -> bms_bondi_charges) after one spline derivative of sigma in HBM: no grid is built.  Host-resident
-objects, the full-band mass_aspect, the supermomenta and CWWY_angular_momentum keep the route through the products.
+ONE launch over the modes (bondi_charges -> bms_bondi_charges) after one spline derivative of sigma in HBM: no grid is built.
+
+The full-band quantities -- mass_aspect, the four supermomenta (together: supermomenta()) and, through them, CWWY_angular_momentum -- of a
+device-resident object with ell_max >= 2 are one derivative of sigma in HBM and ONE launch as well (bms_supermomenta: the product sigma
+sigma-bar-dot on Gauss-Legendre rows, psi2 and the diagonal eth terms added as the row is stored), wherever the product asked for is the
+exact one truncated at the object's ell_max (or, for the mass aspect, at an integer below it).  Host-resident objects, an aliasing
+working_ell_max, an output band other than that and sizes the entry does not carry keep the route through the grid products.
 """
 from math import sqrt
 
@@ -19,6 +24,11 @@ def mass_aspect(self, truncate_ell=max):
     used as the truncator of the product (default `max`: the larger ell_max of the two factors); a false value leaves the
     choice to the series' own multiplication_truncator (the reference's plain `sigma * sigma.bar.dot`: `max` for every
     AsymptoticBondiData built by file_io, from_initial_values and map_to_superrest_frame, `sum` for a bare one)."""
+    ell_out = _exact_band(self, truncate_ell)
+    if ell_out is not None:
+        got = _fields_on_device(self, ("mass_aspect",), ell_out)
+        if got is not None:
+            return got[0]
     # one formula, three ways of choosing the band limit of its two terms
     if callable(truncate_ell):
         product_ell, psi2 = truncate_ell, self.psi2
@@ -59,6 +69,31 @@ def _minkowski_norm_squared(P):
 def _one_pass(self):
     """whether the charges of this object come from the one-pass kernel: fields in HBM and a shear to read"""
     return getattr(self, "is_device_resident", False) and self.ell_max >= 2
+
+
+def _exact_band(self, truncate_ell):
+    """the band limit at which mass_aspect(truncate_ell) of this object is what bms_supermomenta gives -- both of its terms end there and it
+    is no wider than the fields -- or None: the route through the grid product"""
+    if not _one_pass(self):
+        return None
+    if callable(truncate_ell) or not truncate_ell:  # psi2 keeps its band: the product has to end where psi2 does
+        ell = int((truncate_ell if callable(truncate_ell) else self._truncator)((self.ell_max, self.ell_max)))
+        return ell if ell == self.ell_max else None
+    return int(truncate_ell) if 0 <= truncate_ell <= self.ell_max else None
+
+
+def _fields_on_device(self, want, ell_out, integrated=False):
+    """the fields named in `want` (engine.SUPERMOMENTA_NAMES) of a device-resident object, truncated at ell_out, as resident spin-0 series:
+    one derivative of sigma in HBM and one launch.  None if the kernel does not carry the size (a time step beyond its LDS)"""
+    from . import engine
+    from .device_series import DeviceModesTimeSeries
+
+    if engine.product_launch_shape(self.ell_max, self.ell_max, ell_out) is None:
+        return None
+    raw = self._raw_dev  # psi0 .. psi4, sigma
+    sigma_dot = engine.spline_derivative(self.t, raw[5], self.t, 1, ctx=self._ctx)
+    out = engine.supermomenta(raw[2], raw[5], sigma_dot, self.ell_max, ell_out, want=tuple(want), integrated=integrated, ctx=self._ctx)
+    return tuple(DeviceModesTimeSeries(o, self.t, 0, 0, ell_out, ctx=self._ctx, multiplication_truncator=self._truncator) for o in out)
 
 
 _CHARGES = ("four_momentum", "angular", "boost", "com")
@@ -192,6 +227,12 @@ def supermomentum(self, supermomentum_def, **kwargs):
             "  * 'Geroch' or 'G'\n"
             "  * 'Geroch-Winicour' or 'GW'"
         )
+    # the exact product truncated at the fields' own band: one launch for a device-resident object
+    if (_one_pass(self) and set(kwargs) <= {"working_ell_max", "output_ell_max"} and kwargs.get("working_ell_max", 2 * self.ell_max) >= 2 * self.ell_max
+            and kwargs.get("output_ell_max", self.ell_max) == self.ell_max):
+        got = _fields_on_device(self, (_SUPERMOMENTA[name],), self.ell_max, integrated=return_integrated)
+        if got is not None:
+            return got[0]
     base = self.psi2 + self.sigma.grid_multiply(self.sigma.bar.dot, **kwargs)
     if name in ("bondi-sachs", "bs"):
         result = base
@@ -206,7 +247,21 @@ def supermomentum(self, supermomentum_def, **kwargs):
     return result
 
 
+_SUPERMOMENTA = {"bondi-sachs": "bondi_sachs", "bs": "bondi_sachs", "moreschi": "moreschi", "m": "moreschi", "geroch": "geroch", "g": "geroch",
+                 "geroch-winicour": "geroch_winicour", "gw": "geroch_winicour"}
+
+
+def supermomenta(self, integrated=False):
+    """(Bondi-Sachs, Moreschi, Geroch, Geroch-Winicour): the four supermomentum definitions together; of a device-resident object one
+    derivative of sigma in HBM and one launch"""
+    if _one_pass(self):
+        got = _fields_on_device(self, ("bondi_sachs", "moreschi", "geroch", "geroch_winicour"), self.ell_max, integrated=integrated)
+        if got is not None:
+            return got
+    return tuple(self.supermomentum(name, integrated=integrated) for name in ("Bondi-Sachs", "Moreschi", "Geroch", "Geroch-Winicour"))
+
+
 METHODS = (
     mass_aspect, bondi_charges, bondi_rest_mass, bondi_four_momentum, bondi_angular_momentum, bondi_boost_charge, bondi_CoM_charge,
-    bondi_dimensionless_spin, CWWY_angular_momentum, supermomentum,
+    bondi_dimensionless_spin, CWWY_angular_momentum, supermomentum, supermomenta,
 )

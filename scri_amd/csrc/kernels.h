@@ -487,6 +487,25 @@ bool charge_launch_shape(int n_modes, FluxShape* S);  // false: not even one wav
 hipError_t launch_bondi_charges(hipStream_t stream, const double* t, const double* psi1, long long ld_psi1, const double* psi2, long long ld_psi2,
                                 const double* sigma, long long ld_sigma, const double* sigma_dot, long long ld_sigma_dot, long long n_times,
                                 int ell_max, const double* image, double* four_momentum, double* angular, double* boost, double* com);
+// Products on Gauss-Legendre rows (kernels_product.hip): out c16[n][ld_out] = the modes l = 0 .. l_out of op(a) op(b), rows c16[n][ld] from
+// l = 0; op = bar where conj != 0.  tab_a, tab_b: lambda tables f8[n_nodes][(l + 1)^2] of the EFFECTIVE spins, tab_out the output spin's
+// with 2 pi w_j folded (engine_product.hip builds them); n_nodes = product_nodes(l_a, l_b, l_out).
+struct ProductShape {
+  int steps, groups;  // time steps per pass of one workgroup, workgroups at most
+  bool tables_in_lds;
+  size_t lds_bytes;
+};
+int product_nodes(int l_a, int l_b, int l_out);
+bool product_launch_shape(int l_a, int l_b, int l_out, ProductShape* S);  // false: the rows and panels of one time step do not fit in LDS
+hipError_t launch_mode_product(hipStream_t stream, const double* a, long long ld_a, int spin_a, int l_a, int conj_a, const double* b, long long ld_b,
+                               int spin_b, int l_b, int conj_b, long long n_times, int l_out, const double* tab_a, const double* tab_b,
+                               const double* tab_out, double* out, long long ld_out);
+// the same body on sigma and bar(sigma_dot) (tab_plus: spin 2, tab_minus: spin -2, both of ell_max; tab_out: spin 0 of l_out, weighted) with
+// psi2 and the diagonal terms added as the row is stored; any output may be null, not all
+hipError_t launch_supermomenta(hipStream_t stream, const double* psi2, long long ld_psi2, const double* sigma, long long ld_sigma,
+                               const double* sigma_dot, long long ld_sigma_dot, long long n_times, int ell_max, int l_out, int integrated,
+                               const double* tab_plus, const double* tab_minus, const double* tab_out, double* bondi_sachs, double* moreschi,
+                               double* geroch, double* geroch_winicour, double* mass_aspect, long long ld_out);
 // out c16[n] = sum_e op(a[t][rows_e]) values_e b[t][cols_e] for triplets on the device, indices inside [0, n_cols) (the entry checks them)
 int expectation_max_cols();
 hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,

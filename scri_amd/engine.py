@@ -1222,6 +1222,86 @@ def bondi_charges(t, psi1, psi2, sigma, sigma_dot, ell_max, want=CHARGE_NAMES, c
     return res[0] if isinstance(want, str) else res
 
 
+SUPERMOMENTA_NAMES = ("bondi_sachs", "moreschi", "geroch", "geroch_winicour", "mass_aspect")
+
+
+def product_nodes(ell_max_a, ell_max_b, ell_max_out):
+    """the Gauss-Legendre rows on which the product truncated at ell_max_out is exact: floor((l_a + l_b + l_out) / 2) + 1"""
+    return (int(ell_max_a) + int(ell_max_b) + int(ell_max_out)) // 2 + 1
+
+
+def product_launch_shape(ell_max_a, ell_max_b, ell_max_out):
+    """(time steps per pass of one workgroup, workgroups at most, whether the tables sit in LDS) of the product kernel on the current
+    device (bms_product_launch_shape); None if the rows and panels of one time step do not fit in LDS"""
+    shape = (c_i64 * 3)()
+    if not _lib.load().bms_product_launch_shape(int(ell_max_a), int(ell_max_b), int(ell_max_out), shape):
+        return None
+    return int(shape[0]), int(shape[1]), bool(shape[2])
+
+
+def product_tables(spin, ell_max, n_nodes):
+    """(cos_theta f8[n], weights f8[n], table f8[n, (ell_max + 1)^2]): the Gauss-Legendre rule of n_nodes points and sYlm(theta_j, 0) of
+    `spin` as the product kernel reads it (bms_product_tables: a host routine, no device needed)"""
+    x, w, table = np.empty(int(n_nodes)), np.empty(int(n_nodes)), np.empty((int(n_nodes), (int(ell_max) + 1) ** 2))
+    rc = _lib.load().bms_product_tables(int(spin), int(ell_max), int(n_nodes), dptr(x), dptr(w), dptr(table))
+    if rc != 0:
+        raise ValueError(f"bms_product_tables: bad spin = {spin}, ell_max = {ell_max} or n_nodes = {n_nodes} (status {rc})")
+    return x, w, table
+
+
+def mode_product(a, spin_a, ell_max_a, b, spin_b, ell_max_b, ell_max_out, conj_a=False, conj_b=False, ctx=None):
+    """bms_mode_product: the modes l = 0 .. ell_max_out of op(a) op(b) for a [N, (ell_max_a + 1)^2] and b [N, (ell_max_b + 1)^2] from l = 0,
+    spin_* the spin of the stored rows, op = bar where conj_* is set (an operand of spin -spin_*): exact for ell_max_out <= ell_max_a +
+    ell_max_b, on Gauss-Legendre rows, with no grid.  numpy arrays (a numpy array out) or device tensors (complex128, unit column stride,
+    any row stride: a device tensor out), both in one memory; a and b may be the same array."""
+    ctx = _ctx(ctx)
+    A = _stage(ctx, a, np.complex128, "a", shape=(None, (int(ell_max_a) + 1) ** 2))
+    B = _stage(ctx, b, np.complex128, "b", shape=(A.rows, (int(ell_max_b) + 1) ** 2))
+    if A.mem != B.mem:
+        raise ValueError("a and b must live in the same memory")
+    if ell_max_out < 0:
+        raise ValueError(f"ell_max_out = {ell_max_out} is negative")
+    n_out = (int(ell_max_out) + 1) ** 2
+    ptr, out = out_like(A, (A.rows, n_out), np.complex128)
+    if A.rows:
+        rc = _lib.load().bms_mode_product(ctx.handle, A.ptr, A.ld, int(spin_a), int(ell_max_a), int(bool(conj_a)), B.ptr, B.ld, int(spin_b), int(ell_max_b),
+                                          int(bool(conj_b)), A.rows, int(ell_max_out), A.mem, ptr, n_out)
+        ctx.check(rc, "bms_mode_product")
+    return out
+
+
+def supermomenta(psi2, sigma, sigma_dot, ell_max, ell_max_out=None, want=SUPERMOMENTA_NAMES, integrated=False, ctx=None):
+    """bms_supermomenta: the fields named in `want` -- "bondi_sachs", "moreschi", "geroch", "geroch_winicour" (written as -bar / (2 sqrt(pi))
+    with integrated=True) and "mass_aspect" (never altered) -- each [N, (ell_max_out + 1)^2] from l = 0, of psi2, sigma and sigma_dot =
+    d sigma / dt, each [N, (ell_max + 1)^2] from l = 0 as AsymptoticBondiData stores them, in one launch; ell_max_out <= ell_max (default:
+    ell_max).  The fields are numpy arrays (numpy arrays out) or device tensors (complex128, unit column stride, any row stride: device
+    tensors out), all in one memory.  Returns the results in the order of `want` (a tuple); one name as a string returns that array alone."""
+    ctx = _ctx(ctx)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or len(set(names)) != len(names) or not set(names) <= set(SUPERMOMENTA_NAMES):
+        raise ValueError(f"want names {', '.join(repr(k) for k in SUPERMOMENTA_NAMES)}, got {want!r}")
+    ell_max = int(ell_max)
+    ell_max_out = ell_max if ell_max_out is None else int(ell_max_out)
+    if not 0 <= ell_max_out <= ell_max:
+        raise ValueError(f"ell_max_out = {ell_max_out} is outside 0 .. ell_max = {ell_max}")
+    n_modes, n_out = (ell_max + 1) ** 2, (ell_max_out + 1) ** 2
+    S = _stage(ctx, sigma, np.complex128, "sigma", shape=(None, n_modes))
+    D = _stage(ctx, sigma_dot, np.complex128, "sigma_dot", shape=(S.rows, n_modes))
+    P = _stage(ctx, psi2, np.complex128, "psi2", shape=(S.rows, None))
+    if P.cols < n_out:
+        raise ValueError(f"psi2 has {P.cols} columns, fewer than the (ell_max_out + 1)^2 = {n_out} read")
+    if D.mem != S.mem or P.mem != S.mem:
+        raise ValueError("psi2, sigma and sigma_dot must live in the same memory")
+    out = {k: out_like(S, (S.rows, n_out), np.complex128) for k in names}
+    if S.rows:
+        ptr = lambda k: out[k][0] if k in out else None  # noqa: E731
+        rc = _lib.load().bms_supermomenta(ctx.handle, P.ptr, P.ld, S.ptr, S.ld, D.ptr, D.ld, S.rows, ell_max, ell_max_out, S.mem, int(bool(integrated)),
+                                          *(ptr(k) for k in SUPERMOMENTA_NAMES), n_out)
+        ctx.check(rc, "bms_supermomenta")
+    res = tuple(out[k][1] for k in names)
+    return res[0] if isinstance(want, str) else res
+
+
 PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
 
 

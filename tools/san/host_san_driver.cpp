@@ -15,6 +15,7 @@
 #include "../../scri_amd/csrc/engine_sample.hip"
 #include "../../scri_amd/csrc/engine_com.hip"
 #include "../../scri_amd/csrc/engine_flux.hip"
+#include "../../scri_amd/csrc/engine_product.hip"
 
 #include <cstdio>
 #include <random>
@@ -773,6 +774,41 @@ void flux_tables_and_triplets() {
   std::vector<double> charge_image((size_t)20 * 16);
   REQUIRE(bms_charge_coefficients(3, charge_image.data()) == BMS_OK && charge_image[(size_t)19 * 16 + 15] == 3.0 && charge_image[(size_t)18 * 16 + 3] == 0.0);
   REQUIRE(bms_charge_coefficients(1, charge_image.data()) == BMS_ERR_INVALID && bms_charge_coefficients(3, nullptr) == BMS_ERR_INVALID);
+  // the products on Gauss-Legendre rows: the nodes and tables (a pure host routine) and what the two entries refuse
+  for (int n_nodes : {1, 2, 5, 13}) {
+    std::vector<double> x((size_t)n_nodes), w((size_t)n_nodes), table((size_t)n_nodes * 25);
+    REQUIRE(bms_product_tables(-2, 4, n_nodes, x.data(), w.data(), table.data()) == BMS_OK);
+    double sum = 0;
+    for (int j = 0; j < n_nodes; ++j) {
+      sum += w[(size_t)j];
+      REQUIRE(x[(size_t)j] == -x[(size_t)(n_nodes - 1 - j)] && table[(size_t)j * 25 + 3] == 0.0 && std::isfinite(table[(size_t)j * 25 + 24]));
+    }
+    REQUIRE(std::fabs(sum - 2.0) < 1e-15);
+  }
+  REQUIRE(bms_product_tables(5, 4, 3, out, out, out) == BMS_ERR_INVALID && bms_product_tables(0, 4, 0, out, out, out) == BMS_ERR_INVALID &&
+          bms_product_tables(0, 4, 3, nullptr, out, out) == BMS_ERR_INVALID);
+  int nn = 0;
+  REQUIRE(product_checks(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 36, &nn) == BMS_OK && nn == 6);
+  REQUIRE(product_checks(&dummy, nullptr, 9, 2, 2, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 36, &nn) == BMS_ERR_INVALID && says("NULL a, b or out"));
+  REQUIRE(product_checks(&dummy, v, 8, 2, 2, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 36, &nn) == BMS_ERR_INVALID && says("row stride of a or b"));
+  REQUIRE(product_checks(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 35, &nn) == BMS_ERR_INVALID && says("row stride of out"));
+  REQUIRE(product_checks(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, 4, 6, BMS_HOST, out, 49, &nn) == BMS_ERR_INVALID && says("where the product ends"));
+  REQUIRE(product_checks(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, -1, 5, BMS_HOST, out, 36, &nn) == BMS_ERR_INVALID && says("negative n_times"));
+  REQUIRE(product_checks(&dummy, v, 9, 2, -1, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 36, &nn) == BMS_ERR_INVALID && says("negative ell_max"));
+  REQUIRE(product_checks(&dummy, v, 9, 3, 2, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 36, &nn) == BMS_ERR_UNSUPPORTED && says("up to |s| = 4"));
+  REQUIRE(product_checks(&dummy, v, 1 << 30, 2, MAX_ELL + 1, 0, v, 16, -2, 3, 1, 4, 5, BMS_HOST, out, 36, &nn) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(product_checks(&dummy, v + 1, 9, 2, 2, 0, v, 16, -2, 3, 1, 4, 5, BMS_DEVICE, out, 36, &nn) == BMS_ERR_INVALID && says("aligned"));
+  REQUIRE(supermomenta_checks(&dummy, v, 9, v, 16, v, 16, 4, 3, 2, BMS_HOST, out, nullptr, nullptr, nullptr, out, 9, &nn) == BMS_OK && nn == 5);
+  REQUIRE(supermomenta_checks(&dummy, v, 9, v, 16, v, 16, 4, 3, 2, BMS_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, 9, &nn) == BMS_ERR_INVALID && says("every output"));
+  REQUIRE(supermomenta_checks(&dummy, v, 9, nullptr, 16, v, 16, 4, 3, 2, BMS_HOST, out, out, out, out, out, 9, &nn) == BMS_ERR_INVALID && says("NULL psi2, sigma or sigma_dot"));
+  REQUIRE(supermomenta_checks(&dummy, v, 9, v, 15, v, 16, 4, 3, 2, BMS_HOST, out, out, out, out, out, 9, &nn) == BMS_ERR_INVALID && says("row stride of sigma"));
+  REQUIRE(supermomenta_checks(&dummy, v, 8, v, 16, v, 16, 4, 3, 2, BMS_HOST, out, out, out, out, out, 9, &nn) == BMS_ERR_INVALID && says("row stride of psi2"));
+  REQUIRE(supermomenta_checks(&dummy, v, 25, v, 16, v, 16, 4, 3, 4, BMS_HOST, out, out, out, out, out, 25, &nn) == BMS_ERR_INVALID && says("beyond ell_max = 3"));
+  REQUIRE(supermomenta_checks(&dummy, v, 9, v, 16, v, 16, 4, 1, 1, BMS_HOST, out, out, out, out, out, 9, &nn) == BMS_ERR_UNSUPPORTED && says("ell_max = 1"));
+  REQUIRE(bms_mode_product(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, 4, 5, 7, out, 36) == BMS_ERR_INVALID && says("bms_mode_product: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_mode_product(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, 0, 5, BMS_HOST, out, 36) == BMS_OK);
+  REQUIRE(bms_supermomenta(&dummy, v, 9, v, 16, v, 16, 0, 3, 2, BMS_HOST, 1, out, out, out, out, out, 9) == BMS_OK);
+  REQUIRE(bms_supermomenta(nullptr, v, 9, v, 16, v, 16, 4, 3, 2, BMS_HOST, 1, out, out, out, out, out, 9) == BMS_ERR_INVALID);
 }
 
 }  // namespace
