@@ -125,7 +125,8 @@ enum bms_kernel_tag {
   BMS_TAG_THETA_QUADRATURE = 7, /* theta_quadrature_kernel (second step of the unfused separable analysis) */
   BMS_TAG_ANALYSIS_FUSED = 8,   /* analysis_split_kernel / analysis_fused_kernel (phi-DFT on MFMA + theta quadrature, one kernel) */
   BMS_TAG_ANALYSIS_LARGE = 9,   /* phi_dft_folded_kernel + theta_quadrature_mfma_kernel (grids with n_theta > 40) */
-  BMS_TAG_COUNT = 10
+  BMS_TAG_CONSTRAINTS = 10,     /* constraint_kernel (bms_bondi_constraints) */
+  BMS_TAG_COUNT = 11
 };
 int bms_ctx_enable_timing(bms_ctx* ctx, int on);
 int bms_ctx_get_timing(bms_ctx* ctx, double ms[BMS_TAG_COUNT], int64_t calls[BMS_TAG_COUNT], int reset);
@@ -708,6 +709,26 @@ int bms_mode_product(bms_ctx* ctx, const void* a, int64_t ld_a, int spin_a, int 
 int bms_supermomenta(bms_ctx* ctx, const void* psi2, int64_t ld_psi2, const void* sigma, int64_t ld_sigma, const void* sigma_dot,
                      int64_t ld_sigma_dot, int64_t n_times, int ell_max, int ell_max_out, int mem, int integrated, void* bondi_sachs,
                      void* moreschi, void* geroch, void* geroch_winicour, void* mass_aspect, int64_t ld_out);
+/* the violations of the six Bondi-gauge relations (scri/asymptotic_bondi_data/constraints.py) and their L2 norms over the sphere, in one
+ * launch.  fields: psi0 .. psi4, sigma; psi_dot: d/du of psi0, psi1, psi2; sigma_dot, sigma_ddot: d sigma / du, d^2 sigma / du^2; every row
+ * c16 with (ell_max + 1)^2 columns from l = 0 and its own row stride, 2 <= ell_max.  Mode by mode,
+ *   v0 = psi0_dot - eth psi1 - 3 sigma psi2    v1 = psi1_dot - eth psi2 - 2 sigma psi3    v2 = psi2_dot - eth psi3 - sigma psi4
+ *   v3 = psi3 + eth bar(sigma_dot)             v4 = psi4 + bar(sigma_ddot)                v5 = Im[psi2 + eth^2 bar(sigma) + sigma bar(sigma_dot)]
+ * with the GHP eth (a row of spin s times sqrt((l - s)(l + s + 1) / 2), zero for l < |s| or l < |s + 1|), bar as in bms_mode_product and
+ * Im(x) = -i (x - bar x) / 2; the products are those of bms_mode_product truncated at ell_max, sigma's theta sums taken once for all four.
+ * The diagonal terms are read as stored, columns with l < |s| included; product columns with l < |S| are exact zeros.  violations[k]
+ * c16[n_times][ld_out] and norms f8[n_times][6] (in the memory `mem` names; norms[t][k] = sqrt(sum_c |v_k[t][c]|^2), summed in a fixed
+ * order) may each be NULL, not all; `violations` itself may be NULL.  An input that only outputs not asked for read may be NULL (psi0 is never
+ * read); a product that no output asked for needs is not formed.  An output does not depend on which others are asked for; the bit
+ * guarantees of bms_mode_product hold, and the norms of a norms-only call are the norms of a call that stores the violations too.
+ * BMS_ERR_INVALID: a NULL that is needed, every output NULL, a row stride below (ell_max + 1)^2, negative sizes, a bad mem, misaligned
+ * device arrays; BMS_ERR_UNSUPPORTED: ell_max < 2, an ell_max beyond the library's or a time step that does not fit in LDS (bms_product_launch_shape
+ * of (ell_max, ell_max, ell_max)).  Found on the host before anything is launched.  n_times == 0 writes nothing and returns before the
+ * device is asked for its LDS, as in bms_mode_product: an empty series is BMS_OK at any ell_max the library carries.  Timed as
+ * BMS_TAG_CONSTRAINTS. */
+int bms_bondi_constraints(bms_ctx* ctx, const void* const fields[6], const int64_t ld_fields[6], const void* const psi_dot[3],
+                          const int64_t ld_psi_dot[3], const void* sigma_dot, int64_t ld_sigma_dot, const void* sigma_ddot,
+                          int64_t ld_sigma_ddot, int64_t n_times, int ell_max, int mem, void* const violations[6], int64_t ld_out, double* norms);
 /* how the product kernel runs on the current device: shape[0] time steps per pass of one workgroup (returned as well, 0 if the rows and
  * panels of one time step do not fit in LDS), shape[1] workgroups at most, shape[2] != 0 if the tables are held in LDS (they are read
  * through L2); sizes, not a status */

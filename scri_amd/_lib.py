@@ -74,7 +74,7 @@ class bms_com_fit_result(ctypes.Structure):
                 ("t_f", ctypes.c_double), ("i_i", c_i64), ("i_f", c_i64), ("moments", (ctypes.c_double * 3) * 3)]
 
 
-KERNEL_TAGS = ("rotate", "setup", "gemm_synthesis", "spline_forward", "spline_backward", "gemm_analysis", "pointwise", "theta_quadrature", "analysis_fused", "analysis_large")
+KERNEL_TAGS = ("rotate", "setup", "gemm_synthesis", "spline_forward", "spline_backward", "gemm_analysis", "pointwise", "theta_quadrature", "analysis_fused", "analysis_large", "constraints")
 
 # every symbol include/scri_amd.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -216,6 +216,8 @@ SIGNATURES = {
     "bms_charge_coefficients": (c_int, [c_int, c_dp]),
     "bms_mode_product": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int, c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64]),
     "bms_supermomenta": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "bms_bondi_constraints": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_vp, c_i64, c_vp, c_i64,
+                              c_i64, c_int, c_int, ctypes.POINTER(c_vp), c_i64, c_vp]),
     "bms_product_launch_shape": (c_i64, [c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "bms_product_tables": (c_int, [c_int, c_int, c_int, c_dp, c_dp, c_dp]),
 }

@@ -182,14 +182,57 @@ def bondi_constraints(self, lhs=True, rhs=True):
     )
 
 
+def _one_launch(self):
+    """whether the violations of this object come from bms_bondi_constraints: fields in HBM, a shear to read, products that end at the
+    fields' band (the `max` truncator) and a time step that fits the kernel's LDS"""
+    if not getattr(self, "is_device_resident", False) or self.ell_max < 2:
+        return False
+    if int(self._truncator((self.ell_max, self.ell_max))) != self.ell_max:
+        return False
+    return engine.product_launch_shape(self.ell_max, self.ell_max, self.ell_max) is not None
+
+
+_VIOLATION_SPINS = (2, 1, 0, -1, -2, 0)
+# bondi_violations takes the one launch up to here: measured at 1e5 steps, 24 ms against 55 ms through the grid products at ell_max = 16 (three
+# workgroups per compute unit by LDS), but 142 ms against 117 ms at ell_max = 24 (one).  The norms gain at both (DESIGN section 4, "Constraints")
+_VIOLATIONS_ONE_LAUNCH_ELL_MAX = 16
+
+
+def bondi_gauge_check(self, violations=True, norms=True):
+    """(violations, norms): lhs - rhs of the six relations as a list of six series and their L2 norms over the sphere as a list of six
+    arrays [n_times]; either is None if not asked for.  A device-resident object with ell_max >= 2, the `max` truncator and a time step
+    that fits takes five spline derivatives in HBM and ONE launch (bms_bondi_constraints): the series stay resident and only the
+    norms come to the host; bondi_violation_norms of such an object is this call, and bondi_violations up to ell_max = 16.  Every other object goes
+    through the series operators and norm(), as it always did."""
+    if not violations and not norms:
+        return None, None
+    if not _one_launch(self):
+        v = bondi_violations(self)
+        return (v if violations else None), ([x.norm() for x in v] if norms else None)
+    from .device_series import DeviceModesTimeSeries
+
+    raw, t, ctx = self._raw_dev, self.t, self._ctx  # psi0 .. psi4, sigma
+    d = lambda x, order: engine.spline_derivative(t, x, t, order, ctx=ctx)  # noqa: E731
+    # (bar commutes with the derivative: the kernel bars sigma_dot and sigma_ddot as it reads them)
+    out, nrm = engine.bondi_constraints(raw, [d(raw[0], 1), d(raw[1], 1), d(raw[2], 1)], d(raw[5], 1), d(raw[5], 2), self.ell_max,
+                                        want=range(6) if violations else (), norms=norms, ctx=ctx)
+    series = [DeviceModesTimeSeries(o, t, s, 0, self.ell_max, ctx=ctx, multiplication_truncator=self._truncator) for o, s in zip(out, _VIOLATION_SPINS)]
+    return (series if violations else None), ([np.ascontiguousarray(nrm[:, k]) for k in range(6)] if norms else None)
+
+
 def bondi_violations(self):
-    """lhs - rhs of the six relations (constraints.py:42-66)"""
+    """lhs - rhs of the six relations (constraints.py:42-66); of a device-resident object in one launch where bondi_gauge_check has one
+    and it was measured to be the quicker route (ell_max <= 16)"""
+    if self.ell_max <= _VIOLATIONS_ONE_LAUNCH_ELL_MAX and _one_launch(self):
+        return bondi_gauge_check(self, norms=False)[0]
     return [lhs - rhs for (lhs, rhs) in self.bondi_constraints(True, True)]
 
 
 def bondi_violation_norms(self):
     """L2 norm over the sphere of each violation, at every time (constraints.py:69-94)"""
+    if _one_launch(self):
+        return bondi_gauge_check(self, violations=False)[1]
     return [v.norm() for v in self.bondi_violations]
 
 
-METHODS = (bianchi_0, bianchi_1, bianchi_2, constraint_3, constraint_4, constraint_mass_aspect, bondi_constraints)
+METHODS = (bianchi_0, bianchi_1, bianchi_2, constraint_3, constraint_4, constraint_mass_aspect, bondi_constraints, bondi_gauge_check)

@@ -13,7 +13,7 @@
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
 //   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair, Bondi charges (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets, bms_bondi_charges)
-//   engine_product.hip   products of two mode rows on Gauss-Legendre rows, mass aspect and supermomenta          (bms_mode_product, bms_supermomenta, bms_product_tables)
+//   engine_product.hip   products of two mode rows on Gauss-Legendre rows, mass aspect and supermomenta          (bms_mode_product, bms_supermomenta, bms_bondi_constraints, bms_product_tables)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -661,7 +661,7 @@ inline int entry_mem(bms_ctx* c, int mem, const char* who = nullptr, bool select
 // stream instead, so that no queued work still reads or writes the caller's arrays when the error is returned (before this struct
 // such exits returned at once: the one change of behaviour it brings, on failure paths only).  No heap allocation: MAX_BACK records.
 struct CallIO {
-  static constexpr int MAX_BACK = 5;
+  static constexpr int MAX_BACK = 7;
   struct Back {
     void* dst;
     const void* dev;
@@ -767,7 +767,7 @@ BMS_INTERNAL void build_charge_image(int ell_max, std::vector<double>& image);
 BMS_INTERNAL int charge_checks(bms_ctx* c, const double* t, const void* psi1, int64_t ld_psi1, const void* psi2, int64_t ld_psi2, const void* sigma,
                                int64_t ld_sigma, const void* sigma_dot, int64_t ld_sigma_dot, int64_t n_times, int ell_max, int mem,
                                const double* four_momentum, const double* angular, const double* boost, const double* com, int* n_modes);
-// engine_product.hip: the Gauss-Legendre nodes and lambda tables of the products (long double, rounded once) and what the two entries refuse
+// engine_product.hip: the Gauss-Legendre nodes and lambda tables of the products (long double, rounded once) and what the three entries refuse
 // before they select a device
 BMS_INTERNAL void build_product_table(int spin, int ell_max, int n_nodes, bool weighted, double* cos_theta, double* weights, std::vector<double>& table);
 BMS_INTERNAL int product_checks(bms_ctx* c, const void* a, int64_t ld_a, int spin_a, int ell_max_a, int conj_a, const void* b, int64_t ld_b, int spin_b,
@@ -776,6 +776,8 @@ BMS_INTERNAL int supermomenta_checks(bms_ctx* c, const void* psi2, int64_t ld_ps
                                      int64_t ld_sigma_dot, int64_t n_times, int ell_max, int ell_max_out, int mem, const void* bondi_sachs,
                                      const void* moreschi, const void* geroch, const void* geroch_winicour, const void* mass_aspect, int64_t ld_out,
                                      int* n_nodes);
+BMS_INTERNAL int constraint_checks(bms_ctx* c, const void* const in[CONSTRAINT_INPUTS], const int64_t ld[CONSTRAINT_INPUTS], int64_t n_times, int ell_max,
+                                   int mem, const void* const violations[6], int64_t ld_out, const double* norms, unsigned* reads, int* n_nodes);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

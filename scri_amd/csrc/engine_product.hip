@@ -1,6 +1,6 @@
 // Products of spin-weighted functions on Gauss-Legendre rows (kernels_product.hip): the nodes and weights (Newton iteration on P_n) and the
 // tables lambda^s_lm(theta_j) = sYlm(theta_j, 0), built on the host in long double and rounded once, kept on the device per context and
-// (spin, ell_max, n_nodes); the entries bms_mode_product and bms_supermomenta, their launch shape and the pure host export of the tables
+// (spin, ell_max, n_nodes); the entries bms_mode_product, bms_supermomenta and bms_bondi_constraints, their launch shape and the pure host export of the tables
 // (engine.h: the split of the engine by entry family; include/scri_amd.h: the C ABI)
 #include "engine.h"
 
@@ -264,5 +264,104 @@ extern "C" int bms_supermomenta(bms_ctx* c, const void* psi2, int64_t ld_psi2, c
     if ((rc = io.out_rows(block[k], home[k], (size_t)n_times, (size_t)2 * n_o, (size_t)2 * ld_out, &d_out[k]))) return rc;
   TIMED(c, BMS_TAG_POINTWISE, launch_supermomenta(c->stream, d_p, ld_psi2, d_s, ld_sigma, d_d, ld_sigma_dot, n_times, ell_max, ell_max_out, integrated, t_p, t_m,
                                                   t_o, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], io.host() ? n_o : ld_out));
+  return io.finish();
+} BMS_CATCH(c)
+
+// ---- the six Bondi-gauge violations and their norms (constraint_kernel)
+namespace {
+
+constexpr int N_VIOLATIONS = 6;
+const char* const CONSTRAINT_INPUT_NAME[CONSTRAINT_INPUTS] = {"psi0", "psi1", "psi2", "psi3", "psi4", "sigma", "psi0_dot", "psi1_dot", "psi2_dot", "sigma_dot", "sigma_ddot"};
+// bit i: violation k reads input i (kernels.h: psi0 .. psi4, sigma, the three psi_dot, sigma_dot, sigma_ddot)
+constexpr unsigned CONSTRAINT_READS[N_VIOLATIONS] = {
+    1u << 1 | 1u << 2 | 1u << 5 | 1u << 6, 1u << 2 | 1u << 3 | 1u << 5 | 1u << 7, 1u << 3 | 1u << 4 | 1u << 5 | 1u << 8,
+    1u << 3 | 1u << 9,                     1u << 4 | 1u << 10,                    1u << 2 | 1u << 5 | 1u << 9};
+
+}  // namespace
+
+// what bms_bondi_constraints refuses before it selects a device; in[] / ld[] in the order of kernels.h.  *reads: the inputs the outputs asked for read
+BMS_INTERNAL int constraint_checks(bms_ctx* c, const void* const in[CONSTRAINT_INPUTS], const int64_t ld[CONSTRAINT_INPUTS], int64_t n_times, int ell_max,
+                                   int mem, const void* const violations[6], int64_t ld_out, const double* norms, unsigned* reads, int* n_nodes) {
+  const char* who = "bms_bondi_constraints";
+  unsigned need = 0;
+  bool any = norms != nullptr;
+  for (int k = 0; k < N_VIOLATIONS; ++k)
+    if (norms || violations[k]) need |= CONSTRAINT_READS[k], any = any || violations[k];
+  if (!any) return fail(c, BMS_ERR_INVALID, "%s: every output is NULL", who);
+  for (int i = 0; i < CONSTRAINT_INPUTS; ++i)
+    if ((need >> i & 1) && !in[i]) return fail(c, BMS_ERR_INVALID, "%s: NULL %s, which an output asked for reads", who, CONSTRAINT_INPUT_NAME[i]);
+  if (n_times < 0) return fail(c, BMS_ERR_INVALID, "%s: negative n_times", who);
+  if (ell_max < 0) return fail(c, BMS_ERR_INVALID, "%s: negative ell_max", who);
+  if (ell_max < 2) return fail(c, BMS_ERR_UNSUPPORTED, "%s: ell_max = %d: the shear starts at ell = 2", who, ell_max);
+  if (int rc = product_size_checks(c, who, 2, ell_max, -2, ell_max, ell_max, n_times, n_nodes)) return rc;
+  const int64_t n_modes = LM_total_size(0, ell_max);
+  uintptr_t bits = (uintptr_t)norms & 7 ? 15 : 0;  // (norms are doubles; the rest complex)
+  for (int i = 0; i < CONSTRAINT_INPUTS; ++i)
+    if (need >> i & 1) {
+      if (ld[i] < n_modes) return fail(c, BMS_ERR_INVALID, "%s: row stride of %s smaller than the number of modes (%d)", who, CONSTRAINT_INPUT_NAME[i], (int)n_modes);
+      bits |= (uintptr_t)in[i];
+    }
+  for (int k = 0; k < N_VIOLATIONS; ++k)
+    if (violations[k]) {
+      if (ld_out < n_modes) return fail(c, BMS_ERR_INVALID, "%s: row stride of the violations smaller than the (ell_max + 1)^2 = %d columns written", who, (int)n_modes);
+      bits |= (uintptr_t)violations[k];
+    }
+  if (mem == BMS_DEVICE && (bits & 15)) return fail(c, BMS_ERR_INVALID, "%s: device arrays must be aligned to their elements", who);
+  *reads = need;
+  return BMS_OK;
+}
+
+extern "C" int bms_bondi_constraints(bms_ctx* c, const void* const fields[6], const int64_t ld_fields[6], const void* const psi_dot[3],
+                                     const int64_t ld_psi_dot[3], const void* sigma_dot, int64_t ld_sigma_dot, const void* sigma_ddot,
+                                     int64_t ld_sigma_ddot, int64_t n_times, int ell_max, int mem, void* const violations[6], int64_t ld_out,
+                                     double* norms) try {
+  if (!c) return BMS_ERR_INVALID;
+  const char* who = "bms_bondi_constraints";
+  if (int rc0 = entry_mem(c, mem, who, false)) return rc0;  // (the argument checks come before the device is selected)
+  if (!fields || !ld_fields || !psi_dot || !ld_psi_dot) return fail(c, BMS_ERR_INVALID, "%s: NULL list of fields, of psi_dot or of their row strides", who);
+  const void* in[CONSTRAINT_INPUTS];
+  int64_t ld[CONSTRAINT_INPUTS];
+  for (int i = 0; i < 6; ++i) in[i] = fields[i], ld[i] = ld_fields[i];
+  for (int i = 0; i < 3; ++i) in[CONSTRAINT_PSI_DOT + i] = psi_dot[i], ld[CONSTRAINT_PSI_DOT + i] = ld_psi_dot[i];
+  in[CONSTRAINT_SIGMA_DOT] = sigma_dot, ld[CONSTRAINT_SIGMA_DOT] = ld_sigma_dot;
+  in[CONSTRAINT_SIGMA_DDOT] = sigma_ddot, ld[CONSTRAINT_SIGMA_DDOT] = ld_sigma_ddot;
+  void* const none[N_VIOLATIONS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  void* const* home = violations ? violations : none;
+  int rc, n_nodes = 0;
+  unsigned reads = 0;
+  if ((rc = constraint_checks(c, in, ld, n_times, ell_max, mem, home, ld_out, norms, &reads, &n_nodes))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  ProductShape S;
+  if (!product_launch_shape(ell_max, ell_max, ell_max, &S))
+    return fail(c, BMS_ERR_UNSUPPORTED, "%s: ell_max %d on %d rows: the rows and panels of one time step do not fit in LDS", who, ell_max, n_nodes);
+  ConstraintArgs Q{};
+  Q.l_max = ell_max, Q.n_nodes = n_nodes;
+  // sigma's table and, for each product an output asked for needs, its operand's (spins 0, -1, -2) and its own (spins 2, 1, 0, weighted)
+  const bool product[3] = {norms || home[0], norms || home[1], norms || home[2] || home[5]};
+  if (product[0] || product[1] || product[2])
+    if ((rc = ensure_product_table(c, 2, ell_max, n_nodes, false, &Q.tab_sigma))) return rc;
+  for (int t = 0; t < 3; ++t)
+    if (product[t]) {
+      if ((rc = ensure_product_table(c, -t, ell_max, n_nodes, false, &Q.tab_in[t]))) return rc;
+      if ((rc = ensure_product_table(c, 2 - t, ell_max, n_nodes, true, &Q.tab_out[t]))) return rc;
+    }
+  const int n_modes = LM_total_size(0, ell_max);
+  CallIO io(c, mem);
+  for (int i = 0; i < CONSTRAINT_INPUTS; ++i)
+    if (reads >> i & 1) {
+      char block[32];
+      snprintf(block, sizeof block, "constraint_in%d", i);
+      if ((rc = io.in(block, in[i], ((size_t)(n_times - 1) * ld[i] + n_modes) * 16, &Q.in[i]))) return rc;
+      Q.ld[i] = ld[i];
+    }
+  for (int k = 0; k < N_VIOLATIONS; ++k) {
+    char block[32];
+    snprintf(block, sizeof block, "constraint_v%d", k);
+    if ((rc = io.out_rows(block, home[k], (size_t)n_times, (size_t)2 * n_modes, (size_t)2 * ld_out, &Q.v[k]))) return rc;
+  }
+  if ((rc = io.out("constraint_norms", norms, (size_t)n_times * N_VIOLATIONS, &Q.norms))) return rc;
+  Q.ld_out = io.host() ? n_modes : ld_out;
+  TIMED(c, BMS_TAG_CONSTRAINTS, launch_bondi_constraints(c->stream, Q, n_times));
   return io.finish();
 } BMS_CATCH(c)

@@ -506,6 +506,21 @@ hipError_t launch_supermomenta(hipStream_t stream, const double* psi2, long long
                                const double* sigma_dot, long long ld_sigma_dot, long long n_times, int ell_max, int l_out, int integrated,
                                const double* tab_plus, const double* tab_minus, const double* tab_out, double* bondi_sachs, double* moreschi,
                                double* geroch, double* geroch_winicour, double* mass_aspect, long long ld_out);
+// The six Bondi-gauge violations and their norms in one launch (constraint_kernel: the same stages, sigma's theta sums taken once).  Rows
+// c16[n][ld] from l = 0; an input that no output asked for reads may be null.  v[k] c16[n][ld_out] and norms f8[n][6]: any may be null, not all.
+enum { CONSTRAINT_SIGMA = 5, CONSTRAINT_PSI_DOT = 6, CONSTRAINT_SIGMA_DOT = 9, CONSTRAINT_SIGMA_DDOT = 10, CONSTRAINT_INPUTS = 11 };
+struct ConstraintArgs {
+  const double* in[CONSTRAINT_INPUTS];  // psi0 .. psi4, sigma; d/du of psi0, psi1, psi2; d/du and d2/du2 of sigma (psi0 itself is never read)
+  long long ld[CONSTRAINT_INPUTS];
+  int l_max, n_nodes;         // n_nodes = product_nodes(l_max, l_max, l_max)
+  const double* tab_sigma;    // lambda table of spin 2
+  const double* tab_in[3];    // of spins 0, -1, -2: psi2, psi3, psi4 and bar(sigma_dot)
+  const double* tab_out[3];   // of spins 2, 1, 0 with 2 pi w_j folded
+  double* v[6];
+  long long ld_out;
+  double* norms;
+};
+hipError_t launch_bondi_constraints(hipStream_t stream, const ConstraintArgs& Q, long long n_times);
 // out c16[n] = sum_e op(a[t][rows_e]) values_e b[t][cols_e] for triplets on the device, indices inside [0, n_cols) (the entry checks them)
 int expectation_max_cols();
 hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,

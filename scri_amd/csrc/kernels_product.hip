@@ -67,6 +67,40 @@ __device__ __forceinline__ void theta_sums(double2* panel, const double2* row, c
   }
 }
 
+// pan_g[j][M + l_out] = sum_m1 A[j][m1] B[j][M - m1], m1 = max(-l_a, M - l_b) .. min(l_a, M + l_b) ascending
+__device__ __forceinline__ void convolution(double2* pan_g, const double2* pan_a, int l_a, const double2* pan_b, int l_b, int l_out, int n_nodes) {
+  const int wa = 2 * l_a + 1, wb = 2 * l_b + 1, wo = 2 * l_out + 1;
+  for (int idx = threadIdx.x; idx < n_nodes * wo; idx += PRODUCT_THREADS) {
+    const int j = idx / wo, M = idx - j * wo - l_out;
+    const double2* A = pan_a + j * wa + l_a;
+    const double2* B = pan_b + j * wb + l_b;
+    const int lo = -l_a > M - l_b ? -l_a : M - l_b, hi = l_a < M + l_b ? l_a : M + l_b;
+    double re = 0.0, im = 0.0;
+    for (int m1 = lo; m1 <= hi; ++m1) {
+      const double2 x = A[m1], y = B[M - m1];
+      re = fma(x.x, y.x, re);
+      re = fma(-x.y, y.y, re);
+      im = fma(x.x, y.y, im);
+      im = fma(x.y, y.x, im);
+    }
+    pan_g[idx] = double2{re, im};
+  }
+}
+
+// column c = (l, M) of the product: sum_j tab_out[j][c] pan_g[j][M + l_out], j ascending; an exact zero below l = |S|
+__device__ __forceinline__ double2 quadrature(const double2* pan_g, const double* __restrict__ tab_out, int c, int l, int l_out, int S_abs, int n_nodes) {
+  const int M = c - l * (l + 1), no = (l_out + 1) * (l_out + 1), wo = 2 * l_out + 1;
+  double re = 0.0, im = 0.0;
+  if (l >= S_abs)
+    for (int j = 0; j < n_nodes; ++j) {
+      const double w = tab_out[(long long)j * no + c];
+      const double2 g = pan_g[j * wo + M + l_out];
+      re = fma(w, g.x, re);
+      im = fma(w, g.y, im);
+    }
+  return double2{re, im};
+}
+
 struct ProductOperands {
   const double *a, *b;    // rows c16[n_times][ld]
   long long ld_a, ld_b;
@@ -91,7 +125,7 @@ __global__ __launch_bounds__(PRODUCT_THREADS) void product_kernel(ProductOperand
   const int l_a = P.l_a, l_b = SUPER ? P.l_a : P.l_b, l_out = P.l_out, n = P.n_nodes;
   const int spin_a = SUPER ? 2 : P.spin_a, spin_b = SUPER ? 2 : P.spin_b, conj_a = SUPER ? 0 : P.conj_a, conj_b = SUPER ? 1 : P.conj_b;
   const int na = (l_a + 1) * (l_a + 1), nb = (l_b + 1) * (l_b + 1), no = (l_out + 1) * (l_out + 1);
-  const int wa = 2 * l_a + 1, wb = 2 * l_b + 1, wo = 2 * l_out + 1;
+  const int wa = 2 * l_a + 1, wb = 2 * l_b + 1;
   double2* row_a = product_lds;
   double2* row_b = row_a + na;
   double2* row_o = row_b + nb;
@@ -106,36 +140,14 @@ __global__ __launch_bounds__(PRODUCT_THREADS) void product_kernel(ProductOperand
     theta_sums(pan_a, row_a, P.tab_a, l_a, s_a, n);
     theta_sums(pan_b, row_b, P.tab_b, l_b, s_b, n);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < n * wo; idx += PRODUCT_THREADS) {
-      const int j = idx / wo, M = idx - j * wo - l_out;
-      const double2* A = pan_a + j * wa + l_a;
-      const double2* B = pan_b + j * wb + l_b;
-      const int lo = -l_a > M - l_b ? -l_a : M - l_b, hi = l_a < M + l_b ? l_a : M + l_b;
-      double re = 0.0, im = 0.0;
-      for (int m1 = lo; m1 <= hi; ++m1) {
-        const double2 x = A[m1], y = B[M - m1];
-        re = fma(x.x, y.x, re);
-        re = fma(-x.y, y.y, re);
-        im = fma(x.x, y.y, im);
-        im = fma(x.y, y.x, im);
-      }
-      pan_g[idx] = double2{re, im};
-    }
+    convolution(pan_g, pan_a, l_a, pan_b, l_b, l_out, n);
     __syncthreads();
     for (int c = threadIdx.x; c < no; c += PRODUCT_THREADS) {
-      const int l = ell_of_column(c), M = c - l * (l + 1);
-      double re = 0.0, im = 0.0;
-      if (l >= S_abs)
-        for (int j = 0; j < n; ++j) {
-          const double w = P.tab_out[(long long)j * no + c];
-          const double2 g = pan_g[j * wo + M + l_out];
-          re = fma(w, g.x, re);
-          im = fma(w, g.y, im);
-        }
+      const double2 p = quadrature(pan_g, P.tab_out, c, ell_of_column(c), l_out, S_abs, n);
       if (SUPER)
-        row_o[c] = double2{re, im};
+        row_o[c] = p;
       else
-        *reinterpret_cast<double2*>(out + 2 * (step * ld_out + c)) = double2{re, im};
+        *reinterpret_cast<double2*>(out + 2 * (step * ld_out + c)) = p;
     }
     if (SUPER) {
       __syncthreads();
@@ -179,6 +191,129 @@ __global__ __launch_bounds__(PRODUCT_THREADS) void product_kernel(ProductOperand
       }
     }
     __syncthreads();  // (the rows and panels of this step are read until here)
+  }
+}
+
+// the factor of the GHP eth on a row of spin s: sqrt((l - s)(l + s + 1)) / sqrt(2), zero where l is below |s| or |s + 1|
+__device__ __forceinline__ double eth_ghp_factor(int l, int s) {
+  const int s_abs = s < 0 ? -s : s, up_abs = s + 1 < 0 ? -(s + 1) : s + 1;
+  if (l < s_abs || l < up_abs) return 0.0;
+  return sqrt((double)((l - s) * (l + s + 1))) / 0x1.6a09e667f3bcdp+0;  // (the double sqrt(2), as the host's factor tables divide by it)
+}
+
+__device__ __forceinline__ double2 bar_of(double2 x, int spin_plus_m) { return (spin_plus_m & 1) ? double2{-x.x, x.y} : double2{x.x, -x.y}; }
+
+// The six Bondi-gauge violations of one time step and their norms (scri/asymptotic_bondi_data/constraints.py):
+//     v0 = psi0' - eth psi1 - 3 sigma psi2     v1 = psi1' - eth psi2 - 2 sigma psi3     v2 = psi2' - eth psi3 - sigma psi4
+//     v3 = psi3 + eth bar(sigma')              v4 = psi4 + bar(sigma'')                 v5 = Im[psi2 + eth^2 bar(sigma) + sigma bar(sigma')]
+// with the GHP eth, the primes given as rows, Im(x) = -i (x - bar x) / 2.  The four products share sigma: its row and its theta sums are
+// taken once, then each second operand (psi2, psi3, psi4, bar(sigma'): spins 0, -1, -2, -2) goes through the stages of product_kernel on the
+// same two panels.  v0, v1, v2 finish column by column out of the quadrature; sigma bar(sigma') stays in LDS for its mirror column.  The
+// diagonal terms are read from memory as stored.  LDS: the rows and panels of product_kernel at (l, l, l), nothing more.
+// Norms: thread t adds |v_k[c]|^2 = re re + im im over its columns c = t, t + 256, ... ascending; the 256 partials of each k are added in
+// LDS (rows and panels are free by then) in the tree stride = 128, 64, ... 1, red[t] += red[t + stride]; thread 0 takes the root.
+// A product is formed only if an output asked for needs it, and no output depends on which others are asked for.
+__global__ __launch_bounds__(PRODUCT_THREADS) void constraint_kernel(ConstraintArgs Q, long long n_times) {
+#pragma clang fp contract(off)
+  extern __shared__ double2 product_lds[];
+  const int l_max = Q.l_max, n = Q.n_nodes, nc = (l_max + 1) * (l_max + 1), width = 2 * l_max + 1;
+  double2* row_s = product_lds;  // sigma
+  double2* row_b = row_s + nc;   // the second operand of the product at hand
+  double2* row_o = row_b + nc;   // sigma bar(sigma')
+  double2* pan_s = row_o + nc;
+  double2* pan_b = pan_s + n * width;
+  double2* pan_g = pan_b + n * width;
+  double* red = reinterpret_cast<double*>(product_lds);  // [6][PRODUCT_THREADS], once the step's rows and panels are done with
+  const bool norms = Q.norms != nullptr;
+  // bit p: the product of sigma with psi2, psi3, psi4, bar(sigma') is needed (by v0, v1, v2, v5)
+  const int need = norms ? 15 : (Q.v[0] ? 1 : 0) | (Q.v[1] ? 2 : 0) | (Q.v[2] ? 4 : 0) | (Q.v[5] ? 8 : 0);
+  for (long long step = blockIdx.x; step < n_times; step += gridDim.x) {  // (uniform in the workgroup: every wave takes every barrier)
+    auto at = [&](int which, int col) { return *reinterpret_cast<const double2*>(Q.in[which] + 2 * (step * Q.ld[which] + col)); };
+    auto put = [&](double* dst, int col, double2 v) {
+      if (dst) *reinterpret_cast<double2*>(dst + 2 * (step * Q.ld_out + col)) = v;
+      const double sq = v.x * v.x;
+      return sq + v.y * v.y;
+    };
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0, n4 = 0.0, n5 = 0.0;
+    if (need) {
+      load_row(row_s, Q.in[CONSTRAINT_SIGMA] + 2 * step * Q.ld[CONSTRAINT_SIGMA], nc, 2, 0);
+      __syncthreads();
+      theta_sums(pan_s, row_s, Q.tab_sigma, l_max, 2, n);
+    }
+#pragma unroll 1
+    for (int p = 0; p < 4; ++p) {  // sigma times psi2, psi3, psi4, bar(sigma')
+      if (!((need >> p) & 1)) continue;
+      const int t = p < 3 ? p : 2, operand = p < 3 ? p + 2 : CONSTRAINT_SIGMA_DOT;  // the operand has spin -t, the product spin 2 - t
+      load_row(row_b, Q.in[operand] + 2 * step * Q.ld[operand], nc, p < 3 ? -p : 2, p == 3);
+      __syncthreads();
+      theta_sums(pan_b, row_b, Q.tab_in[t], l_max, -t, n);
+      __syncthreads();
+      convolution(pan_g, pan_s, l_max, pan_b, l_max, l_max, n);
+      __syncthreads();
+      double acc = 0.0;
+      for (int c = threadIdx.x; c < nc; c += PRODUCT_THREADS) {
+        const double2 prod = quadrature(pan_g, Q.tab_out[t], c, ell_of_column(c), l_max, 2 - t, n);
+        if (p == 3) {
+          row_o[c] = prod;
+          continue;
+        }
+        // v_p = psi_p' - (eth psi_{p+1} + (3 - p) sigma psi_{p+2})
+        const double f = eth_ghp_factor(ell_of_column(c), 1 - p), times = (double)(3 - p);
+        const double2 d = at(CONSTRAINT_PSI_DOT + p, c), q = at(p + 1, c);
+        const double2 rhs = double2{f * q.x + times * prod.x, f * q.y + times * prod.y};
+        acc = acc + put(Q.v[p], c, double2{d.x - rhs.x, d.y - rhs.y});
+      }
+      if (p == 0) n0 = acc;
+      if (p == 1) n1 = acc;
+      if (p == 2) n2 = acc;
+    }
+#pragma unroll 1
+    for (int k = 3; k < 5; ++k) {  // v3 = psi3 + eth bar(sigma'), v4 = psi4 + bar(sigma'')
+      if (!norms && !Q.v[k]) continue;
+      double acc = 0.0;
+      for (int c = threadIdx.x; c < nc; c += PRODUCT_THREADS) {
+        const int l = ell_of_column(c), m = c - l * (l + 1);
+        const double2 b = bar_of(at(CONSTRAINT_SIGMA_DOT + k - 3, l * (l + 1) - m), 2 + m), q = at(k, c);
+        if (k == 3) {
+          const double f = eth_ghp_factor(l, -2);
+          acc = acc + put(Q.v[k], c, double2{q.x + f * b.x, q.y + f * b.y});
+        } else {
+          acc = acc + put(Q.v[k], c, double2{q.x + b.x, q.y + b.y});
+        }
+      }
+      if (k == 3) n3 = acc;
+      if (k == 4) n4 = acc;
+    }
+    if (need & 8) {
+      __syncthreads();
+      // x = psi2 + eth eth bar(sigma) + sigma bar(sigma') at (l, m): one chain of operations, whichever thread forms it
+      auto x_at = [&](int l, int m) -> double2 {
+        const int col = l * (l + 1) + m;
+        const double f1 = eth_ghp_factor(l, -2), f2 = eth_ghp_factor(l, -1);
+        const double2 b = bar_of(row_s[l * (l + 1) - m], 2 + m), q = at(2, col), prod = row_o[col];
+        return double2{(q.x + f2 * (f1 * b.x)) + prod.x, (q.y + f2 * (f1 * b.y)) + prod.y};
+      };
+      for (int c = threadIdx.x; c < nc; c += PRODUCT_THREADS) {
+        const int l = ell_of_column(c), m = c - l * (l + 1);
+        const double2 x = x_at(l, m), xb = bar_of(x_at(l, -m), m);
+        n5 = n5 + put(Q.v[5], c, double2{0.5 * (x.y - xb.y), -0.5 * (x.x - xb.x)});  // -i (x - bar x) / 2
+      }
+    }
+    if (norms) {
+      __syncthreads();  // (rows and panels are read until here)
+      const int t = threadIdx.x;
+      red[t] = n0, red[PRODUCT_THREADS + t] = n1, red[2 * PRODUCT_THREADS + t] = n2;
+      red[3 * PRODUCT_THREADS + t] = n3, red[4 * PRODUCT_THREADS + t] = n4, red[5 * PRODUCT_THREADS + t] = n5;
+#pragma unroll 1
+      for (int stride = PRODUCT_THREADS / 2; stride > 0; stride >>= 1) {
+        __syncthreads();
+        if (t < stride)
+          for (int k = 0; k < 6; ++k) red[k * PRODUCT_THREADS + t] = red[k * PRODUCT_THREADS + t] + red[k * PRODUCT_THREADS + t + stride];
+      }
+      if (t == 0)
+        for (int k = 0; k < 6; ++k) Q.norms[6 * step + k] = sqrt(red[k * PRODUCT_THREADS]);
+    }
+    __syncthreads();  // (the rows, panels and partial sums of this step are read until here)
   }
 }
 
@@ -250,6 +385,22 @@ hipError_t launch_supermomenta(hipStream_t stream, const double* psi2, long long
                           tab_plus, tab_minus, tab_out};
   const SuperOutputs Q{psi2, ld_psi2, ld_out, bondi_sachs, moreschi, geroch, geroch_winicour, mass_aspect};
   return launch_product(stream, P, n_times, nullptr, 0, &Q, integrated != 0);
+}
+
+hipError_t launch_bondi_constraints(hipStream_t stream, const ConstraintArgs& Q, long long n_times) {
+  if (n_times <= 0) return hipSuccess;
+  ProductShape S;
+  if (Q.l_max < 2 || Q.n_nodes != product_nodes(Q.l_max, Q.l_max, Q.l_max) || !product_launch_shape(Q.l_max, Q.l_max, Q.l_max, &S))
+    return hipErrorInvalidValue;
+  if (!Q.norms && !Q.v[0] && !Q.v[1] && !Q.v[2] && !Q.v[3] && !Q.v[4] && !Q.v[5]) return hipErrorInvalidValue;
+  // (the partial sums of the norms lie over the rows and panels: six doubles per thread, which only ell_max <= 7 falls short of)
+  const size_t lds = std::max(S.lds_bytes, sizeof(double) * 6 * PRODUCT_THREADS);
+  if (lds > 64 * 1024) {
+    hipError_t e = allow_dynamic_lds((const void*)constraint_kernel);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(constraint_kernel, dim3((unsigned)std::min<long long>(S.groups, n_times)), dim3(PRODUCT_THREADS), lds, stream, Q, n_times);
+  return hipGetLastError();
 }
 
 }  // namespace bms

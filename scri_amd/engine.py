@@ -1302,6 +1302,54 @@ def supermomenta(psi2, sigma, sigma_dot, ell_max, ell_max_out=None, want=SUPERMO
     return res[0] if isinstance(want, str) else res
 
 
+# the inputs each violation of bms_bondi_constraints reads, as indices into (psi0 .. psi4, sigma, psi0_dot, psi1_dot, psi2_dot, sigma_dot, sigma_ddot)
+_CONSTRAINT_READS = ((1, 2, 5, 6), (2, 3, 5, 7), (3, 4, 5, 8), (3, 9), (4, 10), (2, 5, 9))
+_CONSTRAINT_INPUTS = ("psi0", "psi1", "psi2", "psi3", "psi4", "sigma", "psi0_dot", "psi1_dot", "psi2_dot", "sigma_dot", "sigma_ddot")
+
+
+def bondi_constraints(fields, psi_dot, sigma_dot, sigma_ddot, ell_max, want=(0, 1, 2, 3, 4, 5), norms=True, ctx=None):
+    """bms_bondi_constraints: the violations of the six Bondi-gauge relations named in `want` (0 .. 5: the three Bianchi identities, psi3,
+    psi4 and the imaginary part of the mass aspect; scri/asymptotic_bondi_data/constraints.py) and, with norms=True, the L2 norms of all
+    six, in one launch.  fields: psi0 .. psi4, sigma (six arrays or one [6, N, (ell_max + 1)^2]); psi_dot: d/du of psi0, psi1, psi2;
+    sigma_dot, sigma_ddot: the first and second derivative of sigma; each [N, (ell_max + 1)^2] from l = 0, numpy arrays or device
+    tensors (complex128, unit column stride, any row stride), all in one memory.  An input that nothing asked for reads may be None
+    (psi0 never is read).  Returns (violations, norms): a tuple in the order of `want` -- numpy arrays, or device tensors for device
+    inputs -- and a host array [N, 6] (None with norms=False)."""
+    ctx = _ctx(ctx)
+    want = tuple(int(k) for k in want)
+    if len(set(want)) != len(want) or not set(want) <= set(range(6)):
+        raise ValueError(f"want names violations 0 .. 5, each once; got {want!r}")
+    if not want and not norms:
+        raise ValueError("neither a violation nor the norms are asked for")
+    ell_max = int(ell_max)
+    n_modes = (ell_max + 1) ** 2
+    given = list(fields) + list(psi_dot) + [sigma_dot, sigma_ddot]
+    if len(given) != 11:
+        raise ValueError("fields holds psi0 .. psi4 and sigma, psi_dot the derivatives of psi0, psi1, psi2")
+    read = set(range(1, 11)) if norms else {i for k in want for i in _CONSTRAINT_READS[k]}
+    staged, first = [None] * 11, None
+    for i in sorted(read):
+        if given[i] is None:
+            raise ValueError(f"the outputs asked for need {_CONSTRAINT_INPUTS[i]}")
+        staged[i] = _stage(ctx, given[i], np.complex128, _CONSTRAINT_INPUTS[i], shape=(None if first is None else first.rows, n_modes))
+        first = first if first is not None else staged[i]
+        if staged[i].mem != first.mem:
+            raise ValueError("the fields and their derivatives must live in the same memory")
+    out = {k: out_like(first, (first.rows, n_modes), np.complex128) for k in want}
+    norm_ptr, norm_out = out_like(first, (first.rows, 6), float) if norms else (None, None)
+    if first.rows:
+        ptrs = lambda idx: (c_vp * len(idx))(*(staged[i].ptr if staged[i] is not None else None for i in idx))  # noqa: E731
+        lds = lambda idx: (c_i64 * len(idx))(*(staged[i].ld if staged[i] is not None else 0 for i in idx))  # noqa: E731
+        dot = lambda i: (staged[i].ptr, staged[i].ld) if staged[i] is not None else (None, 0)  # noqa: E731
+        homes = (c_vp * 6)(*(out[k][0] if k in out else None for k in range(6)))
+        rc = _lib.load().bms_bondi_constraints(ctx.handle, ptrs(range(6)), lds(range(6)), ptrs(range(6, 9)), lds(range(6, 9)), *dot(9), *dot(10),
+                                               first.rows, ell_max, first.mem, homes, n_modes, norm_ptr)
+        ctx.check(rc, "bms_bondi_constraints")
+    if norms and first.mem == BMS_DEVICE:
+        norm_out = norm_out.cpu().numpy()
+    return tuple(out[k][1] for k in want), norm_out
+
+
 PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
 
 

@@ -3,7 +3,7 @@
 // behind engine.h), so that every planning helper is instrumented -- host-only with -fsanitize=address,undefined and runs it: shard plans, output windows, knot ranges, column
 // parts, the chunk planner of the two transforms (plan_chunks, chunk_rows: caps that give 1, 2, 7 and several hundred chunks, the caps and shards it refuses), the pieces of the
 // pipelined calls, rotor / harmonic / conformal tables, the frame integrator, the argument checks of the device frame chain, of the rotor interpolation and of the alignment entries, the planner and the per-step
-// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, the coefficient tables of the fused fluxes and the walk over a list of triplets, the prologues of the entries that stage host or device arguments (entry_mem, CallIO), over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
+// math of the precessing sample waveform, the argument checks, column tables and pieces of the paired-XOR storage entries, the argument checks of the centre-of-mass entries, the refusals of bms_dense_product and of the two dense-product launchers, the coefficient tables of the fused fluxes and the walk over a list of triplets, the inputs the Bondi-gauge violations asked for read and what their entry refuses, the prologues of the entries that stage host or device arguments (entry_mem, CallIO), over the five BASELINE shapes, 1..8 shards, 1..8 column parts, series of 2..9 samples and odd grids.  Nothing here touches a device.
 #include "../../scri_amd/csrc/engine_context.hip"
 #include "../../scri_amd/csrc/engine_tables.hip"
 #include "../../scri_amd/csrc/engine_rotate.hip"
@@ -809,6 +809,43 @@ void flux_tables_and_triplets() {
   REQUIRE(bms_mode_product(&dummy, v, 9, 2, 2, 0, v, 16, -2, 3, 1, 0, 5, BMS_HOST, out, 36) == BMS_OK);
   REQUIRE(bms_supermomenta(&dummy, v, 9, v, 16, v, 16, 0, 3, 2, BMS_HOST, 1, out, out, out, out, out, 9) == BMS_OK);
   REQUIRE(bms_supermomenta(nullptr, v, 9, v, 16, v, 16, 4, 3, 2, BMS_HOST, 1, out, out, out, out, out, 9) == BMS_ERR_INVALID);
+  // the Bondi-gauge violations: which inputs the outputs asked for read, and what the entry refuses
+  {
+    const void* in[CONSTRAINT_INPUTS];
+    int64_t ld[CONSTRAINT_INPUTS];
+    for (int i = 0; i < CONSTRAINT_INPUTS; ++i) in[i] = v, ld[i] = 16;
+    const void* const all[6] = {out, out, out, out, out, out};
+    const void* const none[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const void* const third[6] = {nullptr, nullptr, nullptr, out, nullptr, nullptr};
+    unsigned reads = 0;
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, all, 16, out, &reads, &nn) == BMS_OK && nn == 5 && reads == 0x7feu);
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_OK && reads == (1u << 3 | 1u << 9));
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, none, 16, out, &reads, &nn) == BMS_OK && reads == 0x7feu);
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, none, 16, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("every output is NULL"));
+    in[0] = nullptr;  // psi0 is never read
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, all, 16, out, &reads, &nn) == BMS_OK);
+    in[9] = nullptr;
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("NULL sigma_dot"));
+    in[9] = v, ld[3] = 15;
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("row stride of psi3"));
+    ld[3] = 16, ld[10] = 15;  // (sigma_ddot is not read by v3)
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_OK);
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, third, 15, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("row stride of the violations"));
+    REQUIRE(constraint_checks(&dummy, in, ld, -1, 3, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("negative n_times"));
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, -1, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("negative ell_max"));
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 1, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_ERR_UNSUPPORTED && says("ell_max = 1"));
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, MAX_ELL + 1, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_ERR_UNSUPPORTED);
+    in[3] = v + 1;
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_DEVICE, third, 16, nullptr, &reads, &nn) == BMS_ERR_INVALID && says("aligned"));
+    REQUIRE(constraint_checks(&dummy, in, ld, 4, 3, BMS_HOST, third, 16, nullptr, &reads, &nn) == BMS_OK);
+    const int64_t ld6[6] = {16, 16, 16, 16, 16, 16};
+    void* const homes[6] = {out, out, out, out, out, out};
+    REQUIRE(bms_bondi_constraints(&dummy, in, ld6, in, ld6, v, 16, v, 16, 4, 3, 7, homes, 16, out) == BMS_ERR_INVALID && says("bms_bondi_constraints: mem is BMS_HOST or BMS_DEVICE, got 7"));
+    REQUIRE(bms_bondi_constraints(&dummy, nullptr, ld6, in, ld6, v, 16, v, 16, 4, 3, BMS_HOST, homes, 16, out) == BMS_ERR_INVALID && says("NULL list"));
+    REQUIRE(bms_bondi_constraints(&dummy, in + 1, ld6, in + 1, ld6, v, 16, v, 16, 0, 3, BMS_HOST, homes, 16, out) == BMS_OK);
+    REQUIRE(bms_bondi_constraints(&dummy, in + 1, ld6, in + 1, ld6, v, 16, v, 16, 4, 3, BMS_HOST, nullptr, 16, nullptr) == BMS_ERR_INVALID && says("every output"));
+    REQUIRE(bms_bondi_constraints(nullptr, in + 1, ld6, in + 1, ld6, v, 16, v, 16, 4, 3, BMS_HOST, homes, 16, out) == BMS_ERR_INVALID);
+  }
 }
 
 }  // namespace
