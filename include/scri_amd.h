@@ -126,7 +126,8 @@ enum bms_kernel_tag {
   BMS_TAG_ANALYSIS_FUSED = 8,   /* analysis_split_kernel / analysis_fused_kernel (phi-DFT on MFMA + theta quadrature, one kernel) */
   BMS_TAG_ANALYSIS_LARGE = 9,   /* phi_dft_folded_kernel + theta_quadrature_mfma_kernel (grids with n_theta > 40) */
   BMS_TAG_CONSTRAINTS = 10,     /* constraint_kernel (bms_bondi_constraints) */
-  BMS_TAG_COUNT = 11
+  BMS_TAG_CUT = 11,             /* cut_kernel and the pointwise kernels around it (bms_supermomentum_on_cut, bms_alpha_perturbation) */
+  BMS_TAG_COUNT = 12
 };
 int bms_ctx_enable_timing(bms_ctx* ctx, int on);
 int bms_ctx_get_timing(bms_ctx* ctx, double ms[BMS_TAG_COUNT], int64_t calls[BMS_TAG_COUNT], int reset);
@@ -737,6 +738,39 @@ int64_t bms_product_launch_shape(int ell_max_a, int ell_max_b, int ell_max_out, 
  * f8[n_nodes][(ell_max + 1)^2] of sYlm(theta_j, 0) for spin s = `spin` (|spin| <= 4; zero for l < |s|) as the kernel reads it -- the
  * output spin's table is this one times 2 pi w_j, formed in long double before the one rounding */
 int bms_product_tables(int spin, int ell_max, int n_nodes, double* cos_theta, double* weights, double* table);
+
+/* ---- Cuts: a series of spin-0 modes on the supertranslated cut u = alpha(theta, phi) (scri/asymptotic_bondi_data/map_to_superrest_frame.py:108-224)
+ * N = 2 ell_max + 1, the grid is the equiangular one of bms_salm2map (theta_i = pi i / (N - 1), phi_j = 2 pi j / N), nm = (ell_max + 1)^2.
+ *
+ * bms_supermomentum_on_cut: t host f8[n] strictly increasing; psi c16[n][ld] in `mem`, columns from l = 0 (the Moreschi supermomentum
+ * Psi_M); alpha host f8[N][N], finite.  The window is rows [lo, hi), lo = (number of t <= min alpha) - 1 - 64, hi = (number of t < max alpha)
+ * + 1 + 64, clipped to [0, n]: the not-a-knot cubic splines are taken through these rows only and nothing outside them is read.
+ *   psi_at_alpha[p] = Re sum_lm Y_lm(p) S_lm(alpha_p), S_lm the spline through column lm -- the reference's per-pixel spline through the real
+ *                     part of the synthesised rows, with the two linear steps in the other order;
+ *   k_at_alpha[p]   = the per-pixel spline through K_r(p) = M_r / (P0_r - P_r . r(p)) at alpha_p, P_r = -(the charge vector of the four
+ *                     l <= 1 columns of row r), M_r = sqrt(P0^2 - |P|^2), r(p) = (sin theta cos phi, -sin theta sin phi, cos theta): 4 pi times the same charge vector of
+ *                     the four unit-mode grids, whose y component is Im(a_1-1 + a_11) / sqrt(24 pi);
+ *   modes_out c16[nm] = map2salm((psi_at_alpha - salm2map(D map2salm(alpha))) / k_at_alpha^3), D_l = (l+2)(l+1)l(l-1)/4, 0 below l = 2.
+ * All three are host arrays and each may be NULL, not all; with modes_out == NULL the entry is "a real series on a cut" (K is formed only
+ * if k_at_alpha is asked for).  An output does not depend on which others are asked for.  A pixel whose alpha lies outside [t[0], t[n-1]] is
+ * evaluated as bms_spline_derivative evaluates a point outside its knots: the cubic of the end interval is continued (scipy's
+ * extrapolation), so the two agree there as well.  A row with P0^2 <= |P|^2 gives NaN or infinity in what depends on K, as the
+ * reference's sqrt does, and raises nothing.
+ * Bits: two calls give the same bits; a call on the rows [lo, hi) alone (with their times) gives the bits of the call on the whole
+ * series; row stride and kind of memory change no bit.
+ * BMS_ERR_INVALID: a NULL t, psi or alpha, every output NULL, ld < nm, negative sizes, a bad mem, a device array not aligned to 16 bytes,
+ * times that are not strictly increasing, a non-finite alpha.  BMS_ERR_UNSUPPORTED: ell_max < 2, ell_max > 24, fewer than 4 window rows, or
+ * (with K) a window whose forward sweep of one theta ring, 8 N (hi - lo) bytes, does not fit in LDS beside 8 (nm + 2 N + 5 (hi - lo)) + 2048
+ * bytes of tables (160 KB: 398 rows at ell_max = 24, 795 at 12).  All of it is found on the host before anything is launched and leaves the
+ * outputs untouched.  Stream-ordered on the context's stream up to the one wait behind the copies home.
+ *
+ * bms_alpha_perturbation: alpha_out f8[N][N] = Re salm2map(D^-1 map2salm(salm2map(psi_modes) + M K^3)) for one row psi_modes host c16[nm];
+ * m_grid, k_grid host f8[N][N], or NULL: the rest mass M / the conformal factor K(p) of psi_modes itself, as above.  BMS_ERR_INVALID: a NULL
+ * psi_modes or alpha_out, a negative ell_max; BMS_ERR_UNSUPPORTED: ell_max < 2 or > 24.  Both entries are timed as BMS_TAG_CUT (the grid <->
+ * mode steps and the spline sweeps under their own tags). */
+int bms_supermomentum_on_cut(bms_ctx* ctx, const double* t, int64_t n, const void* psi, int64_t ld, int mem, int ell_max, const double* alpha,
+                             void* modes_out, double* psi_at_alpha, double* k_at_alpha);
+int bms_alpha_perturbation(bms_ctx* ctx, const void* psi_modes, int ell_max, const double* m_grid, const double* k_grid, double* alpha_out);
 
 #ifdef __cplusplus
 }

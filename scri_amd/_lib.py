@@ -74,7 +74,7 @@ class bms_com_fit_result(ctypes.Structure):
                 ("t_f", ctypes.c_double), ("i_i", c_i64), ("i_f", c_i64), ("moments", (ctypes.c_double * 3) * 3)]
 
 
-KERNEL_TAGS = ("rotate", "setup", "gemm_synthesis", "spline_forward", "spline_backward", "gemm_analysis", "pointwise", "theta_quadrature", "analysis_fused", "analysis_large", "constraints")
+KERNEL_TAGS = ("rotate", "setup", "gemm_synthesis", "spline_forward", "spline_backward", "gemm_analysis", "pointwise", "theta_quadrature", "analysis_fused", "analysis_large", "constraints", "cut")
 
 # every symbol include/scri_amd.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -220,6 +220,8 @@ SIGNATURES = {
                               c_i64, c_int, c_int, ctypes.POINTER(c_vp), c_i64, c_vp]),
     "bms_product_launch_shape": (c_i64, [c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "bms_product_tables": (c_int, [c_int, c_int, c_int, c_dp, c_dp, c_dp]),
+    "bms_supermomentum_on_cut": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_dp, c_vp, c_dp, c_dp]),
+    "bms_alpha_perturbation": (c_int, [c_vp, c_vp, c_int, c_dp, c_dp, c_dp]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
 //   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair, Bondi charges (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets, bms_bondi_charges)
 //   engine_product.hip   products of two mode rows on Gauss-Legendre rows, mass aspect and supermomenta          (bms_mode_product, bms_supermomenta, bms_bondi_constraints, bms_product_tables)
+//   engine_cut.hip       a series of modes and its conformal factor on a supertranslated cut, the alpha perturbation   (bms_supermomentum_on_cut, bms_alpha_perturbation)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -778,6 +779,10 @@ BMS_INTERNAL int supermomenta_checks(bms_ctx* c, const void* psi2, int64_t ld_ps
                                      int* n_nodes);
 BMS_INTERNAL int constraint_checks(bms_ctx* c, const void* const in[CONSTRAINT_INPUTS], const int64_t ld[CONSTRAINT_INPUTS], int64_t n_times, int ell_max,
                                    int mem, const void* const violations[6], int64_t ld_out, const double* norms, unsigned* reads, int* n_nodes);
+// engine_cut.hip: the window rule of a cut's times and what bms_supermomentum_on_cut refuses before it selects a device
+BMS_INTERNAL void cut_window(const double* t, int64_t n, double amin, double amax, int64_t* lo, int64_t* hi);
+BMS_INTERNAL int cut_checks(bms_ctx* c, const double* t, int64_t n, const void* psi, int64_t ld, int mem, int ell_max, const double* alpha,
+                            const void* modes_out, const double* psi_at_alpha, const double* k_at_alpha, int64_t* lo, int64_t* hi);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

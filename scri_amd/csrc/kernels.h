@@ -527,6 +527,24 @@ hipError_t launch_expectation_values(hipStream_t stream, const double* a, long l
                                      long long n_times, int n_cols, const int* rows, const int* cols, const double* values, long long n_el,
                                      double* out);
 
+// ---- a real series and its conformal factor on a supertranslated cut (kernels_cut.hip; map_to_superrest_frame.py:108-224)
+// psi_out[p] = Re sum_k Y_k(p) spline_k(alpha[p]) over the (2 ell_max + 1)^2 pixels of the equiangular grid, from the window rows
+// W c16[n_window][ldw] (columns from l = 0), their spline slopes S (same shape) and the knots x; with_k: k_out[p] = the per-pixel spline
+// through K_r(p) = M_r / (P0_r - P_r . r(p)) at alpha[p] (1 otherwise); comb_out c16 = (psi - d_alpha) / K^3 (d_alpha c16 per pixel).
+// lambda f8[(ell_max + 1)^2][2 ell_max + 1]: sYlm(theta_i, 0) of spin 0 (build_synthesis).  Any output may be null.  One workgroup per
+// theta ring; cut_lds_bytes is its dynamic LDS (with K the forward sweep of a ring: 8 n_window (2 ell_max + 1) bytes of it).
+constexpr int CUT_MAX_ELL = 24;
+size_t cut_lds_bytes(int ell_max, long long n_window, int with_k);
+hipError_t launch_cut(hipStream_t stream, const double* W, const double* S, long long ldw, long long n_window, const double* x,
+                      const SplineTable* table, const double* lambda, const double* alpha, const double* d_alpha, int ell_max, int with_k,
+                      double* psi_out, double* k_out, double* comb_out);
+hipError_t launch_cut_real_to_complex(hipStream_t stream, const double* in, double* out, int n);  // c16 out = (in, 0)
+hipError_t launch_cut_real_part(hipStream_t stream, const double* in, double* out, int n);        // f8 out = Re of c16 in
+// modes c16[(ell_max + 1)^2] times (l+2)(l+1)l(l-1)/4, or with `inverse` its reciprocal; zero below l = 2
+hipError_t launch_cut_scale_modes(hipStream_t stream, double* modes, int ell_max, int inverse);
+// Re grid[p] += M(p) K(p)^3; m_grid / k_grid f8 per pixel, or null: the rest mass / conformal factor of the four l <= 1 columns of `modes`
+hipError_t launch_cut_mass_term(hipStream_t stream, double* grid, const double* modes, const double* m_grid, const double* k_grid, int ell_max);
+
 // centre-of-mass track and drift fit of the horizon trajectories (scri/SpEC/com_motion.py), kernels_com.hip
 constexpr int COM_FIT_TILE = 256;  // panels (two intervals each) per partial of the moment sums: one per thread of a workgroup
 constexpr int COM_FIT_OUT = 24;    // doubles of the fit's result block (com_fit_kernel)

@@ -1350,6 +1350,63 @@ def bondi_constraints(fields, psi_dot, sigma_dot, sigma_ddot, ell_max, want=(0, 
     return tuple(out[k][1] for k in want), norm_out
 
 
+CUT_NAMES = ("modes", "psi", "k")
+
+
+def supermomentum_on_cut(t, psi, alpha, ell_max, want=("modes",), ctx=None):
+    """bms_supermomentum_on_cut: the series psi [N, (ell_max + 1)^2] of spin-0 modes from l = 0 on the times t, evaluated on the cut
+    u = alpha, a real [2 ell_max + 1, 2 ell_max + 1] function on the equiangular grid.  want names "psi" (the real part of the series at
+    every pixel's own time, by not-a-knot cubic splines through the rows within 64 knots of alpha's range), "k" (the conformal factor of the
+    series' four-momentum there) and "modes" (the Moreschi supermomentum of the cut, map_to_superrest_frame.py:155-197).  psi is a numpy
+    array or a device tensor (complex128, unit column stride, any row stride: read where it is); the results are host arrays, in the
+    order of `want` (a tuple); one name as a string returns that array alone.  NotImplementedError: ell_max outside 2 .. 24, fewer than 4
+    rows, or a window too long for the kernel's LDS."""
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or len(set(names)) != len(names) or not set(names) <= set(CUT_NAMES):
+        raise ValueError(f"want names {', '.join(repr(k) for k in CUT_NAMES)}, got {want!r}")
+    ell_max = int(ell_max)
+    n_modes, n = (ell_max + 1) ** 2, 2 * ell_max + 1
+    t = np.ascontiguousarray(t, dtype=float)
+    if len(psi.shape) != 2 or psi.shape[1] != n_modes:
+        raise ValueError(f"psi must hold the (ell_max + 1)^2 = {n_modes} modes from l = 0 to ell_max = {ell_max} in every row; it has shape {tuple(psi.shape)}")
+    if t.shape != (psi.shape[0],):
+        raise ValueError(f"{psi.shape[0]} rows of modes on {t.shape} times")
+    alpha = np.ascontiguousarray(alpha, dtype=float)
+    if alpha.shape != (n, n):
+        raise ValueError(f"alpha must have shape ({n}, {n}); it has shape {alpha.shape}")
+    ctx = _ctx(ctx)
+    a = _stage(ctx, psi, np.complex128, "psi", shape=(t.shape[0], n_modes))
+    out = {"modes": np.empty(n_modes, dtype=np.complex128), "psi": np.empty((n, n)), "k": np.empty((n, n))}
+    ptr = lambda k, f: f(out[k]) if k in names else None  # noqa: E731
+    rc = _lib.load().bms_supermomentum_on_cut(ctx.handle, dptr(t), t.shape[0], a.ptr, a.ld, a.mem, ell_max, dptr(alpha), ptr("modes", vptr),
+                                              ptr("psi", dptr), ptr("k", dptr))
+    ctx.check(rc, "bms_supermomentum_on_cut")
+    res = tuple(out[k] for k in names)
+    return res[0] if isinstance(want, str) else res
+
+
+def alpha_perturbation(psi_modes, ell_max, m_grid=None, k_grid=None, ctx=None):
+    """bms_alpha_perturbation: Re salm2map(D^-1 map2salm(salm2map(psi_modes) + M K^3)) on the [2 ell_max + 1, 2 ell_max + 1] grid for one row
+    psi_modes [(ell_max + 1)^2] from l = 0 (map_to_superrest_frame.py:200-224).  m_grid, k_grid: real grids, or None: the rest mass / the
+    conformal factor of psi_modes' own four-momentum.  NotImplementedError: ell_max outside 2 .. 24."""
+    ell_max = int(ell_max)
+    n_modes, n = (ell_max + 1) ** 2, 2 * ell_max + 1
+    psi_modes = np.ascontiguousarray(psi_modes, dtype=np.complex128)
+    if psi_modes.shape != (n_modes,):
+        raise ValueError(f"psi_modes must hold the (ell_max + 1)^2 = {n_modes} modes from l = 0 to ell_max = {ell_max}; it has shape {psi_modes.shape}")
+    grids = []
+    for name, g in (("m_grid", m_grid), ("k_grid", k_grid)):
+        g = None if g is None else np.ascontiguousarray(g, dtype=float)
+        if g is not None and g.shape != (n, n):
+            raise ValueError(f"{name} must have shape ({n}, {n}); it has shape {g.shape}")
+        grids.append(g)
+    ctx = _ctx(ctx)
+    out = np.empty((n, n))
+    rc = _lib.load().bms_alpha_perturbation(ctx.handle, vptr(psi_modes), ell_max, *(dptr(g) if g is not None else None for g in grids), dptr(out))
+    ctx.check(rc, "bms_alpha_perturbation")
+    return out
+
+
 PRODUCT_COMPLEX, PRODUCT_REAL, PRODUCT_COMPLEX_4M = 0, 1, 2
 
 

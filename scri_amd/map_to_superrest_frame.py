@@ -5,12 +5,15 @@ supertranslation (Moreschi supermomentum -> its rest value), the rotation (spin 
 
 Every pass over the data runs on the GPU through the C ABI: `abd.transform` (the hot path itself), the charges
 (`bms_grid_multiply`, `bms_spline_derivative`), grid <-> mode maps (`bms_salm2map`, `bms_map2salm`) and the per-pixel time
-interpolation (`bms_spline_derivative`).  What is left here is the control loop and the algebra of the BMS group
-(`scri_amd.bms_transformations`).
+interpolation: the supermomentum on a supertranslated cut, a target's series on it and the alpha perturbation are one entry
+each (`bms_supermomentum_on_cut`, `bms_alpha_perturbation`), with the chains of building-block calls they replace kept as
+the `_composed` bodies -- the fallback where an entry answers "unsupported", and the other arm of tools/cut_rate.py.
+What is left here is the control loop and the algebra of the BMS group (`scri_amd.bms_transformations`).
 
 Built: the target-free iteration, a target Moreschi supermomentum, a target strain (rotation onto its angular velocity)
 and the "time_phase" step (scri_amd.alignment.align2d, this package's restatement of sxs.waveforms.alignment.align2d).
 """
+import contextlib
 import math
 
 import numpy as np
@@ -144,9 +147,44 @@ def _rows_near(t, times, reach=SPLINE_REACH):
     return max(lo, 0), min(hi, len(t))
 
 
+_ROUTE = {"cut": True}  # False: the composed bodies serve every call (composed_route)
+
+
+@contextlib.contextmanager
+def composed_route():
+    """Within the block the three helpers run their composed bodies: the A/B arm of tools/cut_rate.py and of the parity tests."""
+    was, _ROUTE["cut"] = _ROUTE["cut"], False
+    try:
+        yield
+    finally:
+        _ROUTE["cut"] = was
+
+
+def _modes_from_ell_0(series, ell_max):
+    """(t, [n, (ell_max + 1)^2] modes) of a series that the cut entries read where it is -- the buffer of a device-resident series,
+    else a host array -- or None: another l range than the entries take"""
+    if getattr(series, "ell_min", 0) != 0:
+        return None
+    data = series.buf if hasattr(series, "buf") else getattr(series, "ndarray", getattr(series, "data", series))
+    if len(data.shape) != 2 or data.shape[1] != (ell_max + 1) ** 2:
+        return None
+    return series.t, data
+
+
 def compute_Moreschi_supermomentum(PsiM, alpha, ell_max, ctx=None):
     """Moreschi supermomentum in the frame supertranslated by alpha (a real grid function): Eq. (9) of
-    doi:10.1063/1.532646 (map_to_superrest_frame.py:155-197)."""
+    doi:10.1063/1.532646 (map_to_superrest_frame.py:155-197), in one entry: a resident series is read in HBM."""
+    given = _modes_from_ell_0(PsiM, ell_max) if _ROUTE["cut"] else None
+    if given is not None:
+        try:
+            return engine.supermomentum_on_cut(given[0], given[1], alpha, ell_max, want="modes", ctx=ctx)
+        except NotImplementedError:  # (beyond the entry's ell_max or window, or a series too short for a cubic spline)
+            pass
+    return _compute_Moreschi_supermomentum_composed(PsiM, alpha, ell_max, ctx)
+
+
+def _compute_Moreschi_supermomentum_composed(PsiM, alpha, ell_max, ctx=None):
+    """compute_Moreschi_supermomentum as a chain of building-block calls through host memory"""
     t = PsiM.t
     lo, hi = _rows_near(t, alpha)
     # (a device-resident series hands over the rows around u = 0 only)
@@ -163,9 +201,38 @@ def compute_Moreschi_supermomentum(PsiM, alpha, ell_max, ctx=None):
 def compute_alpha_perturbation(PsiM, M_Grid, K_Grid, ell_max, ctx=None):
     """Supertranslation that removes the l >= 2 supermomentum to first order: Eq. (10) of doi:10.1063/1.532646
     (map_to_superrest_frame.py:200-224)."""
+    n = 2 * ell_max + 1
+    if _ROUTE["cut"] and np.shape(PsiM) == ((ell_max + 1) ** 2,) and np.shape(K_Grid) == (n, n) and np.shape(M_Grid) in ((), (n, n)):
+        try:
+            return engine.alpha_perturbation(PsiM, ell_max, np.broadcast_to(np.asarray(M_Grid, dtype=float), (n, n)), K_Grid, ctx=ctx)
+        except NotImplementedError:
+            pass
+    return _compute_alpha_perturbation_composed(PsiM, M_Grid, K_Grid, ell_max, ctx)
+
+
+def _compute_alpha_perturbation_composed(PsiM, M_Grid, K_Grid, ell_max, ctx=None):
+    """compute_alpha_perturbation as a chain of building-block calls through host memory"""
     PsiM_Grid = _to_grid(np.asarray(PsiM), ell_max, ctx)
     alpha = D_inverse(_to_modes(PsiM_Grid + M_Grid * K_Grid**3, ell_max, ctx), ell_max)
     return _to_grid(alpha, ell_max, ctx).real
+
+
+def _target_at(target_PsiM, times_grid, ell_max, ctx=None):
+    """the target's supermomentum as a real function on the cut u = times_grid: "a real series on a cut" of the same entry"""
+    given = _modes_from_ell_0(target_PsiM, ell_max) if _ROUTE["cut"] and target_PsiM.ell_max == ell_max else None
+    if given is not None:
+        try:
+            return engine.supermomentum_on_cut(given[0], given[1], times_grid, ell_max, want="psi", ctx=ctx)
+        except NotImplementedError:
+            pass
+    return _target_at_composed(target_PsiM, times_grid, ctx)
+
+
+def _target_at_composed(target_PsiM, times_grid, ctx=None):
+    """_target_at as a chain of building-block calls through host memory"""
+    lo, hi = _rows_near(target_PsiM.t, times_grid)
+    tg = _to_grid(np.asarray(target_PsiM.data)[lo:hi], target_PsiM.ell_max, ctx).real
+    return _interpolate_each_pixel(target_PsiM.t[lo:hi], tg, times_grid, ctx)
 
 
 def supertranslation_to_map_to_superrest_frame(abd, target_PsiM=None, N_itr_max=10, rel_err_tol=1e-12, ell_max=12, print_conv=False):
@@ -178,9 +245,7 @@ def supertranslation_to_map_to_superrest_frame(abd, target_PsiM=None, N_itr_max=
     PsiM = abd.supermomentum("Moreschi")
 
     def target_at(times_grid):
-        lo, hi = _rows_near(target_PsiM.t, times_grid)
-        tg = _to_grid(np.asarray(target_PsiM.data)[lo:hi], target_PsiM.ell_max, ctx).real
-        return _interpolate_each_pixel(target_PsiM.t[lo:hi], tg, times_grid, ctx)
+        return _target_at(target_PsiM, times_grid, ell_max, ctx)
 
     itr, rel_err, rel_errs = 0, np.inf, [np.inf]
     PsiM_interp = M_Grid = K_Grid = None
