@@ -772,6 +772,33 @@ int bms_supermomentum_on_cut(bms_ctx* ctx, const double* t, int64_t n, const voi
                              void* modes_out, double* psi_at_alpha, double* k_at_alpha);
 int bms_alpha_perturbation(bms_ctx* ctx, const void* psi_modes, int ell_max, const double* m_grid, const double* k_grid, double* alpha_out);
 
+/* ---- a raw finite-radius series retarded to tortoise time (scri/extrapolation.py:27-45 and :356-402), one radius per call -----------
+ * bms_finite_radius_retard: t, areal_radius, average_lapse host f8[n_raw] as a simulation writes them (coordinate times with the repeated
+ * stretches of restarts); data c16[n_raw][ld] (n_cols columns) and, if not NULL, frame f8[n_raw][4] in `mem`.
+ *   kept samples: k is kept iff fl(t[k] + min_time_step) < min_{j > k} t[j] -- the indices of monotonic_indices, as a suffix minimum and
+ *     an exclusive prefix sum of the mask; *n_kept is their number, K below, and k_0 < k_1 < ... are they;
+ *   g_j = lapse[k_j] / sqrt((-2E / R[k_j]) + 1), term_j = ((t[k_j] - t[k_j-1]) (g_j + g_j-1)) / 2 in the operation order of
+ *     scipy.integrate.cumulative_trapezoid, no fused multiply-add; their inclusive prefix sums are carried in double-double and rounded
+ *     to fp64 once per sample;
+ *   t_out[j] = (fl(sum_j + t[k_0]) - (R + 2E log(R / 2E - 1))) / ch_mass (t[k_0] itself for j = 0), radii_out[j] = R[k_j] / ch_mass;
+ *   data_out[j][m] = data[k_j][m] f_j, both components, f_j = fl(fl((R[k_j] / coord_radius)^p) unit_scale), p = radius_exponent formed by
+ *     repeated multiplication; frame_out[j] = frame[k_j].
+ * t_out and radii_out are host f8[n_raw], data_out c16[n_raw][ld_out] and frame_out f8[n_raw][4] live in `mem`: the caller allocates n_raw
+ * rows, the first K are the result.  Device rows from K on are not written; host entries from K on are unspecified.
+ * Bits: two calls give the same bits; row strides and the kind of memory change no bit; an element's arithmetic depends on no tile.
+ * BMS_ERR_INVALID, found on the host before anything is launched: a NULL series, data or output (frame_out with a frame), n_raw < 1,
+ * n_cols < 1, radius_exponent outside 1 .. 5, ch_mass == 0, coord_radius or initial_adm_energy not finite or <= 0, min_time_step < 0,
+ * ld or ld_out < n_cols, a time that is not finite, a bad mem, a device array not aligned to 16 bytes.  BMS_ERR_INVALID after the kernels:
+ * a KEPT radius that is not finite or <= 2E (counted on the device; the message names the first) -- the reference returns a NaN time axis
+ * there; the outputs are then written and not to be used.  A bad radius at a dropped sample is not read.
+ * Stream-ordered on the context's stream up to the one wait behind the copies home.  Timed as BMS_TAG_POINTWISE. */
+int bms_finite_radius_retard(bms_ctx* ctx, const double* t, const double* areal_radius, const double* average_lapse, int64_t n_raw,
+                             const void* data, int64_t ld, int n_cols, int mem, const double* frame, double coord_radius,
+                             double initial_adm_energy, double ch_mass, double unit_scale, int radius_exponent, double min_time_step,
+                             int64_t* n_kept, double* t_out, double* radii_out, void* data_out, int64_t ld_out, double* frame_out);
+/* samples per tile of the three scans (tests place restarts and lengths around it); a size, not a status */
+int64_t bms_retard_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

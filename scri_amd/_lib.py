@@ -222,6 +222,10 @@ SIGNATURES = {
     "bms_product_tables": (c_int, [c_int, c_int, c_int, c_dp, c_dp, c_dp]),
     "bms_supermomentum_on_cut": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_dp, c_vp, c_dp, c_dp]),
     "bms_alpha_perturbation": (c_int, [c_vp, c_vp, c_int, c_dp, c_dp, c_dp]),
+    "bms_finite_radius_retard": (c_int, [c_vp, c_dp, c_dp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.POINTER(c_i64), c_dp, c_dp, c_vp, c_i64,
+                                          c_vp]),
+    "bms_retard_tile": (c_i64, []),
 }
 
 _lib = None

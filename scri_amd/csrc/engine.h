@@ -15,6 +15,7 @@
 //   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair, Bondi charges (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets, bms_bondi_charges)
 //   engine_product.hip   products of two mode rows on Gauss-Legendre rows, mass aspect and supermomenta          (bms_mode_product, bms_supermomenta, bms_bondi_constraints, bms_product_tables)
 //   engine_cut.hip       a series of modes and its conformal factor on a supertranslated cut, the alpha perturbation   (bms_supermomentum_on_cut, bms_alpha_perturbation)
+//   engine_retard.hip    one raw finite-radius series retarded to tortoise time and scaled                      (bms_finite_radius_retard)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -783,6 +784,11 @@ BMS_INTERNAL int constraint_checks(bms_ctx* c, const void* const in[CONSTRAINT_I
 BMS_INTERNAL void cut_window(const double* t, int64_t n, double amin, double amax, int64_t* lo, int64_t* hi);
 BMS_INTERNAL int cut_checks(bms_ctx* c, const double* t, int64_t n, const void* psi, int64_t ld, int mem, int ell_max, const double* alpha,
                             const void* modes_out, const double* psi_at_alpha, const double* k_at_alpha, int64_t* lo, int64_t* hi);
+// engine_retard.hip: what bms_finite_radius_retard refuses before it selects a device
+BMS_INTERNAL int retard_checks(bms_ctx* c, const double* t, const double* areal_radius, const double* average_lapse, int64_t n_raw, const void* data,
+                               int64_t ld, int n_cols, int mem, const double* frame, double coord_radius, double initial_adm_energy, double ch_mass,
+                               double unit_scale, int radius_exponent, double min_time_step, const int64_t* n_kept, const double* t_out,
+                               const double* radii_out, const void* data_out, int64_t ld_out, const double* frame_out);
 BMS_INTERNAL void time_window(int64_t n, const bms_shard* sh, int64_t& lo, int64_t& hi);
 BMS_INTERNAL int validate_transformation(bms_ctx* c, int64_t n, const double* t, const bms_transformation* tr, int64_t n_min);
 BMS_INTERNAL int walk_time_axis(bms_ctx* c, const double* t, int64_t lo, int64_t hi, bool* regular);

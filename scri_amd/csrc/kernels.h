@@ -612,4 +612,20 @@ struct RadiusTerms {  // coef[k - 1] = amp R^-k, k = 1 .. n
 hipError_t launch_radius_terms(hipStream_t stream, const double* t, long long n, const double2* h0, long long ld0, int n_cols,
                                const RadiusTerms& terms, double2* out, long long ld_out);
 
+// ---- retardation of a raw finite-radius series to tortoise time (scri/extrapolation.py:27-45, :356-402; kernels_retard.hip)
+constexpr int RETARD_TILE = 256;  // samples per tile of the three scans: one per thread of a workgroup
+long long retard_tiles(long long n_raw);
+// idx[j] = the raw index of kept sample j -- k is kept iff fl(T[k] + min_step) < min_{j > k} T[j] -- and st[0] = their number, st[1] = 0,
+// st[2] = LLONG_MAX.  Work space: tile_min f8[tiles], rank i4[n_raw], count i8[tiles].  idx has n_raw entries, st three.
+hipError_t launch_retard_keep(hipStream_t stream, const double* T, long long n_raw, double min_step, double* tile_min, int* rank,
+                              long long* count, long long* idx, long long* st);
+// for kept sample j < st[0]: t_out[j], radii_out[j] and factor[j] = fl(fl((R / coord_radius)^p) unit) (kernels_retard.hip states the
+// arithmetic); st[1] += the kept radii that are not finite or not beyond 2 E, st[2] = the raw index of the first.  totals: 16 bytes per tile.
+hipError_t launch_retard_time(hipStream_t stream, const double* T, const double* R, const double* lapse, long long n_raw, const long long* idx,
+                              long long* st, double initial_adm_energy, double coord_radius, double ch_mass, double unit, int p, void* totals,
+                              double* t_out, double* radii_out, double* factor);
+// out c16[r][m] = in[idx[r]][m] * factor[r] for r < st[0], m < n_cols (factor == nullptr: the rows as they are); rows beyond are not written
+hipError_t launch_retard_gather(hipStream_t stream, const void* in, long long ld, int n_cols, long long n_raw, const long long* idx,
+                                const double* factor, const long long* st, void* out, long long ld_out);
+
 }  // namespace bms

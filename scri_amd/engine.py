@@ -1801,3 +1801,75 @@ def com_fit(t, com, skip_beginning_fraction=0.01, skip_ending_fraction=0.10, fit
     ctx.check(rc, "bms_com_fit")
     return dict(x_i=np.array(res.x_i), v_i=np.array(res.v_i), a_i=np.array(res.a_i), t_i=np.float64(res.t_i), t_f=np.float64(res.t_f),
                 i_i=int(res.i_i), i_f=int(res.i_f), moments=np.array([list(row) for row in res.moments]))
+
+
+# ---------------------------------------------------------------------------------- raw finite-radius series -> tortoise time
+
+
+def retard_tile():
+    """samples per tile of the scans behind finite_radius_retard (bms_retard_tile)"""
+    return int(_lib.load().bms_retard_tile())
+
+
+def _rows_arg(ctx, x, dtype, what, n, cols=None):
+    """(_Arg, array kept alive) of [n, cols] rows of `dtype` with unit column stride and any row stride >= cols: a device tensor, or a
+    numpy array, whose row view is passed as it is (anything else is copied to a contiguous array)"""
+    if _is_device_array(x):
+        return _stage(ctx, x, dtype, what, shape=(n, cols))
+    a = np.asarray(x)
+    item = np.dtype(dtype).itemsize
+    if a.dtype != np.dtype(dtype) or a.ndim != 2 or (a.shape[1] > 1 and a.strides[1] != item) or a.strides[0] % item or a.strides[0] < item * a.shape[1]:
+        a = np.ascontiguousarray(a, dtype=dtype)
+    if a.ndim != 2 or a.shape[0] != n or (cols is not None and a.shape[1] != cols):
+        raise ValueError(f"{what} must have shape ({n}, {'n' if cols is None else cols}); it has shape {a.shape}")
+    ld = a.strides[0] // item if n > 1 else max(a.shape[1], 1)
+    return _Arg(c_vp(a.ctypes.data), ld, n, a.shape[1], BMS_HOST, (a.shape[1],), a, None)
+
+
+def finite_radius_retard(t, areal_radius, average_lapse, data, coord_radius, initial_adm_energy, ch_mass, unit_scale, radius_exponent,
+                         frame=None, min_time_step=1.0e-3, out=None, ctx=None):
+    """One raw finite-radius series retarded to tortoise time (bms_finite_radius_retard; scri/extrapolation.py:27-45, :356-402).
+
+    t, areal_radius, average_lapse: the raw series f8[n_raw]; data [n_raw, n_cols] complex128 and frame [n_raw, 4] float64 (or None):
+    numpy arrays (row views with a stride are read as they are) or device tensors with unit column stride, all in one kind of memory.
+    out: an array [n_raw, >= n_cols] of that kind that receives the rows, or None for a new one.
+    Returns (t_out[K], radii_out[K], data_out[K, n_cols], frame_out[K, 4] or None) for the K kept samples: the times and radii are
+    numpy arrays, the rows and the frame views of arrays of n_raw rows in the memory of `data`."""
+    ctx = _ctx(ctx)
+    t = np.ascontiguousarray(t, dtype=float)
+    n = t.shape[0]
+    r = np.ascontiguousarray(areal_radius, dtype=float)
+    lapse = np.ascontiguousarray(average_lapse, dtype=float)
+    if t.ndim != 1 or r.shape != (n,) or lapse.shape != (n,):
+        raise ValueError(f"times of shape {t.shape}, areal radii of shape {r.shape} and lapses of shape {lapse.shape}: expected three series of one length")
+    if n < 1:
+        raise ValueError("bms_finite_radius_retard: n_raw = 0: at least one sample")
+    a = _rows_arg(ctx, data, np.complex128, "data", n)
+    n_cols = a.cols
+    if out is None:
+        out_ptr, out = out_like(a, (n, n_cols), np.complex128)
+        ld_out = n_cols
+    else:
+        if _is_device_array(out) != (a.mem == BMS_DEVICE):
+            raise ValueError("data and out must live in the same memory")
+        if a.mem == BMS_HOST and (not isinstance(out, np.ndarray) or out.dtype != np.complex128 or not out.flags.writeable):
+            raise ValueError("out must be a writeable complex128 array")
+        o = _rows_arg(ctx, out[:, :n_cols] if out.shape[1] >= n_cols else out, np.complex128, "out", n, n_cols)
+        if a.mem == BMS_HOST and not np.shares_memory(o.keep, out):
+            raise ValueError("out must have unit column stride and a row stride that is a multiple of 16 bytes")
+        out_ptr, ld_out = o.ptr, o.ld
+    f = fo = fo_ptr = None
+    if frame is not None:
+        if _is_device_array(frame) != (a.mem == BMS_DEVICE):
+            raise ValueError("data and frame must live in the same memory")
+        f = _stage(ctx, frame, float, "frame", shape=(n, 4), contiguous=_is_device_array(frame))
+        fo_ptr, fo = out_like(f, (n, 4), float)
+    kept = c_i64(0)
+    t_out, r_out = np.empty(n), np.empty(n)
+    rc = _lib.load().bms_finite_radius_retard(
+        ctx.handle, dptr(t), dptr(r), dptr(lapse), n, a.ptr, a.ld, n_cols, a.mem, f.ptr if f else None, float(coord_radius),
+        float(initial_adm_energy), float(ch_mass), float(unit_scale), int(radius_exponent), float(min_time_step), ctypes.byref(kept),
+        dptr(t_out), dptr(r_out), out_ptr, ld_out, fo_ptr)
+    ctx.check(rc, "bms_finite_radius_retard")
+    k = int(kept.value)
+    return t_out[:k], r_out[:k], out[:k, :n_cols], (fo[:k] if fo is not None else None)

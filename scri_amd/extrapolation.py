@@ -2,6 +2,9 @@
 
     monotonic_indices   scri/extrapolation.py:27-45
     intersection        scri/extrapolation.py:47-125 (mode_operators.time_intersection)
+    finite_radius_waveform  scri/extrapolation.py:343-417 from :356 on (read_finite_radius_waveform behind its file reader): the raw series
+                        of one radius retarded to tortoise time and scaled on the GPU (bms_finite_radius_retard)
+    finite_radius_data  scri/extrapolation.py:419-537 (read_finite_radius_data) on groups held in memory
     set_common_time     scri/extrapolation.py:539-554, the radii and the waveforms through the GPU cubic spline
     _Extrapolate        scri/extrapolation.py:1270-1474, the per-time-step fit in 1/r on the GPU (bms_extrapolate)
     extrapolate_waveforms   the steps of the file driver `extrapolate` (:744-853) between reading and writing the files
@@ -14,12 +17,13 @@ import warnings
 
 import numpy as np
 
-from . import Inertial, Corotating, psi0, psi1
+from . import Inertial, Corotating, h, hdot, psi0, psi1, psi2, psi3, psi4
 from . import engine
 from .mode_operators import time_intersection as intersection
 from .waveform_modes import WaveformModes
 
-__all__ = ["monotonic_indices", "intersection", "set_common_time", "_Extrapolate", "extrapolate_waveforms"]
+__all__ = ["monotonic_indices", "intersection", "finite_radius_waveform", "finite_radius_data", "set_common_time", "_Extrapolate",
+           "extrapolate_waveforms"]
 
 
 def monotonic_indices(T, MinTimeStep=1.0e-3):
@@ -33,6 +37,114 @@ def monotonic_indices(T, MinTimeStep=1.0e-3):
             kept.pop()
         kept.append(k)
     return np.array(kept, dtype=int)
+
+
+def _mass_scaling(dataType, ChMass):
+    """(UnitScaleFactor, RadiusRatioExp) of scri/extrapolation.py:364-386"""
+    table = {h: (1.0 / ChMass, 1), hdot: (1.0, 1), psi4: (ChMass, 1), psi3: (1.0, 2), psi2: (1.0 / ChMass, 3), psi1: (1.0 / ChMass**2, 4),
+             psi0: (1.0 / ChMass**3, 5)}
+    if dataType not in table:
+        raise ValueError(f'DataType "{dataType}" is unknown.')
+    return table[dataType]
+
+
+def finite_radius_waveform(t, data, ArealRadius, AverageLapse, CoordRadius, InitialAdmEnergy, ChMass, dataType, ell_min=2, ell_max=None,
+                           frame=None, MinTimeStep=1.0e-3, ctx=None):
+    """One finite-radius waveform as a simulation writes it -> (W, Radii) on the retarded time axis, with the mass scaled out: what
+    scri's read_finite_radius_waveform does after it has read its file (scri/extrapolation.py:356-417), on the GPU
+    (bms_finite_radius_retard).
+
+    t, ArealRadius, AverageLapse: the raw series, one value per written step (coordinate times, with the repeated stretches of
+    restarts).  data [len(t), n_modes]: the modes in code units, a numpy array or a device tensor, which is read where it is; W is then
+    device resident.  frame: None or [len(t), 4].  The raw arrays are taken rather than a WaveformModes because a waveform on a
+    restarting time axis is not a valid one.
+
+    The steps monotonic_indices(t, MinTimeStep) names are kept; their times become the cumulative trapezoid of
+    AverageLapse / sqrt(1 - 2 InitialAdmEnergy / ArealRadius) minus the tortoise coordinate, over ChMass; Radii = ArealRadius / ChMass;
+    every row of modes is multiplied by (ArealRadius / CoordRadius)^p UnitScaleFactor, p and the factor by dataType.
+    A kept radius that is not finite or not beyond 2 InitialAdmEnergy raises ValueError (the reference: a NaN time axis and a warning)."""
+    if ChMass == 0.0:
+        raise ValueError("ChMass=0.0 is not a valid input value.")
+    unit, p = _mass_scaling(dataType, ChMass)
+    n_cols = int(data.shape[1])
+    if ell_max is None:
+        ell_max = int(round(np.sqrt(n_cols + ell_min**2))) - 1
+    if n_cols != engine.LM_total_size(ell_min, ell_max):
+        raise ValueError(f"data of {n_cols} columns do not hold the modes of ell = {ell_min} .. {ell_max}")
+    if ctx is None:
+        from . import _lib
+
+        ctx = _lib.default_context()
+    resident = hasattr(data, "data_ptr")
+    if resident:
+        from . import device_series
+
+        dev = device_series.attach(ctx)
+        if frame is not None and not hasattr(frame, "data_ptr"):
+            frame = device_series._torch().from_numpy(np.ascontiguousarray(frame, dtype=float)).to(dev)
+    T, Radii, rows, frame_out = engine.finite_radius_retard(t, ArealRadius, AverageLapse, data, CoordRadius, InitialAdmEnergy, ChMass, unit, p,
+                                                            frame=frame, min_time_step=MinTimeStep, ctx=ctx)
+    if frame_out is None:
+        frame_out = np.empty((0, 4))
+    elif resident:
+        frame_out = frame_out.cpu().numpy()
+    history = f"# extrapolation.read_finite_radius_waveform({CoordRadius}, {InitialAdmEnergy}, {dataType}, {ChMass})"
+    W = WaveformModes(t=T.copy(), frame=frame_out, data=np.empty((0, n_cols), dtype=complex) if resident else rows, ell_min=ell_min, ell_max=ell_max,
+                      frameType=Inertial, dataType=dataType, r_is_scaled_out=True, m_is_scaled_out=True, ctx=ctx)
+    W.history = [history]  # (the one line, as the reference assigns it: :415)
+    if resident:
+        W._host, W._dev = None, rows
+    return W, Radii.copy()
+
+
+def finite_radius_data(groups, ChMass=0.0, CoordRadii=[], ctx=None):
+    """(Ws, Radii, CoordRadii) of the groups of a finite-radius file held in memory: the selection rules and errors of scri's
+    read_finite_radius_data (scri/extrapolation.py:419-537) around finite_radius_waveform.  groups: an ordered mapping from names such as
+    "R0247.dir" to the keyword arguments of finite_radius_waveform (without ChMass and ctx).  CoordRadii: empty for every group, integers
+    for positions, or strings searched in the names as regular expressions.  The file, its validation and the progress messages are
+    out of scope."""
+    import numbers
+    import re
+
+    if ChMass == 0.0:
+        raise ValueError("ChMass=0.0 is not a valid input value.")
+    radius_of = re.compile(r"""R(?P<r>.*?)\.dir""")
+
+    def radius_string(name):
+        m = radius_of.search(str(name))
+        if not m:
+            raise ValueError(f"Could not parse radius from waveform name {name!r}")
+        return m.group("r")
+
+    names = [name for name in groups if name != "VersionHist.ver"]
+    all_names = list(names)
+    if not CoordRadii:
+        CoordRadii = [m.group("r") for name in names for m in [radius_of.search(name)] if m]
+    elif isinstance(CoordRadii[0], numbers.Integral):
+        names = [names[i] for i in CoordRadii]
+        CoordRadii = [radius_string(name) for name in names]
+    else:
+        names = [name for name in names for radius in CoordRadii for m in [re.compile(radius).search(name)] if m]
+        try:
+            CoordRadii = [radius_string(name) for name in names]
+        except Exception:
+            pass
+    if not names:
+        raise ValueError("No waveform groups matched the requested CoordRadii. "
+                         f"Requested CoordRadii={CoordRadii}; available groups={all_names}.")
+    if len(names) != len(CoordRadii):
+        raise ValueError("Mismatch between requested radii and matched waveform groups. "
+                         f"Requested CoordRadii={CoordRadii}; matched groups={names}.")
+    try:
+        [float(r) for r in CoordRadii]
+    except Exception as e:
+        raise ValueError(f"Could not convert CoordRadii entries to float: CoordRadii={CoordRadii}") from e
+    Ws, Radii = [], []
+    for name in names:
+        W, R = finite_radius_waveform(ChMass=ChMass, ctx=ctx, **groups[name])
+        Ws.append(W)
+        Radii.append(R)
+    return Ws, Radii, CoordRadii
 
 
 def _resident(W):

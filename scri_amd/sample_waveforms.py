@@ -3,7 +3,8 @@ constant and single-mode data, random data, the single mode proportional to time
 (the known answer of tests/test_waveform_grid.py), and the precessing binary `fake_precessing_waveform` (:383-593) with the
 finite-radius family the reference builds on it (:596-755).  The first group are host-side generators; what is done WITH them runs on
 the GPU.  The precessing waveform is generated on the GPU itself, per time step (bms_precessing_waveform), and may stay there.  Of
-`create_fake_finite_radius_strain_h5file` the in-memory core is here, `fake_finite_radius_waveforms`; the HDF5 file is not written."""
+`create_fake_finite_radius_strain_h5file` the in-memory core is here, `fake_finite_radius_waveforms`, and what it writes, as arrays in
+memory, `fake_finite_radius_data`; the HDF5 file is not written."""
 import math
 import warnings
 from fractions import Fraction
@@ -294,3 +295,45 @@ def fake_finite_radius_waveforms(n_subleading=3, amp=1.0, t_0=0.0, t_1=3000.0, d
         Radii.append(np.full(h0.n_times, R))
     ctx.synchronize()
     return Ws, Radii, (h0 if device else h0.to_host())
+
+
+def fake_finite_radius_data(n_subleading=3, amp=1.0, t_0=0.0, t_1=3000.0, dt=0.1, r_min=100.0, r_max=600.0, n_radii=24, ell_max=8,
+                            initial_adm_energy=0.99, avg_lapse=0.99, avg_areal_radius_diff=1.0, mass_ratio=1.0, precession_opening_angle=0.0,
+                            device=False, ctx=None, **kwargs):
+    """What `create_fake_finite_radius_strain_h5file` writes (scri/sample_waveforms.py:704-745), in memory: an ordered mapping from the
+    group names "R0100.dir" ... to the keyword arguments of extrapolation.finite_radius_waveform, so that
+    `extrapolation.finite_radius_data(fake_finite_radius_data(...), 1.0)` is the reference's file followed by its reader.
+
+    Every group is on all_times = linspace(0, t_1 + r_max, N + int(r_max / dt)) with constant coordinate radius, areal radius (larger by
+    avg_areal_radius_diff) and lapse; its modes are those of fake_finite_radius_waveforms at that radius, moved to the simulation time
+    (t + r*) sqrt(1 - 2E/R) / lapse, r* = R + 2E log(R / 2E - 1), splined onto all_times (engine.cubic_spline), zero outside the warped
+    range, plus the drift (1 + i) 1e-14 t.  The two deliberate differences of fake_finite_radius_waveforms hold here as well.
+    device=True leaves the modes of every group on the device."""
+    from . import _lib, device_series, engine
+
+    ctx = ctx if ctx is not None else _lib.default_context()
+    Ws, Radii, h0 = fake_finite_radius_waveforms(n_subleading=n_subleading, amp=amp, t_0=t_0, t_1=t_1, dt=dt, r_min=r_min, r_max=r_max,
+                                                 n_radii=n_radii, ell_max=ell_max, avg_areal_radius_diff=avg_areal_radius_diff,
+                                                 mass_ratio=mass_ratio, precession_opening_angle=precession_opening_angle, device=True, ctx=ctx,
+                                                 **kwargs)
+    coord_radii = (1 / np.linspace(1 / r_min, 1 / r_max, n_radii)).astype(int)
+    n_times = int(h0.t.shape[0] + r_max / dt)
+    all_times = np.linspace(0, t_1 + r_max, n_times)
+    torch = device_series._torch()
+    dev = device_series.attach(ctx)
+    drift = torch.from_numpy(((1 + 1j) * 1e-14 * all_times).reshape(-1, 1)).to(dev)
+    groups = {}
+    for coord_radius, W, R_series in zip(coord_radii, Ws, Radii):
+        R = float(R_series[0])
+        tortoise_coord = R + 2 * initial_adm_energy * np.log(R / (2 * initial_adm_energy) - 1)
+        simulation_time = (h0.t + tortoise_coord) * np.sqrt(1 - 2 * initial_adm_energy / R) / avg_lapse
+        data = engine.cubic_spline(simulation_time, W._dev, all_times, ctx=ctx)
+        outside = torch.from_numpy((all_times < simulation_time[0]) | (all_times > simulation_time[-1])).to(dev)
+        data[outside] = 0.0
+        data += drift
+        groups[f"R{coord_radius:04}.dir"] = dict(
+            t=all_times.copy(), data=data if device else data.cpu().numpy(), ArealRadius=np.full(n_times, R),
+            AverageLapse=np.full(n_times, float(avg_lapse)), CoordRadius=float(coord_radius), InitialAdmEnergy=float(initial_adm_energy),
+            dataType=h, ell_min=h0.ell_min, ell_max=h0.ell_max)
+    ctx.synchronize()
+    return groups
