@@ -125,7 +125,7 @@ enum bms_kernel_tag {
   BMS_TAG_THETA_QUADRATURE = 7, /* theta_quadrature_kernel (second step of the unfused separable analysis) */
   BMS_TAG_ANALYSIS_FUSED = 8,   /* analysis_split_kernel / analysis_fused_kernel (phi-DFT on MFMA + theta quadrature, one kernel) */
   BMS_TAG_ANALYSIS_LARGE = 9,   /* phi_dft_folded_kernel + theta_quadrature_mfma_kernel (grids with n_theta > 40) */
-  BMS_TAG_CONSTRAINTS = 10,     /* constraint_kernel (bms_bondi_constraints) */
+  BMS_TAG_CONSTRAINTS = 10,     /* constraint_kernel (bms_bondi_constraints), bianchi_kernel (bms_bianchi_rhs) */
   BMS_TAG_CUT = 11,             /* cut_kernel and the pointwise kernels around it (bms_supermomentum_on_cut, bms_alpha_perturbation) */
   BMS_TAG_COUNT = 12
 };
@@ -730,6 +730,26 @@ int bms_supermomenta(bms_ctx* ctx, const void* psi2, int64_t ld_psi2, const void
 int bms_bondi_constraints(bms_ctx* ctx, const void* const fields[6], const int64_t ld_fields[6], const void* const psi_dot[3],
                           const int64_t ld_psi_dot[3], const void* sigma_dot, int64_t ld_sigma_dot, const void* sigma_ddot,
                           int64_t ld_sigma_ddot, int64_t n_times, int ell_max, int mem, void* const violations[6], int64_t ld_out, double* norms);
+/* one stage of the Bianchi identities run forwards (scri/asymptotic_bondi_data/from_initial_values.py:128-154): what the constraint
+ * kernel subtracts from a given derivative, stored.  Rows c16 with (ell_max + 1)^2 columns from l = 0, each array with its own row stride,
+ * 2 <= ell_max.  Mode by mode, with the GHP eth, bar and the truncated product of bms_bondi_constraints,
+ *   rhs[c] = f(l, 1 - k) a[c] + (3 - k) (sigma b)[c],   f(l, s) = sqrt((l - s)(l + s + 1)) / sqrt(2), zero for l < |s| or l < |s + 1|,
+ * evaluated as written per real and imaginary part (two products, one sum);
+ *   k = 1: a = psi2 (spin 0), b = psi3 (spin -1)          k = 0: a = psi1 (spin 1), b = psi2 (spin 0)
+ *   k = 2, the head: a = sigma_dot and b = sigma_ddot as stored (spin 2);  psi4 = -bar(b),  psi3 = -f(l, -2) bar(a),
+ *                    rhs = f(l, -1) psi3 + sigma psi4;  psi3 and psi4 c16[n_times][ld_psi] are written as well
+ * psi3 and psi4 are required at k = 2 and must be NULL at k = 1 and k = 0 (ld_psi is then not read).  The product is the one
+ * bms_mode_product forms of sigma (spin 2) and b (spin -k) truncated at ell_max, bit for bit; its columns below l = |2 - k| are exact zeros
+ * and input columns below the operand's spin are never read by it; the diagonal term reads `a` as stored.  The time integral between the
+ * stages is the caller's (bms_spline_derivative of order -1).
+ * BMS_ERR_INVALID: k outside 0 .. 2, a NULL that is needed, psi3 or psi4 given where it is not written, a row stride below (ell_max + 1)^2,
+ * negative sizes, a bad mem, misaligned device arrays; BMS_ERR_UNSUPPORTED: ell_max < 2, an ell_max beyond the library's or a time step that
+ * does not fit in LDS (bms_product_launch_shape of (ell_max, ell_max, ell_max)).  Found on the host before anything is launched.
+ * n_times == 0 writes nothing and returns before the device is asked for its LDS.  The bit guarantees of bms_mode_product hold: two calls
+ * give the same bits, a slice of the time steps gives the bits of the whole call, row strides and the kind of memory change no bit.  The
+ * tables are those of the product family, kept per context.  Timed as BMS_TAG_CONSTRAINTS, beside the kernel whose inner step it is. */
+int bms_bianchi_rhs(bms_ctx* ctx, int k, const void* sigma, int64_t ld_sigma, const void* a, int64_t ld_a, const void* b, int64_t ld_b,
+                    int64_t n_times, int ell_max, int mem, void* rhs, int64_t ld_rhs, void* psi3, void* psi4, int64_t ld_psi);
 /* how the product kernel runs on the current device: shape[0] time steps per pass of one workgroup (returned as well, 0 if the rows and
  * panels of one time step do not fit in LDS), shape[1] workgroups at most, shape[2] != 0 if the tables are held in LDS (they are read
  * through L2); sizes, not a status */

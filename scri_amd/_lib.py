@@ -218,6 +218,7 @@ SIGNATURES = {
     "bms_supermomenta": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
     "bms_bondi_constraints": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_vp, c_i64, c_vp, c_i64,
                               c_i64, c_int, c_int, ctypes.POINTER(c_vp), c_i64, c_vp]),
+    "bms_bianchi_rhs": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_i64]),
     "bms_product_launch_shape": (c_i64, [c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "bms_product_tables": (c_int, [c_int, c_int, c_int, c_dp, c_dp, c_dp]),
     "bms_supermomentum_on_cut": (c_int, [c_vp, c_dp, c_i64, c_vp, c_i64, c_int, c_int, c_dp, c_vp, c_dp, c_dp]),

@@ -66,13 +66,93 @@ def _as_row(x, nm):
     return x.astype(complex)
 
 
-def from_initial_values(cls, time, ell_max=8, sigma0=0.0, sigmadot0=0.0, sigmaddot0=0.0, psi2=0.0, psi1=0.0, psi0=0.0, ctx=None):
+def _resident_from_shear(cls, time, L, sigma0, psi2, psi1, psi0, ctx):
+    """from_initial_values for a shear series in HBM: sigma0 a device tensor [n_times, (L + 1)^2] or a DeviceModesTimeSeries of spin 2.
+    The statements of the host route, stage by stage (bms_bianchi_rhs) with the time integrals between the stages
+    (bms_spline_derivative of order -1), written into the [6, N, nm] tensor of a device-resident object.  Only one-row arrays cross PCIe:
+    the three constant rows go up, one row of the Moreschi supermomentum comes down for the imaginary part of psi2 at time[0]."""
+    from . import _lib, device_series
+    from .device_series import DeviceModesTimeSeries
+
+    torch = device_series._torch()
+    nm = (L + 1) ** 2
+    if isinstance(sigma0, DeviceModesTimeSeries):
+        if sigma0.spin_weight != 2:
+            raise ValueError(f"Input `sigma0` must have spin weight 2; it has {sigma0.spin_weight}")
+        ctx = ctx if ctx is not None else sigma0._ctx
+        sigma0 = sigma0._from_ell_0()
+    ctx = ctx if ctx is not None else _lib.default_context()
+    u = np.array(time, dtype=float)
+    n = u.size if u.ndim == 1 else 0
+    abd = cls(u, L, multiplication_truncator=max, ctx=ctx, _raw=device_series.empty(ctx, (6, n, nm)), device=True)
+    if tuple(sigma0.shape) != (n, nm):
+        raise ValueError(f"Input `sigma0` must have shape {(n, nm)}; it has {tuple(sigma0.shape)}")
+    if sigma0.dtype != torch.complex128:
+        raise ValueError(f"Input `sigma0` must be a complex128 device array; it is {sigma0.dtype}")
+    engine._on_device_of(ctx, sigma0)
+    psi2 = _zero_below_spin(_as_row(psi2, nm), 0)
+    psi1 = _zero_below_spin(_as_row(psi1, nm), 1)
+    psi0 = _zero_below_spin(_as_row(psi0, nm), 2)
+    raw = abd._raw_dev  # psi0 .. psi4, sigma
+    sig = raw[5]
+    sig.copy_(sigma0)
+    sig[:, :4].zero_()
+    d = lambda x, k: engine.spline_derivative(u, x, u, k, ctx=ctx)  # noqa: E731
+    # field = the integral of rhs from time[0] plus a constant row, written where the field lives
+    settle = lambda field, rhs, row: torch.add(d(rhs, -1), device_series.to_device(ctx, row), out=raw[field])  # noqa: E731
+    if L >= 2 and engine.product_launch_shape(L, L, L) is not None:
+        sdot = d(sig, 1)
+        rhs = device_series.empty(ctx, (n, nm))
+        engine.bianchi_rhs(2, sig, sdot, d(sig, 2), L, ctx=ctx, out=(rhs, raw[3], raw[4]))
+        # psi2 + eth^2 sigma-bar + sigma sigma-bar-dot at time[0] with psi2 = 0: what fixes Im psi2 there
+        zero = torch.zeros((1, nm), dtype=torch.complex128, device=sig.device)
+        at_0 = device_series.to_host(engine.supermomenta(zero, sig[:1], sdot[:1], L, want="moreschi", ctx=ctx))
+        settle(2, rhs, _real(psi2, L) - 1j * _imag(at_0, L))
+        engine.bianchi_rhs(1, sig, raw[2], raw[3], L, ctx=ctx, out=rhs)
+        settle(1, rhs, psi1)
+        engine.bianchi_rhs(0, sig, raw[1], raw[2], L, ctx=ctx, out=rhs)
+        settle(0, rhs, psi0)
+        return abd
+    # no shear below ell = 2, or a time step beyond the kernel's LDS: the same statements from the series operators
+    series = lambda i, s: DeviceModesTimeSeries(raw[i], u, s, 0, L, ctx=ctx, multiplication_truncator=max)  # noqa: E731
+    S = series(5, 2)
+    sb = S.bar
+    sbdot = sb.dot
+    raw[4].copy_((-sb.ddot).buf)
+    raw[3].copy_((-sbdot.eth_GHP).buf)
+    sb_0, sbdot_0, sig_0 = sb.rows(0, 1), sbdot.rows(0, 1), S.rows(0, 1)
+    adjust = _real(psi2, L) - 1j * _imag(_eth(_eth(sb_0, -2, L), -1, L) + _mul(sig_0, 2, sbdot_0, -2, L, ctx), L)
+    settle(2, (series(3, -1).eth_GHP + S * series(4, -2)).buf, adjust)
+    settle(1, (series(2, 0).eth_GHP + 2 * (S * series(3, -1))).buf, psi1)
+    settle(0, (series(1, 1).eth_GHP + 3 * (S * series(2, 0))).buf, psi0)
+    return abd
+
+
+def from_initial_values(cls, time, ell_max=8, sigma0=0.0, sigmadot0=0.0, sigmaddot0=0.0, psi2=0.0, psi1=0.0, psi0=0.0, ctx=None, device=None):
     """Bondi data from the shear and initial values of psi2, psi1, psi0.
 
     sigma0 of dimension 0 or 1: sigma = sigma0 + u sigmadot0 + u^2 sigmaddot0 / 2 and everything is integrated exactly as
     polynomials in u (values given at u = 0).  sigma0 of dimension 2 ([n_times, modes]): sigma as a function of time; the
-    rest is integrated with cubic splines from the values at time[0]."""
+    rest is integrated with cubic splines from the values at time[0].
+
+    A shear series may live in HBM: sigma0 a device tensor [n_times, (ell_max + 1)^2] (complex128, unit column stride) or a
+    DeviceModesTimeSeries of spin 2.  The result is then device-resident and nothing of the series' size crosses PCIe
+    (_resident_from_shear).  device=True takes that route for a numpy series too, uploaded once, and is `.to_device()` of the result
+    for the polynomial branch; device=False brings a resident result home; None leaves the result where sigma0 is."""
+    from .device_series import DeviceModesTimeSeries
+
     L = int(ell_max)
+    resident = engine._is_device_array(sigma0) or isinstance(sigma0, DeviceModesTimeSeries)
+    if resident or (device and np.ndim(sigma0) == 2):
+        if not resident:
+            from . import _lib, device_series
+
+            ctx = ctx if ctx is not None else _lib.default_context()
+            sigma0 = device_series.to_device(ctx, sigma0)
+        abd = _resident_from_shear(cls, time, L, sigma0, psi2, psi1, psi0, ctx)
+        return abd.to_host() if device is not None and not device else abd
+    if device:
+        return from_initial_values(cls, time, L, sigma0, sigmadot0, sigmaddot0, psi2, psi1, psi0, ctx=ctx).to_device(ctx)
     nm = (L + 1) ** 2
     abd = cls(time, L, multiplication_truncator=max, ctx=ctx)
     u = abd.time

@@ -13,7 +13,7 @@
 //   engine_sample.hip    the precessing sample waveform and its finite-radius family                         (bms_precessing_waveform, bms_radius_terms)
 //   engine_com.hip       centre-of-mass track of the horizon trajectories and the fit of its drift           (bms_com_motion, bms_com_fit)
 //   engine_flux.hip      the four fluxes in one pass over the modes, sparse expectation values, brackets of a pair, Bondi charges (bms_poincare_fluxes, bms_expectation_values, bms_pair_brackets, bms_bondi_charges)
-//   engine_product.hip   products of two mode rows on Gauss-Legendre rows, mass aspect and supermomenta          (bms_mode_product, bms_supermomenta, bms_bondi_constraints, bms_product_tables)
+//   engine_product.hip   products of two mode rows on Gauss-Legendre rows, mass aspect and supermomenta          (bms_mode_product, bms_supermomenta, bms_bondi_constraints, bms_bianchi_rhs, bms_product_tables)
 //   engine_cut.hip       a series of modes and its conformal factor on a supertranslated cut, the alpha perturbation   (bms_supermomentum_on_cut, bms_alpha_perturbation)
 //   engine_retard.hip    one raw finite-radius series retarded to tortoise time and scaled                      (bms_finite_radius_retard)
 #pragma once
@@ -780,6 +780,9 @@ BMS_INTERNAL int supermomenta_checks(bms_ctx* c, const void* psi2, int64_t ld_ps
                                      int* n_nodes);
 BMS_INTERNAL int constraint_checks(bms_ctx* c, const void* const in[CONSTRAINT_INPUTS], const int64_t ld[CONSTRAINT_INPUTS], int64_t n_times, int ell_max,
                                    int mem, const void* const violations[6], int64_t ld_out, const double* norms, unsigned* reads, int* n_nodes);
+BMS_INTERNAL int bianchi_checks(bms_ctx* c, int k, const void* sigma, int64_t ld_sigma, const void* a, int64_t ld_a, const void* b, int64_t ld_b,
+                                int64_t n_times, int ell_max, int mem, const void* rhs, int64_t ld_rhs, const void* psi3, const void* psi4, int64_t ld_psi,
+                                int* n_nodes);
 // engine_cut.hip: the window rule of a cut's times and what bms_supermomentum_on_cut refuses before it selects a device
 BMS_INTERNAL void cut_window(const double* t, int64_t n, double amin, double amax, int64_t* lo, int64_t* hi);
 BMS_INTERNAL int cut_checks(bms_ctx* c, const double* t, int64_t n, const void* psi, int64_t ld, int mem, int ell_max, const double* alpha,

@@ -1,6 +1,6 @@
 // Products of spin-weighted functions on Gauss-Legendre rows (kernels_product.hip): the nodes and weights (Newton iteration on P_n) and the
 // tables lambda^s_lm(theta_j) = sYlm(theta_j, 0), built on the host in long double and rounded once, kept on the device per context and
-// (spin, ell_max, n_nodes); the entries bms_mode_product, bms_supermomenta and bms_bondi_constraints, their launch shape and the pure host export of the tables
+// (spin, ell_max, n_nodes); the entries bms_mode_product, bms_supermomenta, bms_bondi_constraints and bms_bianchi_rhs, their launch shape and the pure host export of the tables
 // (engine.h: the split of the engine by entry family; include/scri_amd.h: the C ABI)
 #include "engine.h"
 
@@ -363,5 +363,60 @@ extern "C" int bms_bondi_constraints(bms_ctx* c, const void* const fields[6], co
   if ((rc = io.out("constraint_norms", norms, (size_t)n_times * N_VIOLATIONS, &Q.norms))) return rc;
   Q.ld_out = io.host() ? n_modes : ld_out;
   TIMED(c, BMS_TAG_CONSTRAINTS, launch_bondi_constraints(c->stream, Q, n_times));
+  return io.finish();
+} BMS_CATCH(c)
+
+// ---- one stage of the Bianchi identities run forwards (bianchi_kernel)
+// what bms_bianchi_rhs refuses before it selects a device
+BMS_INTERNAL int bianchi_checks(bms_ctx* c, int k, const void* sigma, int64_t ld_sigma, const void* a, int64_t ld_a, const void* b, int64_t ld_b,
+                                int64_t n_times, int ell_max, int mem, const void* rhs, int64_t ld_rhs, const void* psi3, const void* psi4, int64_t ld_psi,
+                                int* n_nodes) {
+  const char* who = "bms_bianchi_rhs";
+  if (k < 0 || k > 2) return fail(c, BMS_ERR_INVALID, "%s: k = %d names no stage (2: the head, then 1, then 0)", who, k);
+  if (!sigma || !a || !b || !rhs) return fail(c, BMS_ERR_INVALID, "%s: NULL sigma, a, b or rhs", who);
+  if (k == 2 && (!psi3 || !psi4)) return fail(c, BMS_ERR_INVALID, "%s: NULL psi3 or psi4, which the head (k = 2) writes", who);
+  if (k != 2 && (psi3 || psi4)) return fail(c, BMS_ERR_INVALID, "%s: psi3 and psi4 are written by the head (k = 2) alone and must be NULL at k = %d", who, k);
+  if (n_times < 0) return fail(c, BMS_ERR_INVALID, "%s: negative n_times", who);
+  if (ell_max < 0) return fail(c, BMS_ERR_INVALID, "%s: negative ell_max", who);
+  if (ell_max < 2) return fail(c, BMS_ERR_UNSUPPORTED, "%s: ell_max = %d: the shear starts at ell = 2", who, ell_max);
+  if (int rc = product_size_checks(c, who, 2, ell_max, -k, ell_max, ell_max, n_times, n_nodes)) return rc;
+  const int64_t n_modes = LM_total_size(0, ell_max);
+  if (ld_sigma < n_modes || ld_a < n_modes || ld_b < n_modes)
+    return fail(c, BMS_ERR_INVALID, "%s: row stride of sigma, a or b smaller than the (ell_max + 1)^2 = %lld columns read", who, (long long)n_modes);
+  if (ld_rhs < n_modes || (k == 2 && ld_psi < n_modes))
+    return fail(c, BMS_ERR_INVALID, "%s: row stride of rhs or of psi3 and psi4 smaller than the (ell_max + 1)^2 = %lld columns written", who, (long long)n_modes);
+  if (mem == BMS_DEVICE && (((uintptr_t)sigma | (uintptr_t)a | (uintptr_t)b | (uintptr_t)rhs | (uintptr_t)psi3 | (uintptr_t)psi4) & 15))
+    return fail(c, BMS_ERR_INVALID, "%s: device arrays must be aligned to their elements", who);
+  return BMS_OK;
+}
+
+extern "C" int bms_bianchi_rhs(bms_ctx* c, int k, const void* sigma, int64_t ld_sigma, const void* a, int64_t ld_a, const void* b, int64_t ld_b,
+                               int64_t n_times, int ell_max, int mem, void* rhs, int64_t ld_rhs, void* psi3, void* psi4, int64_t ld_psi) try {
+  if (!c) return BMS_ERR_INVALID;
+  const char* who = "bms_bianchi_rhs";
+  if (int rc0 = entry_mem(c, mem, who, false)) return rc0;  // (the argument checks come before the device is selected)
+  int rc, n_nodes = 0;
+  if ((rc = bianchi_checks(c, k, sigma, ld_sigma, a, ld_a, b, ld_b, n_times, ell_max, mem, rhs, ld_rhs, psi3, psi4, ld_psi, &n_nodes))) return rc;
+  if (n_times == 0) return BMS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  ProductShape S;
+  if (!product_launch_shape(ell_max, ell_max, ell_max, &S))
+    return fail(c, BMS_ERR_UNSUPPORTED, "%s: ell_max %d on %d rows: the rows and panels of one time step do not fit in LDS", who, ell_max, n_nodes);
+  BianchiArgs Q{};
+  Q.k = k, Q.l_max = ell_max, Q.n_nodes = n_nodes;
+  if ((rc = ensure_product_table(c, 2, ell_max, n_nodes, false, &Q.tab_sigma))) return rc;
+  if ((rc = ensure_product_table(c, -k, ell_max, n_nodes, false, &Q.tab_b))) return rc;
+  if ((rc = ensure_product_table(c, 2 - k, ell_max, n_nodes, true, &Q.tab_out))) return rc;
+  const int n_modes = LM_total_size(0, ell_max);
+  CallIO io(c, mem);
+  if ((rc = io.in("in_data", sigma, ((size_t)(n_times - 1) * ld_sigma + n_modes) * 16, &Q.sigma))) return rc;
+  if ((rc = io.in("in_aux0", a, ((size_t)(n_times - 1) * ld_a + n_modes) * 16, &Q.a))) return rc;
+  if ((rc = io.in("in_aux1", b, ((size_t)(n_times - 1) * ld_b + n_modes) * 16, &Q.b))) return rc;
+  if ((rc = io.out_rows("bianchi_rhs", rhs, (size_t)n_times, (size_t)2 * n_modes, (size_t)2 * ld_rhs, &Q.rhs))) return rc;
+  if ((rc = io.out_rows("bianchi_psi3", psi3, (size_t)n_times, (size_t)2 * n_modes, (size_t)2 * ld_psi, &Q.psi3))) return rc;
+  if ((rc = io.out_rows("bianchi_psi4", psi4, (size_t)n_times, (size_t)2 * n_modes, (size_t)2 * ld_psi, &Q.psi4))) return rc;
+  Q.ld_sigma = ld_sigma, Q.ld_a = ld_a, Q.ld_b = ld_b;
+  Q.ld_rhs = io.host() ? n_modes : ld_rhs, Q.ld_psi = io.host() ? n_modes : ld_psi;
+  TIMED(c, BMS_TAG_CONSTRAINTS, launch_bianchi_rhs(c->stream, Q, n_times));
   return io.finish();
 } BMS_CATCH(c)

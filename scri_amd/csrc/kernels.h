@@ -521,6 +521,19 @@ struct ConstraintArgs {
   double* norms;
 };
 hipError_t launch_bondi_constraints(hipStream_t stream, const ConstraintArgs& Q, long long n_times);
+// One stage of the Bianchi identities run forwards (bianchi_kernel: the inner step of constraint_kernel, stored instead of subtracted):
+//     rhs_k = eth a + (3 - k) sigma b     k = 1: a = psi2, b = psi3     k = 0: a = psi1, b = psi2
+//     k = 2 (the head): a = sigma_dot, b = sigma_ddot as stored;  psi4 = -bar(b), psi3 = -eth bar(a), rhs_2 = eth psi3 + sigma psi4
+// Rows c16[n][ld] from l = 0.  psi3, psi4 c16[n][ld_psi]: written by the head alone, null otherwise.
+struct BianchiArgs {
+  const double *sigma, *a, *b;
+  long long ld_sigma, ld_a, ld_b;
+  int k, l_max, n_nodes;                    // n_nodes = product_nodes(l_max, l_max, l_max)
+  const double *tab_sigma, *tab_b, *tab_out;  // lambda tables of spins 2, -k and 2 - k (the last with 2 pi w_j folded)
+  double *rhs, *psi3, *psi4;
+  long long ld_rhs, ld_psi;
+};
+hipError_t launch_bianchi_rhs(hipStream_t stream, const BianchiArgs& Q, long long n_times);
 // out c16[n] = sum_e op(a[t][rows_e]) values_e b[t][cols_e] for triplets on the device, indices inside [0, n_cols) (the entry checks them)
 int expectation_max_cols();
 hipError_t launch_expectation_values(hipStream_t stream, const double* a, long long ld_a, int conj_a, const double* b, long long ld_b,

@@ -317,6 +317,60 @@ __global__ __launch_bounds__(PRODUCT_THREADS) void constraint_kernel(ConstraintA
   }
 }
 
+// One stage of the Bianchi identities run forwards (scri/asymptotic_bondi_data/from_initial_values.py:128-154): the inner step of
+// constraint_kernel, stored where that kernel subtracts it from a given derivative.
+//     rhs_k = eth a + (3 - k) sigma b       k = 1: a = psi2 (spin 0), b = psi3 (spin -1)      k = 0: a = psi1 (spin 1), b = psi2 (spin 0)
+// k = 2, the head, takes sigma_dot and sigma_ddot as stored (spin 2) for a and b and forms, mode by mode,
+//     psi4 = -bar(sigma_ddot)      psi3 = -eth bar(sigma_dot)      rhs_2 = eth psi3 + sigma psi4
+// psi4 is negated in LDS by the thread that loaded the column and goes through the product from there, so the product is the one
+// product_kernel forms of sigma and the stored psi4; psi3 at a column is formed by the thread that stores rhs_2 there.  sigma and
+// sigma_ddot are read once, sigma_dot once in mirrored column order.  The diagonal term reads `a` from memory as stored.
+// LDS: two rows and the three panels of product_kernel at (l, l, l).
+__global__ __launch_bounds__(PRODUCT_THREADS) void bianchi_kernel(BianchiArgs Q, long long n_times) {
+#pragma clang fp contract(off)
+  extern __shared__ double2 product_lds[];
+  const int k = Q.k, l_max = Q.l_max, n = Q.n_nodes, nc = (l_max + 1) * (l_max + 1), width = 2 * l_max + 1;
+  double2* row_s = product_lds;  // sigma
+  double2* row_b = row_s + nc;   // psi2, psi3 or psi4
+  double2* pan_s = row_b + nc;
+  double2* pan_b = pan_s + n * width;
+  double2* pan_g = pan_b + n * width;
+  const bool head = k == 2;
+  const double times = (double)(3 - k);
+  for (long long step = blockIdx.x; step < n_times; step += gridDim.x) {  // (uniform in the workgroup: every wave takes every barrier)
+    load_row(row_s, Q.sigma + 2 * step * Q.ld_sigma, nc, 2, 0);
+    load_row(row_b, Q.b + 2 * step * Q.ld_b, nc, head ? 2 : -k, head);
+    if (head)  // (the columns this thread has just loaded)
+      for (int c = threadIdx.x; c < nc; c += PRODUCT_THREADS) {
+        const double2 v = row_b[c], p4 = double2{-v.x, -v.y};
+        row_b[c] = p4;
+        *reinterpret_cast<double2*>(Q.psi4 + 2 * (step * Q.ld_psi + c)) = p4;
+      }
+    __syncthreads();
+    theta_sums(pan_s, row_s, Q.tab_sigma, l_max, 2, n);
+    theta_sums(pan_b, row_b, Q.tab_b, l_max, -k, n);
+    __syncthreads();
+    convolution(pan_g, pan_s, l_max, pan_b, l_max, l_max, n);
+    __syncthreads();
+    for (int c = threadIdx.x; c < nc; c += PRODUCT_THREADS) {
+      const int l = ell_of_column(c), m = c - l * (l + 1);
+      const double2 prod = quadrature(pan_g, Q.tab_out, c, l, l_max, 2 - k, n);
+      double2 q;
+      if (head) {
+        const double2 b = bar_of(*reinterpret_cast<const double2*>(Q.a + 2 * (step * Q.ld_a + l * (l + 1) - m)), 2 + m);
+        const double f2 = eth_ghp_factor(l, -2);
+        q = double2{-(f2 * b.x), -(f2 * b.y)};
+        *reinterpret_cast<double2*>(Q.psi3 + 2 * (step * Q.ld_psi + c)) = q;
+      } else {
+        q = *reinterpret_cast<const double2*>(Q.a + 2 * (step * Q.ld_a + c));
+      }
+      const double f = eth_ghp_factor(l, 1 - k);
+      *reinterpret_cast<double2*>(Q.rhs + 2 * (step * Q.ld_rhs + c)) = double2{f * q.x + times * prod.x, f * q.y + times * prod.y};
+    }
+    __syncthreads();  // (the rows and panels of this step are read until here)
+  }
+}
+
 int product_compute_units() {
   int dev = 0, cus = 0;
   (void)hipGetDevice(&dev);
@@ -400,6 +454,23 @@ hipError_t launch_bondi_constraints(hipStream_t stream, const ConstraintArgs& Q,
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(constraint_kernel, dim3((unsigned)std::min<long long>(S.groups, n_times)), dim3(PRODUCT_THREADS), lds, stream, Q, n_times);
+  return hipGetLastError();
+}
+
+hipError_t launch_bianchi_rhs(hipStream_t stream, const BianchiArgs& Q, long long n_times) {
+  if (n_times <= 0) return hipSuccess;
+  ProductShape S;
+  if (Q.k < 0 || Q.k > 2 || Q.l_max < 2 || Q.n_nodes != product_nodes(Q.l_max, Q.l_max, Q.l_max) || !product_launch_shape(Q.l_max, Q.l_max, Q.l_max, &S))
+    return hipErrorInvalidValue;
+  const long long n_modes = (long long)(Q.l_max + 1) * (Q.l_max + 1);
+  if (!Q.sigma || !Q.a || !Q.b || !Q.rhs || !Q.tab_sigma || !Q.tab_b || !Q.tab_out || (Q.k == 2) != (Q.psi3 != nullptr) || (Q.k == 2) != (Q.psi4 != nullptr))
+    return hipErrorInvalidValue;
+  if (Q.ld_sigma < n_modes || Q.ld_a < n_modes || Q.ld_b < n_modes || Q.ld_rhs < n_modes || (Q.k == 2 && Q.ld_psi < n_modes)) return hipErrorInvalidValue;
+  if (S.lds_bytes > 64 * 1024) {
+    hipError_t e = allow_dynamic_lds((const void*)bianchi_kernel);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(bianchi_kernel, dim3((unsigned)std::min<long long>(S.groups, n_times)), dim3(PRODUCT_THREADS), S.lds_bytes, stream, Q, n_times);
   return hipGetLastError();
 }
 

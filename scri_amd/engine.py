@@ -1350,6 +1350,51 @@ def bondi_constraints(fields, psi_dot, sigma_dot, sigma_ddot, ell_max, want=(0, 
     return tuple(out[k][1] for k in want), norm_out
 
 
+def _rows_out(arg, out, n_modes, what):
+    """(address, row stride) of the device tensor `out` [arg.rows, n_modes] (complex128, unit column stride, any row stride) that a
+    device call writes in place"""
+    if arg.mem != BMS_DEVICE:
+        raise ValueError("out= names device arrays; with host inputs the results are new host arrays")
+    if (not _is_device_array(out) or out.dtype != _torch_dtype(np.complex128) or out.device != arg.device or tuple(out.shape) != (arg.rows, n_modes)
+            or (n_modes > 1 and out.stride(1) != 1)):
+        raise ValueError(f"{what}: expected a complex128 device array ({arg.rows}, {n_modes}) with unit column stride on {arg.device}")
+    return c_vp(out.data_ptr()), _row_stride(out, arg.rows, n_modes)
+
+
+def bianchi_rhs(k, sigma, a, b, ell_max, ctx=None, out=None):
+    """bms_bianchi_rhs: one stage of the Bianchi identities run forwards, rhs = eth a + (3 - k) sigma b with the GHP eth and the product
+    truncated at ell_max, every array [N, (ell_max + 1)^2] from l = 0.  k = 1: a = psi2, b = psi3; k = 0: a = psi1, b = psi2; k = 2 (the
+    head): a = sigma_dot, b = sigma_ddot as stored, and psi4 = -bar(b), psi3 = -eth bar(a), rhs = eth psi3 + sigma psi4.  numpy arrays
+    (numpy arrays out) or device tensors (complex128, unit column stride, any row stride: device tensors out), all in one memory.
+    out: the device tensor the result is written into, (rhs, psi3, psi4) of them at k = 2 -- row views of wider tensors are written through
+    their row stride.  Returns rhs, or (rhs, psi3, psi4) at k = 2."""
+    ctx = _ctx(ctx)
+    k, ell_max = int(k), int(ell_max)
+    n_modes = (ell_max + 1) ** 2
+    S = _stage(ctx, sigma, np.complex128, "sigma", shape=(None, n_modes))
+    A = _stage(ctx, a, np.complex128, "a", shape=(S.rows, n_modes))
+    B = _stage(ctx, b, np.complex128, "b", shape=(S.rows, n_modes))
+    if A.mem != S.mem or B.mem != S.mem:
+        raise ValueError("sigma, a and b must live in the same memory")
+    n_out = 3 if k == 2 else 1
+    if out is None:
+        made = [out_like(S, (S.rows, n_modes), np.complex128) for _ in range(n_out)]
+        ptrs, lds, res = [p for p, _ in made], [n_modes] * n_out, [o for _, o in made]
+    else:
+        res = list(out) if isinstance(out, (tuple, list)) else [out]
+        if len(res) != n_out:
+            raise ValueError(f"out names {len(res)} arrays; stage k = {k} writes {n_out}")
+        homes = [_rows_out(S, o, n_modes, name) for o, name in zip(res, ("rhs", "psi3", "psi4"))]
+        ptrs, lds = [p for p, _ in homes], [ld for _, ld in homes]
+        if n_out == 3 and lds[1] != lds[2]:
+            raise ValueError("psi3 and psi4 share one row stride")
+    if S.rows:
+        psi = (ptrs[1], ptrs[2], lds[1]) if n_out == 3 else (None, None, 0)
+        rc = _lib.load().bms_bianchi_rhs(ctx.handle, k, S.ptr, S.ld, A.ptr, A.ld, B.ptr, B.ld, S.rows, ell_max, S.mem, ptrs[0], lds[0], *psi)
+        ctx.check(rc, "bms_bianchi_rhs")
+    return tuple(res) if n_out == 3 else res[0]
+
+
 CUT_NAMES = ("modes", "psi", "k")
 
 

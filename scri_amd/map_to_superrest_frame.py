@@ -58,8 +58,14 @@ def MT_to_WM(h_mts, sxs_version=False, dataType=None):
 
 
 def WM_to_MT(h_wm):
-    """A WaveformModes as a ModesTimeSeries with the same l range (map_to_superrest_frame.py:55-73), products truncated at max"""
+    """A WaveformModes as a ModesTimeSeries with the same l range (map_to_superrest_frame.py:55-73), products truncated at max.  A
+    device-resident waveform gives a DeviceModesTimeSeries over its device buffer: nothing is copied and the waveform stays resident."""
     from .modes_time_series import ModesTimeSeries
+
+    if getattr(h_wm, "is_device_resident", False):
+        from .device_series import DeviceModesTimeSeries
+
+        return DeviceModesTimeSeries(h_wm._dev, h_wm.t, h_wm.spin_weight, h_wm.ell_min, h_wm.ell_max, ctx=h_wm._ctx, multiplication_truncator=max)
 
     return ModesTimeSeries(np.array(h_wm.data), h_wm.t, spin_weight=h_wm.spin_weight, ell_min=h_wm.ell_min, ell_max=h_wm.ell_max,
                            multiplication_truncator=max)

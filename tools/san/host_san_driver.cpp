@@ -846,6 +846,27 @@ void flux_tables_and_triplets() {
     REQUIRE(bms_bondi_constraints(&dummy, in + 1, ld6, in + 1, ld6, v, 16, v, 16, 4, 3, BMS_HOST, nullptr, 16, nullptr) == BMS_ERR_INVALID && says("every output"));
     REQUIRE(bms_bondi_constraints(nullptr, in + 1, ld6, in + 1, ld6, v, 16, v, 16, 4, 3, BMS_HOST, homes, 16, out) == BMS_ERR_INVALID);
   }
+  // a stage of the Bianchi identities run forwards: which stage writes psi3 and psi4, and what the entry refuses
+  REQUIRE(bianchi_checks(&dummy, 2, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, out, out, 16, &nn) == BMS_OK && nn == 5);
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 17, v, 18, 4, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_OK && nn == 5);
+  REQUIRE(bianchi_checks(&dummy, 0, v, 16, v, 16, v, 16, 0, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_OK);
+  REQUIRE(bianchi_checks(&dummy, 3, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("names no stage"));
+  REQUIRE(bianchi_checks(&dummy, -1, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("names no stage"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, nullptr, 16, v, 16, 4, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("NULL sigma, a, b or rhs"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, nullptr, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("NULL sigma, a, b or rhs"));
+  REQUIRE(bianchi_checks(&dummy, 2, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, out, nullptr, 16, &nn) == BMS_ERR_INVALID && says("NULL psi3 or psi4"));
+  REQUIRE(bianchi_checks(&dummy, 0, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, nullptr, out, 16, &nn) == BMS_ERR_INVALID && says("must be NULL at k = 0"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 15, 4, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("columns read"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 15, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("columns written"));
+  REQUIRE(bianchi_checks(&dummy, 2, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, out, out, 15, &nn) == BMS_ERR_INVALID && says("columns written"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 16, -1, 3, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("negative n_times"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 16, 4, -1, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("negative ell_max"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 16, 4, 1, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_UNSUPPORTED && says("ell_max = 1"));
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v, 16, v, 16, 4, MAX_ELL + 1, BMS_HOST, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_UNSUPPORTED);
+  REQUIRE(bianchi_checks(&dummy, 1, v, 16, v + 1, 16, v, 16, 4, 3, BMS_DEVICE, out, 16, nullptr, nullptr, 0, &nn) == BMS_ERR_INVALID && says("aligned"));
+  REQUIRE(bms_bianchi_rhs(&dummy, 1, v, 16, v, 16, v, 16, 4, 3, 7, out, 16, nullptr, nullptr, 0) == BMS_ERR_INVALID && says("bms_bianchi_rhs: mem is BMS_HOST or BMS_DEVICE, got 7"));
+  REQUIRE(bms_bianchi_rhs(&dummy, 2, v, 16, v, 16, v, 16, 0, 3, BMS_HOST, out, 16, out, out, 16) == BMS_OK);
+  REQUIRE(bms_bianchi_rhs(nullptr, 1, v, 16, v, 16, v, 16, 4, 3, BMS_HOST, out, 16, nullptr, nullptr, 0) == BMS_ERR_INVALID);
 }
 
 }  // namespace
